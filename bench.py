@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- scenes/sec of D3Net's training step on MI355X (BASELINE.json metric).
 
-    python bench.py [--config speaker|detector|listener|joint] --gpus N --steps K --warmup W [--scaling weak|strong]
+    python bench.py [--config speaker|detector|listener|joint] --gpus N --steps K --warmup W [--scaling weak|strong] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 With N > 1 and no WORLD_SIZE in the environment bench.py starts its N ranks ITSELF (one child process group through
@@ -64,7 +64,13 @@ def parse():
                     help="time the step at the REFERENCE'S precision (minkowski.set_exact: fp32 storage, fp32 MFMA convolutions) instead of bf16")
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak",
                     help="weak: the config's scenes per rank per step (4); strong: the GLOBAL batch is fixed at 8 scenes, 8/N per rank")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (loss, the step's output dict, the updated "
+                         "parameters) as DIR/<name>.npy, float32 / float64, at most 64 MB in all (larger arrays: a fixed seeded sample)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 CPU_THREADS = 8            # default thread count of the CPU baseline child (the parent sweeps CPU_THREAD_SWEEP; all 256 hardware threads of the GPU box: 1000x slower)
@@ -104,6 +110,76 @@ def make_dataset(n_scenes, chunk, joint):
     if joint:
         ds.chunked_data, ds.organized = S.make_language_corpus(n_scenes, chunk=chunk, vocab=VOCAB)
     return {"train": ds}
+
+
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000      # (64 MB, decimal: also under 64 MiB)
+
+
+def _dump_leaves(obj, prefix, out):
+    """(name, value) of every leaf of a nested dict / list / tuple, dict keys in sorted order"""
+    if isinstance(obj, dict):
+        for k in sorted(obj, key=str):
+            _dump_leaves(obj[k], "%s.%s" % (prefix, k) if prefix else str(k), out)
+    elif isinstance(obj, (list, tuple)):
+        for i, v in enumerate(obj):
+            _dump_leaves(v, "%s.%d" % (prefix, i), out)
+    else:
+        out.append((prefix, obj))
+
+
+def dump_outputs(outdir, outputs, meta=None, budget=DUMP_BUDGET_BYTES):
+    """Write every numeric leaf of `outputs` (tensors on any device, numpy arrays, Python numbers) as outdir/<name>.npy:
+    floating point as float32 (float64 stays float64), integers and booleans as float64.  The files together stay within
+    `budget` bytes: the budget is shared out smallest array first, and an array over its share is replaced by the values at
+    a sorted sample of flat indices drawn by numpy's default_rng seeded with the crc32 of its name -- the same indices in
+    every run with the same shapes.  outdir/manifest.json records each array's source name, shape, dtype and sample size
+    (and `meta`)."""
+    import re
+    import zlib
+    import numpy as np
+    import torch
+    leaves = []
+    _dump_leaves(outputs, "", leaves)
+    arrays, used = [], set()
+    for name, v in leaves:
+        if isinstance(v, (bool, int, float)):
+            v = np.asarray(v, dtype=np.float64)
+        if isinstance(v, np.ndarray):
+            v = torch.from_numpy(v)
+        if not torch.is_tensor(v) or v.dtype.is_complex:
+            continue
+        v = v.detach()
+        dt = torch.float32 if v.is_floating_point() and v.dtype != torch.float64 else torch.float64
+        fname = re.sub(r"[^A-Za-z0-9_.-]", "_", name) or "value"
+        base, n = fname, 1
+        while fname in used:
+            n += 1
+            fname = "%s_%d" % (base, n)
+        used.add(fname)
+        arrays.append((fname, name, v, dt))
+    os.makedirs(outdir, exist_ok=True)
+    manifest, todo = {}, len(arrays)
+    meta_json = json.dumps(meta)
+    left = budget - 4096 * (todo + 1) - len(meta_json)      # (.npy headers and the manifest)
+    for fname, name, v, dt in sorted(arrays, key=lambda a: (a[2].numel() * (4 if a[3] == torch.float32 else 8), a[0])):
+        item = 4 if dt == torch.float32 else 8
+        k = min(v.numel(), (left // todo) // item)
+        flat = v.reshape(-1)
+        sampled = k < v.numel()
+        if sampled:
+            idx = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(v.numel(), k, replace=False))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        a = flat.to(dt).cpu().numpy()
+        if not sampled:
+            a = a.reshape(tuple(v.shape))
+        np.save(os.path.join(outdir, fname + ".npy"), a)
+        left -= a.nbytes
+        todo -= 1
+        manifest[fname] = {"name": name, "shape": list(v.shape), "dtype": str(v.dtype).replace("torch.", ""),
+                           "sampled": int(k) if sampled else None}
+    with open(os.path.join(outdir, "manifest.json"), "w") as f:
+        json.dump({"budget_bytes": budget, "arrays": dict(sorted(manifest.items())), "meta": meta}, f, indent=1)
+    return manifest
 
 
 def code_sha():
@@ -676,6 +752,14 @@ def main():
     hg_shapes = kernels.pop("__hg_shapes__", [])
     L.d3_prof_enable(0)
     final_loss = float(loss.detach())
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed step receives from its last run: the loss, the output dict and the parameters AdamW updated
+        names = [n for n, p in model.named_parameters() if p.requires_grad]
+        dump_outputs(args.dump_outputs, {"loss": loss, "outputs": d,
+                                         "params": torch.cat([p.detach().reshape(-1).float() for p in params])},
+                     meta={"config": config, "steps": args.steps, "warmup": args.warmup, "settle": settle_steps,
+                           "params_layout": [[n, list(p.shape)] for n, p in zip(names, params)]})
+        torch.cuda.synchronize()
 
     # reference precision beside the bf16 number: a few untimed-for-`value` steps with the exact-fp32 kernels
     fp32 = None
