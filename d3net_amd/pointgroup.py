@@ -915,6 +915,22 @@ class PointGroup(nn.Module):
         empty.update(pick=pick, scores=sig[pick], cross_ious=ious)
         return empty
 
+    def evaluate_segmentation(self, batches, evaluator=None):
+        """ScanNet instance AP / semantic IoU of the predictions over `batches` (collated batches with GT), in place of the
+        reference's test() files + scripts/eval.py evaluate_instance / evaluate_semantic: predict_instances in eval() mode, the
+        counting of each batch on the device (seg_eval.SegmentationEvaluator) -> (instance averages dict, semantic IoU dict)"""
+        from .seg_eval import SegmentationEvaluator
+        ev = evaluator if evaluator is not None else SegmentationEvaluator()
+        was_training = self.training
+        self.eval()
+        try:
+            for batch in batches:
+                gt = {k: batch[k] for k in ("sem_labels", "instance_ids", "batch_offsets", "instance_offsets") if k in batch}
+                ev.add_batch(self.predict_instances(batch), gt)
+        finally:
+            self.train(was_training)
+        return ev.instance_results()[0], ev.semantic_results()[0]
+
     def training_step(self, data_dict, idx=0):
         """(reference :513-528) minus the Lightning logging."""
         _mark("begin")

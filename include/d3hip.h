@@ -712,6 +712,28 @@ int d3_instance_cross_iou(const int *cluster_idxs, const int *offsets, long long
 int d3_nms_matrix(const float *ious, const float *scores, const unsigned char *keep, int n, float thr, int *order_scratch, int *picked,
                   int *npicked, void *stream);
 
+/* ---- segmentation evaluation counts (csrc/seg_eval.hip) ---------------------------------------------------------------------
+ * The per-point counting of the ScanNet segmentation evaluators for a batch of B scenes (points [batch_offsets[b],
+ * batch_offsets[b+1]) of N; batch_offsets nondecreasing, batch_offsets[B] <= N), all ids int32 raw class ids in [0, 40):
+ *   gt_sem / gt_inst: the reference's GT files (lib/utils/eval.py:14-56, value = sem * 1000 + inst) split in two, gt_inst 1-based
+ *     within its scene (0 = none, <= G = the largest id of any scene); pred_sem: NYU20_CLASS_IDX[1:][argmax] (model/pointgroup.py:561-566);
+ *   predictions: pick[0..n_pick) proposal ids into proposals_offset (P+1) / proposals_idx (S,2) [cluster, point], in pick order.
+ * Outputs (int32, bit-exact):
+ *   confusion (40,40) [gt][pred] summed over the batch, GT row 0 included (lib/evaluation/semantic_segmentation.py:18-25);
+ *   gt_stats (B,G,2) = [vertex count, class = first maximum of the instance's GT class bincount] (lib/utils/eval.py:142-158);
+ *   pred_stats (n_pick,5) = [vertex count, void intersection (GT class not in inst_class_mask, bit per class id), class of the first
+ *     member, scene of the first member, flags: 1 members disagree on the class (model/pointgroup.py:620 asserts they agree),
+ *     2 a member outside that scene or a malformed pick / segment];
+ *   inter (n_pick,G): points of prediction j with gt_inst == k + 1 in its scene (lib/evaluation/instance_segmentation.py:219-274);
+ *   *status (device) = 1 when some point's ids are out of range (those points are skipped).
+ * G > d3_seg_eval_max_inst() (the LDS bound of the point pass) returns D3_ERR_RANGE before any launch; ws: d3_seg_eval_ws_bytes(B, G). */
+int d3_seg_eval_max_inst(void);
+size_t d3_seg_eval_ws_bytes(int B, int G);
+int d3_seg_eval(const int *gt_sem, const int *gt_inst, const int *pred_sem, const int *batch_offsets, int B, int N, int max_scene_points,
+                int G, const int *pick, int n_pick, const int *proposals_idx, const int *proposals_offset, int P, long long S,
+                unsigned long long inst_class_mask, int *confusion, int *gt_stats, int *pred_stats, int *inter, int *status, void *ws,
+                size_t ws_bytes, void *stream);
+
 /* ---- CIDEr-D reward of the self-critical speaker update (csrc/cider.hip) -----------------------------
  * Replaces lib/capeval/cider/cider_scorer.py:11-193 (precook / compute_doc_freq / counts2vec / sim) as called per RL step by
  * lib/captioning/loss_helper.py:15-96 (host python over word tuples, twice per step).  Sentences are int32 token ids (< 65535;
