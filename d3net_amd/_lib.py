@@ -154,6 +154,18 @@ SIGNATURES = {
     "d3_seg_eval_max_inst": (i32, []),
     "d3_seg_eval_ws_bytes": (sz, [i32, i32]),
     "d3_seg_eval": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp, i32, vp, vp, i32, i64, C.c_ulonglong, vp, vp, vp, vp, vp, vp, sz, vp]),
+    "d3_scene_limits": (i32, [pi, pi, pi]),
+    "d3_scene_transform": (i32, [vp, i32, vp, f64, i32, vp, vp, vp]),
+    "d3_scene_reduce": (i32, [vp, vp, i32, vp, vp]),
+    "d3_scene_noise": (i32, [vp, i64, C.c_ulonglong, vp]),
+    "d3_scene_elastic_ws_bytes": (sz, [i32, i32, i32]),
+    "d3_scene_elastic": (i32, [vp, i32, vp, vp, i32, i32, i32, f64, vp, sz, vp]),
+    "d3_scene_offset": (i32, [vp, i32, vp, i32, vp]),
+    "d3_scene_crop_count": (i32, [vp, i32, vp, vp, vp, vp, vp]),
+    "d3_scene_ws_bytes": (sz, [i32, i32]),
+    "d3_scene_emit": (i32, [vp, vp, vp, i32, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+    "d3_scene_relabel": (i32, [vp, i32, i32, vp, sz, vp]),
+    "d3_scene_instances": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
     "d3_cider_ws_bytes": (sz, [i32, i32, i32]),
     "d3_cider_scores": (i32, [vp, i32, vp, vp, vp, vp, vp, i32, i32, vp, i32, vp, i32, i32, f64, i32, vp, vp, vp, sz, vp]),
     "d3_graph_edges": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),

@@ -1,0 +1,304 @@
+"""PointGroup scene preparation on the device: the per-scene half of the reference's `PipelineDataset.__getitem__`
+(lib/dataset/pipeline.py:141-187) -- augmentation (:679-697), two elastic distortions (lib/utils/transform.py:elastic), offset,
+crop (lib/utils/pc.py:crop), instance relabelling (:699-709), instance statistics and box labels (:711-772), GT proposal lists
+(:804-833) -- followed by the batch stacking of `collate.sparse_collate_fn`, so `prepare_batch` hands `PointGroup.feed` a
+device-resident batch without the host numpy / scipy pass.
+
+The bulk work is HIP (csrc/scene_prep.hip).  The host keeps the reference's data-dependent control flow, and that is where it
+synchronises with the device, per scene:
+  * the |s| maxima that size each elastic's noise grids (one read per elastic, augmented detector path only);
+  * the coordinate extent and instance-id range after the elastic (one read: crop range, workspace size);
+  * each crop iteration's kept-point count (the reference's `while` loop);
+  * the instance count and labelled-point count (output shapes).
+
+Random draws come from `rng` (a numpy RandomState, or None for numpy's global state as the reference's loader uses) in the
+reference's order: randn(3,3) jitter, randint(0,2) flip, rand() rotation, then the noise grids, then one rand(3) per crop
+iteration.  noise="host" draws the six noise grids with rng.randn in the reference's order and sizes, which reproduces the
+reference wherever fp64 allows.  noise="device" instead takes ONE rng.randint draw in the grids' place and fills the grids on the
+device (Philox4x32-10 + Box-Muller): the training path then pays no host RNG for the grids, but the host RNG stream -- and so
+every later draw -- differs from the reference's.
+"""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _lib, pointgroup_ops
+from .pointgroup_ops import _ptr, _stream
+
+_NOISE_MODES = ("host", "device")
+
+
+# ------------------------------------------------------------------------------------------------ host control flow
+def augment_matrix(rng, tcfg):
+    """`_augment`'s matrix (pipeline.py:679-697, transform.py jitter / flip / rotz) with the same draws in the same order."""
+    m = np.eye(3)
+    if tcfg.jitter:
+        m *= np.eye(3) + rng.randn(3, 3) * 0.1
+    if tcfg.flip:
+        f = np.eye(3)
+        f[0][0] *= rng.randint(0, 2) * 2 - 1
+        m *= f
+    if tcfg.rot:
+        t = rng.rand() * 2 * np.pi
+        c, s = np.cos(t), np.sin(t)
+        m = np.matmul(m, np.array([[c, -s, 0], [s, c, 0], [0, 0, 1]]))
+    return m
+
+
+def elastic_params(scale):
+    """(gran, mag) of the two elastic calls (pipeline.py:152-153)"""
+    return [(6 * scale // 50, 40 * scale / 50), (20 * scale // 50, 160 * scale / 50)]
+
+
+def grid_shape(absmax, gran):
+    """transform.py:elastic `bb = np.abs(x).max(0).astype(np.int32)//gran + 3`"""
+    return np.asarray(absmax, dtype=np.float64).astype(np.int32) // gran + 3
+
+
+def grid_axes(bb, gran):
+    return [np.linspace(-(b - 1) * gran, (b - 1) * gran, b) for b in bb]
+
+
+def host_noise(rng, bb):
+    """the reference's three noise grids of one elastic call, in its draw order"""
+    return [rng.randn(bb[0], bb[1], bb[2]).astype("float32") for _ in range(3)]
+
+
+def crop_loop(count, n, pc_range, max_num_point, scale, rng):
+    """pc.py:crop's loop with the kept-point count of a candidate offset supplied by `count(offset, max_pc_range)`.
+    -> (offset or None when the loop never ran, number of kept points)"""
+    max_pc_range = np.array([scale] * 3)
+    valid, offset = n, None
+    while valid > max_num_point:
+        offset = np.clip(max_pc_range - pc_range + 0.001, None, 0) * rng.rand(3)
+        valid = count(offset, max_pc_range.astype(np.float64))
+        max_pc_range[:2] -= 32
+    return offset, valid
+
+
+def relabel_table(present):
+    """`_croppedInstanceIds` (pipeline.py:699-709) as a map over id values, from the presence table of ids 0..V-1; the same walk
+    as csrc/scene_prep.hip's sp_relabel_map_kernel.  -> val_of (V,) int: points with id v end with id val_of[v]."""
+    present = np.asarray(present, dtype=bool)
+    V = len(present)
+    val_of = np.arange(V)
+    orig_at = np.where(present, np.arange(V), -1)
+    cur = int(np.nonzero(present)[0].max()) if present.any() else -1
+    j = 0
+    while j < cur:
+        if orig_at[j] == -1:
+            o = orig_at[cur]
+            orig_at[j], val_of[o], orig_at[cur] = o, j, -1
+            while cur > j and orig_at[cur] == -1:
+                cur -= 1
+        j += 1
+    return val_of
+
+
+def _decode(enc):
+    """order-preserving u64 encodings of csrc/scene_prep.hip -> float64"""
+    e = np.asarray(enc, dtype=np.uint64)
+    neg = (e >> np.uint64(63)) != 0
+    b = np.where(neg, e & np.uint64(0x7FFFFFFFFFFFFFFF), ~e)
+    return b.view(np.float64)
+
+
+def _range_error(what):
+    _lib.check(-2, what)
+
+
+def elastic_enabled(cfg, is_augment):
+    """pipeline.py:150 / :158: elastic distortion and crop run on the augmented detector-only path"""
+    m = cfg.model
+    return bool(is_augment and (not m.no_detection and m.no_captioning and m.no_grounding))
+
+
+# ------------------------------------------------------------------------------------------------ one scene
+def _dev_tensor(x, dtype, device):
+    t = torch.as_tensor(x) if isinstance(x, np.ndarray) else x
+    return t.to(device=device, dtype=dtype).contiguous()
+
+
+def prepare_scene(scene, cfg, mean_size_arr, rng=None, is_augment=True, noise="device", device=None):
+    """One raw scene -> the per-scene sample dict of the reference's `__getitem__` (point keys, box labels, GT proposal lists
+    when cfg.data.requires_gt_mask), as device tensors (num_instance a python int).  See the module docstring for the draws."""
+    if noise not in _NOISE_MODES:
+        raise ValueError("noise must be one of %s" % (_NOISE_MODES,))
+    rng = np.random if rng is None else rng
+    if device is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    L = _lib.lib()
+    st = _stream()
+    d = cfg.data
+    scale, R = d.scale, int(d.max_num_instance)
+    xyz = _dev_tensor(scene["points"], torch.float32, device)
+    n = xyz.shape[0]
+    feats = _dev_tensor(scene["feats"], torch.float32, device).reshape(n, -1)
+    sem = _dev_tensor(scene["sem_labels"], torch.int32, device)
+    ids = _dev_tensor(scene["instance_ids"], torch.int32, device)
+    ms = _dev_tensor(np.asarray(mean_size_arr, dtype=np.float64), torch.float64, device)
+    fp32 = 0 if is_augment else 1
+    elastic = elastic_enabled(cfg, is_augment)
+
+    y = torch.empty((n, 3), dtype=torch.float64, device=device)
+    s = torch.empty((n, 3), dtype=torch.float64, device=device)
+    stats = torch.empty(12, dtype=torch.int64, device=device)
+    m = augment_matrix(rng, d.transform) if is_augment else np.eye(3)
+    mh = np.ascontiguousarray(m, dtype=np.float64)
+    _lib.check(L.d3_scene_transform(_ptr(xyz), n, mh.ctypes.data_as(C.c_void_p), float(scale), fp32, _ptr(y), _ptr(s), st),
+               "d3_scene_transform")
+
+    if elastic:
+        seed = None if noise == "host" else int(rng.randint(0, 2 ** 31 - 1))
+        for e, (gran, mag) in enumerate(elastic_params(scale)):
+            _lib.check(L.d3_scene_reduce(_ptr(s), None, n, _ptr(stats), st), "d3_scene_reduce")
+            bb = grid_shape(_decode(stats[0:3].cpu().numpy()), gran)             # sync: grid sizes
+            X, Y, Z = (int(b) for b in bb)
+            nbytes = L.d3_scene_elastic_ws_bytes(X, Y, Z)
+            if nbytes == 0:
+                _range_error("scene_prep: noise grid %dx%dx%d" % (X, Y, Z))
+            if noise == "host":
+                grids = torch.from_numpy(np.stack(host_noise(rng, bb))).to(device)
+            else:
+                grids = torch.empty((3, X, Y, Z), dtype=torch.float32, device=device)
+                _lib.check(L.d3_scene_noise(_ptr(grids), 3 * X * Y * Z, (seed << 1) | e, st), "d3_scene_noise")
+            axes = torch.from_numpy(np.concatenate(grid_axes(bb, gran))).to(device)
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
+            _lib.check(L.d3_scene_elastic(_ptr(s), n, _ptr(grids), _ptr(axes), X, Y, Z, float(mag), _ptr(ws), nbytes, st),
+                       "d3_scene_elastic")
+
+    _lib.check(L.d3_scene_reduce(_ptr(s), _ptr(ids), n, _ptr(stats), st), "d3_scene_reduce")
+    sh = stats.cpu().numpy().view(np.uint64)                                         # sync: extent, id range
+    mn, mx = _decode(sh[3:6]), _decode(sh[6:9])
+    id_lo, id_hi = (int(v) - 2 ** 31 for v in sh[9:11]) if n else (-1, -1)
+    if id_lo < -1:
+        _range_error("scene_prep: instance id %d < -1" % id_lo)
+    nbytes = L.d3_scene_ws_bytes(n, id_hi)
+    if nbytes == 0:
+        _range_error("scene_prep: %d points / instance id %d" % (n, id_hi))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    _lib.check(L.d3_scene_offset(_ptr(s), n, _ptr(stats), fp32, st), "d3_scene_offset")
+
+    flags, off, keep = None, None, n
+    if elastic:
+        flags_t = torch.empty(n, dtype=torch.int32, device=device)
+        cnt = torch.empty(1, dtype=torch.int32, device=device)
+
+        def count(offset, rng_):
+            o = np.ascontiguousarray(offset, dtype=np.float64)
+            r = np.ascontiguousarray(rng_, dtype=np.float64)
+            _lib.check(L.d3_scene_crop_count(_ptr(s), n, o.ctypes.data_as(C.c_void_p), r.ctypes.data_as(C.c_void_p),
+                                             _ptr(flags_t), _ptr(cnt), st), "d3_scene_crop_count")
+            return int(cnt.item())                                               # sync: one per crop iteration
+
+        off, keep = crop_loop(count, n, (mx - mn) - 0.0, d.max_num_point, d.full_scale[1], rng)
+        if off is not None:
+            flags = flags_t
+            off = np.ascontiguousarray(off, dtype=np.float64)
+
+    Cf = feats.shape[1]
+    y2 = torch.empty((keep, 3), dtype=torch.float64, device=device)
+    locs = torch.empty((keep, 3), dtype=torch.float32, device=device)
+    locs_scaled = torch.empty((keep, 3), dtype=torch.float32, device=device)
+    feats2 = torch.empty((keep, Cf), dtype=torch.float32, device=device)
+    sem2 = torch.empty(keep, dtype=torch.int32, device=device)
+    ids2 = torch.empty(keep, dtype=torch.int32, device=device)
+    _lib.check(L.d3_scene_emit(_ptr(y), _ptr(s), _ptr(feats), Cf, _ptr(sem), _ptr(ids), n,
+                               _ptr(flags) if flags is not None else None,
+                               off.ctypes.data_as(C.c_void_p) if off is not None else None, fp32,
+                               _ptr(y2), _ptr(locs), _ptr(locs_scaled), _ptr(feats2), _ptr(sem2), _ptr(ids2),
+                               _ptr(ws), nbytes, st), "d3_scene_emit")
+    if elastic:
+        _lib.check(L.d3_scene_relabel(_ptr(ids2), keep, id_hi, _ptr(ws), nbytes, st), "d3_scene_relabel")
+
+    V = max(id_hi, 0) + 1
+    info = torch.empty((keep, 12), dtype=torch.float32, device=device)
+    npt = torch.zeros(V, dtype=torch.int32, device=device)
+    gt_idx = torch.empty((max(keep, 1), 2), dtype=torch.int32, device=device)
+    gt_off = torch.zeros(V + 1, dtype=torch.int32, device=device)
+    boxes = torch.zeros((R, 36), dtype=torch.float64, device=device)
+    counts = torch.empty(4, dtype=torch.int32, device=device)
+    _lib.check(L.d3_scene_instances(_ptr(y2), _ptr(ids2), _ptr(sem2), keep, id_hi, fp32, R, _ptr(ms), _ptr(info), _ptr(npt),
+                                    _ptr(gt_idx), _ptr(gt_off), _ptr(boxes), _ptr(counts), _ptr(ws), nbytes, st),
+               "d3_scene_instances")
+    K, Lp, _, _ = (int(v) for v in counts.cpu())                                    # sync: output shapes
+
+    out = {"locs": locs, "locs_scaled": locs_scaled, "feats": feats2, "sem_labels": sem2, "instance_ids": ids2,
+           "num_instance": K, "instance_info": info, "instance_num_point": npt[:K]}
+    if d.requires_gt_mask:
+        out["gt_proposals_idx"] = gt_idx[:Lp]
+        out["gt_proposals_offset"] = gt_off[:K + 1]
+    zeros = torch.zeros(R, dtype=torch.int64, device=device)
+    out.update({
+        "center_label": boxes[:, 0:3].float(),
+        "sem_cls_label": boxes[:, 6].long(),
+        "heading_class_label": zeros,
+        "heading_residual_label": torch.zeros(R, dtype=torch.float32, device=device),
+        "size_class_label": boxes[:, 6].long(),
+        "size_residual_label": boxes[:, 9:12].float(),
+        "gt_bbox_object_id": boxes[:, 7].long(),
+        "gt_bbox_label": boxes[:, 8].long(),
+        "gt_bbox": boxes[:, 12:36].reshape(R, 8, 3).float(),
+    })
+    return out
+
+
+_BOX_KEYS = ("center_label", "sem_cls_label", "heading_class_label", "heading_residual_label", "size_class_label",
+             "size_residual_label", "gt_bbox_object_id", "gt_bbox_label", "gt_bbox")
+
+
+def collate_scenes(samples, device, mode=4):
+    """`sparse_collate_fn`'s stacking (collate.py) over per-scene dicts that are already on the device"""
+    data = {k: torch.stack([smp[k] for smp in samples], 0) for k in _BOX_KEYS}
+    locs, locs_scaled, feats, sem, ids, info, npt, gt_idx, gt_off = [], [], [], [], [], [], [], [], []
+    batch_offsets, instance_offsets = [0], [0]
+    total_inst = total_pts = 0
+    for i, b in enumerate(samples):
+        n = b["locs_scaled"].shape[0]
+        locs.append(b["locs"])
+        locs_scaled.append(torch.cat([torch.full((n, 1), i, dtype=torch.int64, device=device), b["locs_scaled"].long()], 1))
+        feats.append(b["feats"])
+        batch_offsets.append(batch_offsets[-1] + n)
+        if "gt_proposals_idx" in b:
+            gi = b["gt_proposals_idx"].clone()
+            gi[:, 0] += total_inst
+            gi[:, 1] += total_pts
+            gt_idx.append(gi)
+            go = b["gt_proposals_offset"]
+            gt_off.append(go + gt_off[-1][-1] if gt_off else go)
+            if len(gt_off) > 1:
+                gt_off[-1] = gt_off[-1][1:]
+        ii = b["instance_ids"]
+        ids.append(torch.where(ii != -1, ii + total_inst, ii))
+        total_inst += b["num_instance"]
+        total_pts += n
+        sem.append(b["sem_labels"]); info.append(b["instance_info"]); npt.append(b["instance_num_point"])
+        instance_offsets.append(instance_offsets[-1] + b["num_instance"])
+    data["locs"] = torch.cat(locs, 0)
+    data["locs_scaled"] = torch.cat(locs_scaled, 0)
+    data["feats"] = torch.cat(feats, 0)
+    data["batch_offsets"] = torch.tensor(batch_offsets, dtype=torch.int32, device=device)
+    data["sem_labels"] = torch.cat(sem, 0).long()
+    data["instance_ids"] = torch.cat(ids, 0).long()
+    data["instance_info"] = torch.cat(info, 0)
+    data["instance_num_point"] = torch.cat(npt, 0)
+    data["instance_offsets"] = torch.tensor(instance_offsets, dtype=torch.int32, device=device)
+    if gt_idx:
+        data["gt_proposals_idx"] = torch.cat(gt_idx, 0)
+        data["gt_proposals_offset"] = torch.cat(gt_off, 0)
+    data["voxel_locs"], data["p2v_map"], data["v2p_map"] = pointgroup_ops.voxelization_idx(data["locs_scaled"], len(samples), mode)
+    return data
+
+
+def prepare_batch(scenes, cfg, mean_size_arr, rng=None, is_augment=True, noise="device", device=None, mode=4):
+    """Raw scenes (dicts of `points` (N,3) metres, `feats` (N,C), `sem_labels` (N,) -1 ignored, `instance_ids` (N,) -1 none; numpy
+    or device tensors) -> the device batch `collate.sparse_collate_fn` returns for the reference's per-scene sample dicts built
+    from the same scenes and draws (point keys, voxelisation maps, GT proposal lists when cfg.data.requires_gt_mask, stacked box
+    labels).  Scenes are prepared one after another: each scene's crop draws depend on that scene's device counts and precede
+    the next scene's draws, as in the reference's loader.  mean_size_arr: (18,3), scannet_reference_means.npz."""
+    if device is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    rng = np.random if rng is None else rng
+    samples = [prepare_scene(sc, cfg, mean_size_arr, rng=rng, is_augment=is_augment, noise=noise, device=device) for sc in scenes]
+    return collate_scenes(samples, device, mode)

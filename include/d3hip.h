@@ -734,6 +734,50 @@ int d3_seg_eval(const int *gt_sem, const int *gt_inst, const int *pred_sem, cons
                 unsigned long long inst_class_mask, int *confusion, int *gt_stats, int *pred_stats, int *inter, int *status, void *ws,
                 size_t ws_bytes, void *stream);
 
+/* ---- PointGroup scene preparation (csrc/scene_prep.hip, driven by d3net_amd/scene_prep.py) ----------------------------------
+ * One scene of n points: xyz (n,3) float32, ids / sem (n) int32 (ids -1 = none).  Coordinates are fp64 (numpy's float32 @ float64
+ * promotion) unless fp32 != 0 (the validation path, float32 throughout like the reference's `points.copy() * scale`).
+ * Sizes beyond d3_scene_limits (points, elements per noise grid, largest instance id) return D3_ERR_RANGE before any launch. */
+int d3_scene_limits(int *max_points, int *max_grid, int *max_id);
+/* lib/dataset/pipeline.py:145-146 + :679-697 (_augment): y = xyz @ m (m_host: 9 doubles, host memory), s = y * scale. */
+int d3_scene_transform(const float *xyz, int n, const double *m_host, double scale, int fp32, double *y, double *s, void *stream);
+/* stats (12 u64, device): order-preserving encodings of |s| max, min, max per axis (lib/utils/transform.py:elastic `bb`,
+ * pipeline.py:155 offset, lib/utils/pc.py:38 pc_range) and ids min / max + 2^31 (ids may be NULL). */
+int d3_scene_reduce(const double *s, const int *ids, int n, unsigned long long *stats, void *stream);
+/* transform.py:elastic noise, device mode: count N(0,1) float32 values from Philox4x32-10 (key = seed) + Box-Muller. */
+int d3_scene_noise(float *grid, long long count, unsigned long long seed, void *stream);
+/* transform.py:elastic: grids = 3 noise grids (X,Y,Z) float32, contiguous, blurred in place by the six scipy.ndimage.convolve
+ * passes; axes = the X + Y + Z np.linspace node values; then s += RegularGridInterpolator(...)(s) * mag (fill 0 outside).
+ * ws: d3_scene_elastic_ws_bytes(X, Y, Z) (0: grid outside the limits). */
+size_t d3_scene_elastic_ws_bytes(int X, int Y, int Z);
+int d3_scene_elastic(double *s, int n, float *grids, const double *axes, int X, int Y, int Z, double mag, void *ws, size_t ws_bytes,
+                     void *stream);
+/* pipeline.py:155 `points -= points.min(0)` with the min of `stats` (d3_scene_reduce). */
+int d3_scene_offset(double *s, int n, const unsigned long long *stats, int fp32, void *stream);
+/* pc.py:crop :40-42 for one candidate: flags[i] = all(s + off >= 0) and all(s + off < range); *count (device) = sum(flags).
+ * off_host / range_host: 3 doubles each, host memory.  The host runs the reference's while loop on the counts. */
+int d3_scene_crop_count(const double *s, int n, const double *off_host, const double *range_host, int *flags, int *count,
+                        void *stream);
+/* workspace of d3_scene_emit / d3_scene_relabel / d3_scene_instances for n points and ids <= max_id (0: outside the limits) */
+size_t d3_scene_ws_bytes(int n, int max_id);
+/* pipeline.py:160-164 (+ :182-186 casts): stable order-preserving compaction of the points with flags[i] != 0 (flags NULL: all);
+ * locs = (float)y, locs_scaled = (float)(s + off) (off_host NULL: 0), y_out = y, feats (n,C) rows, sem, ids. */
+int d3_scene_emit(const double *y, const double *s, const float *feats, int C, const int *sem, const int *ids, int n,
+                  const int *flags, const double *off_host, int fp32, double *y_out, float *locs, float *locs_scaled,
+                  float *feats_out, int *sem_out, int *ids_out, void *ws, size_t ws_bytes, void *stream);
+/* pipeline.py:699-709 (_croppedInstanceIds) in place, from the id-presence table of ids in [-1, max_id]. */
+int d3_scene_relabel(int *ids, int n, int max_id, void *ws, size_t ws_bytes, void *stream);
+/* pipeline.py:711-772 (_getInstanceInfo) and :804-833 (_generate_gt_clusters) over ids in np.unique order (ids in [-1, max_id]):
+ *   info (n,12) float32 = mean, (min+max)/2, min, max of y per instance (zeros when unlabelled);
+ *   num_point[r], gt_off[r] (r < K) and gt_off[K]; gt_idx (L,2) = [cid, point], ascending point index inside an instance;
+ *   boxes (R,36) float64 rows = [center 3, size 3, class, id, label, size residual 3, 8 corners x 3] (zero-filled by the caller),
+ *     with the reference's slot -1 / k >= 128 quirks; class = sem of the lowest-index point, c - 2 if c >= 2 else 17;
+ *     residual = size - mean_size (18,3) float64 device;
+ *   counts (4 int, device) = [K instances, L labelled points, has unlabelled points, 0].  Deterministic (no float atomics). */
+int d3_scene_instances(const double *y, const int *ids, const int *sem, int n, int max_id, int fp32, int R, const double *mean_size,
+                       float *info, int *num_point, int *gt_idx, int *gt_off, double *boxes, int *counts, void *ws,
+                       size_t ws_bytes, void *stream);
+
 /* ---- CIDEr-D reward of the self-critical speaker update (csrc/cider.hip) -----------------------------
  * Replaces lib/capeval/cider/cider_scorer.py:11-193 (precook / compute_doc_freq / counts2vec / sim) as called per RL step by
  * lib/captioning/loss_helper.py:15-96 (host python over word tuples, twice per step).  Sentences are int32 token ids (< 65535;
