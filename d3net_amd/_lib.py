@@ -166,6 +166,12 @@ SIGNATURES = {
     "d3_scene_emit": (i32, [vp, vp, vp, i32, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
     "d3_scene_relabel": (i32, [vp, i32, i32, vp, sz, vp]),
     "d3_scene_instances": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+    "d3_multiview_limits": (i32, [pi, pi, pi]),
+    "d3_multiview_project_ws_bytes": (sz, [i32, i32]),
+    "d3_multiview_project": (i32, [vp, i32, vp, vp, vp, i32, C.POINTER(f64), i32, i32, vp, vp, vp, sz, vp]),
+    "d3_multiview_project_frame": (i32, [vp, i32, i32, vp, vp, i32, vp, vp]),
+    "d3_multiview_fuse_ws_bytes": (sz, [i32, i32, i32]),
+    "d3_multiview_fuse": (i32, [vp, i32, vp, vp, vp, i32, C.POINTER(f64), i32, i32, vp, i32, i32, vp, vp, vp, sz, vp]),
     "d3_cider_ws_bytes": (sz, [i32, i32, i32]),
     "d3_cider_scores": (i32, [vp, i32, vp, vp, vp, vp, vp, i32, i32, vp, i32, vp, i32, i32, f64, i32, vp, vp, vp, sz, vp]),
     "d3_graph_edges": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),

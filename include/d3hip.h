@@ -778,6 +778,36 @@ int d3_scene_instances(const double *y, const int *ids, const int *sem, int n, i
                        float *info, int *num_point, int *gt_idx, int *gt_off, double *boxes, int *counts, void *ws,
                        size_t ws_bytes, void *stream);
 
+/* ---- multiview feature projection (csrc/multiview.hip, driven by d3net_amd/multiview.py) --------------------------------------
+ * The reference's ProjectionHelper.compute_projection / project (lib/utils/projection.py:180-256) and the per-scene loop of
+ * data/scannet/project_multiview_features.py:88-205.  One scene: points (N,3) float32 mesh vertices; F frames in the caller's order:
+ * depths (F,H,W) float32 metres, c2w / w2c (F,4,4) float32 camera_to_world and its inverse (the caller's torch.inverse);
+ * intr_host: 7 doubles, host memory = fx, fy, cx, cy, depth_min, depth_max, accuracy (the image corners are unprojected from them
+ * in double and stored as float32, like projection.py:18-45).  Frustum, projection and depth test are float32 in a fixed order.
+ * N, F, W * H beyond d3_multiview_limits return D3_ERR_RANGE before any launch. */
+int d3_multiview_limits(int *max_points, int *max_frames, int *max_pixels);
+/* compute_projection for F frames at once: idx3d / idx2d (F, N+1) int64, row f = [count, point ids ascending..., 0...] /
+ * [count, pixel v * W + u..., 0...] (zero-filled here).  N * F must stay below 2^31 (else D3_ERR_RANGE);
+ * ws: d3_multiview_project_ws_bytes(N, F) (0: outside the limits). */
+size_t d3_multiview_project_ws_bytes(int N, int F);
+int d3_multiview_project(const float *points, int N, const float *depths, const float *c2w, const float *w2c, int F,
+                         const double *intr_host, int W, int H, long long *idx3d, long long *idx2d, void *ws, size_t ws_bytes,
+                         void *stream);
+/* ProjectionHelper.project for one frame: out (C, N) = 0, then out[:, idx3d[1+j]] = label[:, idx2d[1+j]] for j < idx3d[0] (read
+ * on the device); label (C, HW) float32.  Indices outside [0, N) / [0, HW) are skipped. */
+int d3_multiview_project_frame(const float *label, int C, int HW, const long long *idx3d, const long long *idx2d, int N, float *out,
+                               void *stream);
+/* The fused scene: feats (F, C, H, W) float32 ENet maps, C == 128 (the reference's emptiness test hard-codes 128; else
+ * D3_ERR_ARG) -> out (N, 128) float32, fused over the frames with at least one mapped point, in order
+ * (project_multiview_features.py:170-200): maxpool != 0: a non-empty projection fills an empty row and max-pools a filled one;
+ * maxpool == 0: an empty row takes the frame's projection (zeros for an unmapped point).  "Empty" = all 128 values == 0.
+ * frame_counts (F int32, device; may be NULL) = mapped points per frame.  Bitwise deterministic (no float atomics).
+ * ws: d3_multiview_fuse_ws_bytes(F, W, H) (0: outside the limits). */
+size_t d3_multiview_fuse_ws_bytes(int F, int W, int H);
+int d3_multiview_fuse(const float *points, int N, const float *depths, const float *c2w, const float *w2c, int F,
+                      const double *intr_host, int W, int H, const float *feats, int C, int maxpool, float *out, int *frame_counts,
+                      void *ws, size_t ws_bytes, void *stream);
+
 /* ---- CIDEr-D reward of the self-critical speaker update (csrc/cider.hip) -----------------------------
  * Replaces lib/capeval/cider/cider_scorer.py:11-193 (precook / compute_doc_freq / counts2vec / sim) as called per RL step by
  * lib/captioning/loss_helper.py:15-96 (host python over word tuples, twice per step).  Sentences are int32 token ids (< 65535;
