@@ -808,6 +808,32 @@ int d3_multiview_fuse(const float *points, int N, const float *depths, const flo
                       const double *intr_host, int W, int H, const float *feats, int C, int maxpool, float *out, int *frame_counts,
                       void *ws, size_t ws_bytes, void *stream);
 
+/* ---- ENet frame features (csrc/enet.hip, driven by d3net_amd/enet.py) ---------------------------------------------------------
+ * Replaces data/scannet/compute_multiview_features.py:53-73 (EnetDataset._resize_crop_image / _load_image: PIL NEAREST resize to
+ * height 256, CenterCrop to 256 x 328, x / 255, Normalize) and :77-96 (Sequential(enet_fixed, enet_trainable) of
+ * model/enet.py:697-715 create_enet_for_3d, elements 0-25 of create_enet(41) at :130-695, in eval mode).  Inference only.
+ * d3_enet_layers: the 67 convolution rows (initial block, then conv a / b / c of blocks 4-25), 7 ints each = cin, cout, kh, kw,
+ * stride, pad, dilation (the asymmetric 1x5 + 5x1 pair is one folded 5x5 row); table == NULL: only the count, cap too small:
+ * D3_ERR_ARG.  d3_enet_param_count: floats of the folded parameter blob, laid out per row in that order, every segment padded to
+ * a multiple of 4 floats: the initial block = W (13,3,3,3), bias 13, pool scale 3, pool shift 3, PReLU 16; a convolution =
+ * W (kh*kw, cout, cin), bias cout, PReLU cout (conv c: the block's output PReLU; its W and bias carry BN and the x(1 - p)). */
+int d3_enet_layers(int *table, int cap);
+long long d3_enet_param_count(void);
+/* frames (F, H0, W0, 3) uint8 RGB -> out (F, 3, H, W) float32 = (src / 255 - mean) / std with src = frames[f, rows[y], cols[x]]
+ * (rows (H), cols (W) int32 device tables, crop included; true float32 divisions).  Per-frame sizes of 2^31 elements or more or
+ * F > 65535: D3_ERR_RANGE. */
+int d3_enet_preprocess(const unsigned char *frames, int F, int H0, int W0, const int *rows, const int *cols, int H, int W, float *out,
+                       void *stream);
+/* x (F, 3, H, W) float32 -> out (F, 128, H/8, W/8) float32 (the reference's per-frame array).  params: the folded blob
+ * (n_params == d3_enet_param_count()); table / n_table: the caller's copy of d3_enet_layers (any difference: D3_ERR_ARG).
+ * upto = 25; 3..24 stops after that element of create_enet(41) and writes its output NHWC: (F, H/2, W/2, 16) for 3,
+ * (F, H/4, W/4, 64) for 4..8, (F, H/8, W/8, 128) for 9..24 (a test hook; other values: D3_ERR_ARG).
+ * H or W not a multiple of 8: D3_ERR_ARG; H * W * 4 >= 2^31 or F > 65535: D3_ERR_RANGE; all before any launch.  67 launches,
+ * no host synchronisation; a frame's output is bitwise independent of F.  ws: d3_enet_ws_bytes(F, H, W) (0: invalid sizes). */
+size_t d3_enet_ws_bytes(int F, int H, int W);
+int d3_enet_forward(const float *x, int F, int H, int W, const float *params, long long n_params, const int *table, int n_table,
+                    int upto, float *out, void *ws, size_t ws_bytes, void *stream);
+
 /* ---- CIDEr-D reward of the self-critical speaker update (csrc/cider.hip) -----------------------------
  * Replaces lib/capeval/cider/cider_scorer.py:11-193 (precook / compute_doc_freq / counts2vec / sim) as called per RL step by
  * lib/captioning/loss_helper.py:15-96 (host python over word tuples, twice per step).  Sentences are int32 token ids (< 65535;
