@@ -1,8 +1,12 @@
 #!/usr/bin/env python3
 """bench.py -- scenes/sec of D3Net's training step on MI355X (BASELINE.json metric).
 
-    python bench.py [--config speaker|detector|listener|joint] --gpus N --steps K --warmup W [--scaling weak|strong] [--dump-outputs DIR]
+    python bench.py [--config speaker|detector|listener|joint] --gpus N --steps K --warmup W [--scaling weak|strong] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+
+A plain run does what the headline figure needs: set-up, warm-up, the K timed steps, --dump-outputs, the line.  The side
+measurements -- the exact-fp32 steps (`fp32_exact`), the strong-scaling ceiling (`strong_scaling_ceiling`, which starts a
+32-scene child run) and the CPU baseline sweep (`cpu_baseline`) -- run after the timed steps only with --full.
 
 With N > 1 and no WORLD_SIZE in the environment bench.py starts its N ranks ITSELF (one child process group through
 torch.distributed.run, as the reference spawns its DDP ranks: scripts/train.py:265-268), decided before anything touches the
@@ -49,11 +53,13 @@ def parse():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", choices=sorted(CONF), default="speaker")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the side measurements: exact-fp32 steps, strong-scaling ceiling, CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline sweep")
     ap.add_argument("--settle", type=int, default=SETTLE_STEPS,
                     help="untimed steps between the dry pass and the --warmup steps (a fresh box reaches its sustained rate after some tens of steps)")
-    ap.add_argument("--no-fp32", action="store_true", help="skip the untimed exact-fp32 (reference precision) steps")
-    ap.add_argument("--no-ceiling", action="store_true", help="skip the untimed 8-scene / 1-scene steps behind `strong_scaling_ceiling`")
+    ap.add_argument("--no-fp32", action="store_true", help="with --full: skip the untimed exact-fp32 (reference precision) steps")
+    ap.add_argument("--no-ceiling", action="store_true", help="with --full: skip the untimed 8-scene / 1-scene steps behind `strong_scaling_ceiling`")
     ap.add_argument("--scene-count", type=int, default=0, help=argparse.SUPPRESS)   # (child of the 32-scene ceiling measurement: scenes 0..N-1 on this rank)
     ap.add_argument("--cpu-baseline-only", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--cpu-threads", type=int, default=0, help=argparse.SUPPRESS)
@@ -73,8 +79,18 @@ def parse():
     return args
 
 
+def side_measurements(args, dist_on):
+    """which measurements beyond the headline figure this run makes after its timed steps: none without --full; with it, those
+    its configuration supports and no --no-* switch turns off (one rank only)"""
+    full = args.full and not dist_on
+    return {"fp32": full and not args.no_fp32 and not args.exact,
+            "ceiling": (full and not args.no_ceiling and not args.exact and args.config in ("speaker", "listener")
+                        and args.scaling == "weak" and not args.small),
+            "cpu_baseline": full and not args.no_cpu_baseline}
+
+
 CPU_THREADS = 8            # default thread count of the CPU baseline child (the parent sweeps CPU_THREAD_SWEEP; all 256 hardware threads of the GPU box: 1000x slower)
-CPU_THREAD_SWEEP = (8, 16, 32)   # the sweep behind that "8", re-run with every bench line (the best one is `cpu_baseline.value`)
+CPU_THREAD_SWEEP = (8, 16, 32)   # the sweep behind that "8", re-run with every --full bench line (the best one is `cpu_baseline.value`)
 CPU_WARMUP_STEPS, CPU_TIMED_STEPS = 1, 3   # per thread count: ~4 x 5 s of CPU work
 
 
@@ -752,6 +768,7 @@ def main():
     hg_shapes = kernels.pop("__hg_shapes__", [])
     L.d3_prof_enable(0)
     final_loss = float(loss.detach())
+    side = side_measurements(args, dist_on)
     if args.dump_outputs and rank == 0:
         # what a caller of the timed step receives from its last run: the loss, the output dict and the parameters AdamW updated
         names = [n for n, p in model.named_parameters() if p.requires_grad]
@@ -761,11 +778,12 @@ def main():
                            "params_layout": [[n, list(p.shape)] for n, p in zip(names, params)]})
         torch.cuda.synchronize()
 
+    # side measurements (--full only; none of them feeds `value` or the dumped outputs)
     # reference precision beside the bf16 number: a few untimed-for-`value` steps with the exact-fp32 kernels
     fp32 = None
     if args.exact:
         ME.set_exact(False)
-    if not dist_on and not args.no_fp32 and not args.exact:
+    if side["fp32"]:
         ME.set_exact(True)
         try:
             for _ in range(6):                            # (the fp32 program's own plan / arena / workspaces / code objects; the caching
@@ -786,7 +804,7 @@ def main():
     # strong-scaling ceiling of ONE GPU's step: the 8-scene global batch of `--scaling strong` on this GPU
     # against one scene per step -- what 8 ranks with 1 scene each can gain at best before any link is involved
     ceiling = None
-    if not dist_on and not args.no_ceiling and not args.exact and config in ("speaker", "listener") and args.scaling == "weak" and not args.small:
+    if side["ceiling"]:
         try:
             def timed(scene_list, k=10, warm=6):
                 b = S.make_batch(scene_list, dev)
@@ -949,7 +967,7 @@ def main():
                                           "heads_bucket_started_inside_backward": grad_sync.early_launches,
                                           "executor_chunks": [[hi - lo for lo, hi in it["ranges"]] for it in items],
                                           "executor_chunk_collectives_started_inside_backward": grad_sync.chunk_launches}
-        if not dist_on and not args.no_cpu_baseline:
+        if side["cpu_baseline"]:
             out["cpu_baseline"] = cpu_baseline(config)
     # The JSON line must be the LAST thing on stdout: RCCL writes a five-line version banner through C stdio at communicator
     # set-up, and with stdout on a pipe that text sits in the C buffer of EVERY rank until the process exits -- after the line.
