@@ -177,6 +177,11 @@ SIGNATURES = {
     "d3_enet_preprocess": (i32, [vp, i32, i32, i32, vp, vp, i32, i32, vp, vp]),
     "d3_enet_ws_bytes": (sz, [i32, i32, i32]),
     "d3_enet_forward": (i32, [vp, i32, i32, i32, vp, i64, vp, i32, i32, vp, vp, sz, vp]),
+    "d3_scan_limits": (i32, [pi, pi, pi, pi, pi]),
+    "d3_scan_mesh_ws_bytes": (sz, [i32, i32]),
+    "d3_scan_mesh": (i32, [vp, i32, vp, i32, C.POINTER(f64), vp, vp, vp, vp, sz, vp]),
+    "d3_scan_labels_ws_bytes": (sz, [i32, i32, i32, i32, i32]),
+    "d3_scan_labels": (i32, [vp, vp, i32, i32, vp, vp, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
     "d3_cider_ws_bytes": (sz, [i32, i32, i32]),
     "d3_cider_scores": (i32, [vp, i32, vp, vp, vp, vp, vp, i32, i32, vp, i32, vp, i32, i32, f64, i32, vp, vp, vp, sz, vp]),
     "d3_graph_edges": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),

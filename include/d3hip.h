@@ -834,6 +834,36 @@ size_t d3_enet_ws_bytes(int F, int H, int W);
 int d3_enet_forward(const float *x, int F, int H, int W, const float *params, long long n_params, const int *table, int n_table,
                     int upto, float *out, void *ws, size_t ws_bytes, void *stream);
 
+/* ---- ScanNet scan export (csrc/scan_export.hip, driven by d3net_amd/scan_export.py) -----------------------------------------------
+ * Replaces data/scannet/prepare_scannet.py:138-197 (export / process_one_scan) with the helpers it calls (:23-25, :29-135),
+ * scannet_utils.py:21-48 / :117-136 (read_mesh_vertices_rgb_normal, compute_normal, normalize_v3) and the instance-GT body of
+ * prepare_scannet_inst_gt.py:38-65.  The host parses the files and builds the object tables; everything per vertex or per face runs
+ * here.  Integer atomics only: every output is bitwise reproducible.  Sizes outside d3_scan_limits return D3_ERR_RANGE and NULL or
+ * misaligned pointers D3_ERR_ARG, both before any launch.  flags: device int[2], zeroed by the caller; flags[0] collects problem bits
+ * of the data (1 face vertex count != 3, 2 face index outside [0, N), 4 raw label >= 150, 8 segment id outside [0, S), 16 a
+ * listed segment that no vertex carries, 32 an object table entry outside its contract: pair_obj outside [0, K), obj_id outside
+ * [0, R) or repeated; such entries are skipped, never used as an index), flags[1] = box rows kept by d3_scan_labels. */
+int d3_scan_limits(int *max_vertices, int *max_faces, int *max_segments, int *max_objects, int *max_rows);
+/* vertex_rec: N raw 16-byte PLY vertex records (float x, y, z; uchar red, green, blue, alpha), 4-byte aligned; face_rec: F raw
+ * 13-byte face records (uchar count; int32 vertex_indices[3]).  mesh / aligned_mesh (N, 9) float32 = xyz, rgb, vertex normals
+ * (numpy's buffered `normals[faces[:, c]] += n`: the last face per vertex and corner); aligned xyz = [x y z 1] . M^T in fp64,
+ * ((x m0 + y m1) + z m2) + m3 rounded to float32 with M = align_host (host double[16], row-major), a copy when NULL.
+ * ws: d3_scan_mesh_ws_bytes(N, F) (0: outside the limits). */
+size_t d3_scan_mesh_ws_bytes(int N, int F);
+int d3_scan_mesh(const void *vertex_rec, int N, const void *face_rec, int F, const double *align_host, float *mesh, float *aligned_mesh,
+                 int *flags, void *ws, size_t ws_bytes, void *stream);
+/* raw (N) uint16 nyu40 labels, seg (N) int32 segment ids in [0, S).  The aggregation as K objects in dict order (index k): P pairs
+ * (pair_seg[p], pair_obj[p] = k), obj_id[k] = objectId, obj_label_seg[k] = the segment whose first vertex labels the object;
+ * R = max objectId + 1.  Outputs: instance_ids / sem_labels (N) float64 (objectId of the last object listing the vertex's segment
+ * or -1; remapper[raw]), inst_gt (N) int32 (the instance GT code), boxes / aligned_boxes (R, 8) float64 capacity: the first
+ * flags[1] rows are get_instance_bboxes of mesh / aligned_mesh after process_one_scan's filter of labels 1, 2, 22.
+ * ws: d3_scan_labels_ws_bytes(N, S, P, K, R) (0: outside the limits). */
+size_t d3_scan_labels_ws_bytes(int N, int S, int P, int K, int R);
+int d3_scan_labels(const unsigned short *raw, const int *seg, int N, int S, const int *pair_seg, const int *pair_obj, int P,
+                   const int *obj_id, const int *obj_label_seg, int K, int R, const float *mesh, const float *aligned_mesh,
+                   double *instance_ids, double *sem_labels, int *inst_gt, double *boxes, double *aligned_boxes, int *flags, void *ws,
+                   size_t ws_bytes, void *stream);
+
 /* ---- CIDEr-D reward of the self-critical speaker update (csrc/cider.hip) -----------------------------
  * Replaces lib/capeval/cider/cider_scorer.py:11-193 (precook / compute_doc_freq / counts2vec / sim) as called per RL step by
  * lib/captioning/loss_helper.py:15-96 (host python over word tuples, twice per step).  Sentences are int32 token ids (< 65535;
