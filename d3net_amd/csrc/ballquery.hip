@@ -549,18 +549,6 @@ __global__ void bqg_clique_kernel(const int *__restrict__ skey, const int *__res
     if (T > 64 && diag2 * 1.00001f < radius2 && diag2 == diag2) tlead[cslot[c]] = sidx[s0];
 }
 
-__device__ __forceinline__ int bqg_bitonic64(int v, int lane) {   // ascending across the 64 lanes
-#pragma unroll
-    for (int k = 2; k <= 64; k <<= 1) {
-#pragma unroll
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            const int o = __shfl_xor(v, j);
-            const bool up = (lane & k) == 0, lower = (lane & j) == 0;
-            v = (lower == up) ? min(v, o) : max(v, o);
-        }
-    }
-    return v;
-}
 // ascending bitonic sort of buf[0..P) (P a power of two >= 64) by ONE wave
 __device__ __forceinline__ void bqg_sort_lds(int *buf, int P, int lane) {
     for (int k = 2; k <= P; k <<= 1) {
@@ -637,35 +625,6 @@ __device__ __forceinline__ bool bqg_test(const BqProbe &r, int t, const int *pre
     return live && d2 < radius2;
 }
 
-// one query on one wave: followers of a clique leader and queries with <= 64 candidates finish here, the others are queued for the
-// dense pass (which needs an 8 KB hit buffer per wave -- kept out of this kernel's occupancy)
-__device__ __forceinline__ void bqg_query_one(int q, const float *__restrict__ xyz, const int *__restrict__ batch_idxs, float radius, float inv,
-                                              const int *__restrict__ sidx, const float *__restrict__ sxyz, const BqSlot *__restrict__ tbl,
-                                              const int *__restrict__ tlead, size_t mask, int *__restrict__ leader_of,
-                                              int *__restrict__ len_out, int *__restrict__ idx, int *dense, int *scal, int lane, int *preS, int *cstS) {
-    const BqProbe r = bqg_probe(xyz, batch_idxs, q, inv, tbl, tlead, mask, lane, preS, cstS);
-    if (r.leader >= 0 && r.leader != q) { if (lane == 0) leader_of[q] = r.leader; return; }   // shares the leader's list
-    if (lane == 0) leader_of[q] = q;
-    if (r.T > 64) { if (lane == 0) dense[atomicAdd(&scal[1], 1)] = q; return; }
-    int k;
-    const bool hit = bqg_test(r, lane, preS, cstS, sidx, sxyz, __fmul_rn(radius, radius), k);
-    const int v = bqg_bitonic64(hit ? k : 0x7FFFFFFF, lane);
-    const int cnt = (int)__popcll(__ballot(hit));
-    if (lane < cnt) idx[(long long)q * BQ_CAP + lane] = v;
-    if (lane == 0) len_out[q] = cnt;
-}
-// sparse pass, one wave per query (rounds 3 - 4; D3_BQ_HALF=0)
-__global__ __launch_bounds__(256) void bqg_query_kernel(const float *__restrict__ xyz, const int *__restrict__ batch_idxs, int n,
-                                                       float radius, float inv, const int *__restrict__ sidx,
-                                                       const float *__restrict__ sxyz, const BqSlot *__restrict__ tbl,
-                                                       const int *__restrict__ tlead, size_t mask, int *__restrict__ leader_of,
-                                                       int *__restrict__ len_out, int *__restrict__ idx, int *dense, int *scal) {
-    __shared__ int preS[4][32], cstS[4][32];
-    const int q = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
-    if (q >= n) return;                      // (whole waves: no workgroup barrier below)
-    const int lane = d3_lane(), wave = (int)(threadIdx.x >> 6);
-    bqg_query_one(q, xyz, batch_idxs, radius, inv, sidx, sxyz, tbl, tlead, mask, leader_of, len_out, idx, dense, scal, lane, preS[wave], cstS[wave]);
-}
 // Round 5 -- TWO queries per wave.  The wave-per-query kernel is bound by waves x latency (600 k waves of four dependent round trips
 // at full occupancy: ~390 us for the 4-scene batch) and a query of a surface has ~25 candidates in its 27 cells: 32 lanes hold the 27
 // probes, up to 32 candidates and a 32-lane bitonic network.  A half owns lanes [32 h, 32 h + 32); every cross-lane step is
@@ -853,12 +812,8 @@ static int bqg_padded(const float *xyz, const int *batch_idxs, int n, float radi
     bqg_cellbox_kernel<<<(int)(((long long)n * BQG_CB + 255) / 256), 256, 0, s>>>(g.cstart, g.cslot, g.scal, g.sxyz, g.tbl, g.cbox);          // (<= n cells)
     bqg_clique_kernel<<<(n + 255) / 256, 256, 0, s>>>(g.skey, g.sidx, g.cstart, g.cslot, g.scal, g.tbl, g.cap - 1, g.cbox,
                                                      radius * radius, g.tlead);
-    if (d3_tune(D3T_BQ_HALF) != 0) {
-        bqg_query32_kernel<<<(n + 7) / 8, 256, 0, s>>>(xyz, batch_idxs, n, radius, inv, g.sidx, g.sxyz, g.tbl, g.tlead, g.cap - 1,
-                                                      g.leader_of, w.len, idx_padded, g.dense, g.scal);
-    } else
-    bqg_query_kernel<<<(n + 3) / 4, 256, 0, s>>>(xyz, batch_idxs, n, radius, inv, g.sidx, g.sxyz, g.tbl, g.tlead, g.cap - 1,
-                                                g.leader_of, w.len, idx_padded, g.dense, g.scal);
+    bqg_query32_kernel<<<(n + 7) / 8, 256, 0, s>>>(xyz, batch_idxs, n, radius, inv, g.sidx, g.sxyz, g.tbl, g.tlead, g.cap - 1,
+                                                  g.leader_of, w.len, idx_padded, g.dense, g.scal);
     // dense pass: as many workgroups as the chip holds (LDS: 5 per CU), each wave walks the queue
     int nblk = (n + 3) / 4;
     if (nblk > 1280) nblk = 1280;

@@ -384,8 +384,10 @@ static int cl_count_enqueue(const int *semantic_label, const int *ball_query_idx
     const int T = 256, nb = (n + T - 1) / T, nwb = (n + 3) / 4;
     if (it == 0) {
         cl_init_kernel<<<nb, T, 0, s>>>(w.parent, w.lab, w.sizes, w.par, w.klen, w.qln, n, w.scalars);   // (klen, qln: scratch until the fill)
-        if (d3_tune(D3T_CL_HOOK) != 0) cl_hook_kernel<<<nb, T, 0, s>>>(semantic_label, ball_query_idxs, start_len, n, w.parent);
-        if (d3_tune(D3T_CL_HOOK) == 2) cl_flatten_kernel<<<nb, T, 0, s>>>(w.parent, n);      // (trees flattened before the unions: most edges then compare two roots without a walk)
+        // one hook per node under a smaller-index neighbour first (ECL-CC init), then the hooked trees flattened before the unions: most
+        // edges then find parent[i] == parent[j] with two loads and no walk (speaker step 16.59 -> 16.42 ms in-process, round 5)
+        cl_hook_kernel<<<nb, T, 0, s>>>(semantic_label, ball_query_idxs, start_len, n, w.parent);
+        cl_flatten_kernel<<<nb, T, 0, s>>>(w.parent, n);
         cl_union_kernel<<<(int)(((long long)n * CL_UG + T - 1) / T), T, 0, s>>>(semantic_label, ball_query_idxs, start_len, n, w.parent, w.scalars);
         cl_flatten_kernel<<<nb, T, 0, s>>>(w.parent, n);
         D3_LAUNCH_CHECK();
@@ -776,13 +778,6 @@ __device__ __forceinline__ void b2_scan2(int v0, int v1, int *wsum, int &phase, 
     p1 = __shfl(s1 - w1, wv) + x1 - v1;
 }
 
-#ifdef B2_TIMING
-#define B2_TICK(k) { const long long t_ = (long long)__builtin_readcyclecounter(); tacc[k] += t_ - tprev; tprev = t_; }
-#define B2_TDUMP if (dbg && tid == 0 && c < 20) for (int k = 0; k < 8; k++) dbg[60 + c * 8 + k] = (int)(tacc[k] >> 4);
-#else
-#define B2_TICK(k)
-#define B2_TDUMP
-#endif
 // One workgroup per kept cluster.  Profiled per level (cycle counters, profiles/r01_n): the global round trip for the
 // edge records is only ~15 % of a level; the rest is workgroup barriers and dependent LDS chains.  So the level loop
 // is organised to need few of both:
@@ -796,13 +791,9 @@ __global__ __launch_bounds__(B2_THREADS) void cl_bfs2_kernel(const int4 *__restr
                                                             const int *__restrict__ lid, const int *__restrict__ seeds,
                                                             const int *__restrict__ koff, const int *__restrict__ sizes,
                                                             const int *__restrict__ star, int *qst_all, int *qln_all,
-                                                            int *cluster_idxs, int *dbg, int min_size, const int *__restrict__ cnt, int c0) {
+                                                            int *cluster_idxs, int min_size, const int *__restrict__ cnt, int c0) {
     extern __shared__ __attribute__((aligned(16))) int b2_smem[];
     if (cnt && (int)blockIdx.x + c0 >= cnt[1]) return;       // (speculative launch on an upper-bound grid: no such cluster)
-    int n_levels = 0, n_batches = 0;
-#ifdef B2_TIMING
-    long long tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tprev = (long long)__builtin_readcyclecounter();
-#endif
     unsigned int *bitmap = (unsigned int *)b2_smem;                 // B2_BITWORDS
     int *hkey = b2_smem + B2_BITWORDS;                              // B2_HASH
     int *hval = hkey + B2_HASH;                                     // B2_HASH
@@ -863,7 +854,6 @@ __global__ __launch_bounds__(B2_THREADS) void cl_bfs2_kernel(const int4 *__restr
                 if (tid == 0) coff[nf] = t0;
                 b2_barrier();
             }
-            B2_TICK(0)
             const int E = coff[nf];
             for (int e0 = 0; e0 < E; e0 += B2_BATCH) {
                 // A level is a chain of dependent LDS / L2 latencies, so the per-thread work is written for
@@ -896,16 +886,11 @@ __global__ __launch_bounds__(B2_THREADS) void cl_bfs2_kernel(const int4 *__restr
                         }
                     }
                 }
-                B2_TICK(2)
 #pragma unroll
                 for (int r = 0; r < B2_EPT; r++) rec[r] = erec[addr[r] >= 0 ? addr[r] : 0];   // branch-free: one wait for all
                 __builtin_amdgcn_sched_barrier(0);   // (keeps the first use, and its wait, behind the last load)
 #pragma unroll
                 for (int r = 0; r < B2_EPT; r++) if (addr[r] < 0) rec[r] = make_int4(-1, 0, 0, 0);
-#ifdef B2_TIMING
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-                B2_TICK(3)
                 unsigned int bw[B2_EPT];
 #pragma unroll
                 for (int r = 0; r < B2_EPT; r++) bw[r] = (rec[r].x >= 0) ? bitmap[rec[r].y >> 5] : 0xFFFFFFFFu;
@@ -930,7 +915,6 @@ __global__ __launch_bounds__(B2_THREADS) void cl_bfs2_kernel(const int4 *__restr
                     }
                 }
                 b2_barrier();
-                B2_TICK(4)
                 unsigned int win = 0u;
                 int nwin = 0, lwin = 0;
 #pragma unroll
@@ -952,7 +936,6 @@ __global__ __launch_bounds__(B2_THREADS) void cl_bfs2_kernel(const int4 *__restr
 #endif
                 int pos, lpos, tot, ltot;
                 b2_scan2(nwin, lwin, s_w, phase, pos, lpos, tot, ltot);   // (its barrier: every hval read is done)
-                B2_TICK(5)
                 int p = tail + pos, lp = ltail + lpos;
 #pragma unroll
                 for (int r = 0; r < B2_EPT; r++) {
@@ -981,21 +964,13 @@ __global__ __launch_bounds__(B2_THREADS) void cl_bfs2_kernel(const int4 *__restr
                 for (int r = 0; r < B2_EPT; r++) asm volatile("" :: "v"(pf0[r]), "v"(pf1[r]), "v"(pf2[r]));
 #endif
                 b2_barrier();
-                B2_TICK(6)
-                n_batches++;
-                if (tail >= size) {   // every node of the component is queued: the remaining edges (a dense component has
-                                      // ~size^2 of them) cannot discover anything
-                    if (dbg && tid == 0 && c < 20) { dbg[c * 3] = size; dbg[c * 3 + 1] = n_levels; dbg[c * 3 + 2] = n_batches; }
-                    B2_TDUMP
-                    return;
-                }
+                if (tail >= size) return;   // every node of the component is queued: the remaining edges (a dense component has
+                                            // ~size^2 of them) cannot discover anything
             }
         }
         hints_ok = (tail - hi) <= B2_FMAX && ltail <= B2_HINTS * B2_HGRID;
-        lo = hi; hi = tail; cur ^= 1; n_levels++;
+        lo = hi; hi = tail; cur ^= 1;
     }
-    if (dbg && tid == 0 && c < 20) { dbg[c * 3] = size; dbg[c * 3 + 1] = n_levels; dbg[c * 3 + 2] = n_batches; }
-    B2_TDUMP
 }
 
 
@@ -1042,26 +1017,14 @@ static int cl_fill2_impl(const int *semantic_label, const int *ball_query_idxs, 
         cl_ninfo_kernel<<<nb, T, 0, s>>>(w.own, w.lid, w.estart, start_len, w.ninfo, n);
         cl_erec_kernel<<<(int)(((long long)n * CL_EG + T - 1) / T), T, 0, s>>>(ball_query_idxs, start_len, w.own, w.flag, w.star, w.ninfo, w.estart, (int4 *)erec, n);
         }
-        const bool debug = d3_tune(D3T_BFS_DEBUG) != 0;
         // launch timing (bench.py): SURVEY 8(d) "BFS/CC" bytes = 4 nActive + 12 n + 8 S, nActive = the list entries of the kept
         // clusters' nodes (what the replay streams; the padded lists' capacity says nothing) -- known on the device only
         void *pr = d3_prof_begin(5, 12.0 * (double)n + (dev_counts ? 0.0 : 8.0 * (double)sumNPoint), 0.0, s);
         cl_bfs2_kernel<<<nCluster - c0, B2_THREADS, lds, s>>>((const int4 *)erec, start_len, w.estart, w.lid, w.seeds, w.koff, w.sizes,
-                                                        w.star, w.fcnt, w.qln, cluster_idxs, debug ? w.lcnt : nullptr, 0, cnt, c0);
+                                                        w.star, w.fcnt, w.qln, cluster_idxs, 0, cnt, c0);
         if (pr) {
             d3_prof_tag(pr, 0, n); d3_prof_tag(pr, 1, nCluster); d3_prof_end(pr, s);
             if (double *slot = d3_prof_dev_slot(pr, 4.0)) cl_prof_total_kernel<<<1, 1, 0, s>>>(w.estart, w.klen, n, slot, cnt);   // (behind the bracket)
-        }
-        if (debug && !dev_counts) {
-            int h[60 + 160];
-            hipMemcpyAsync(h, w.lcnt, sizeof(h), hipMemcpyDeviceToHost, s); hipStreamSynchronize(s);
-            for (int c = 0; c < nCluster && c < 20; c++) {
-                fprintf(stderr, "bfs2 cluster %d size %d levels %d batches %d", c, h[c * 3], h[c * 3 + 1], h[c * 3 + 2]);
-#if defined(B2_TIMING)
-                for (int k = 0; k < 8; k++) fprintf(stderr, " t%d=%d", k, h[60 + c * 8 + k] * 16);
-#endif
-                fprintf(stderr, "\n");
-            }
         }
         // clusters beyond the LDS bitmap: the generic level loop (none can exist when all kept points together fit)
         if (!dev_counts && c0 == 0 && sumNPoint > B2_MAXSIZE)
@@ -1096,7 +1059,7 @@ static std::vector<ClTicket *> g_clt_free;
 // sweeps, kept clusters beyond the speculative grid, clusters beyond the LDS bitmap).  ONE host thread can so keep two clusterings
 // (PointGroup's shifted and unshifted branch, on two streams) in flight: begin, begin, end, end -- no helper thread whose wake-up
 // sits on the step's critical path (on a slow host the wait for the helper's branch grew from 0.5 to 0.8 ms: profiles r05_d vs r05_e).
-// When the speculative form is not available (D3_CL_SPEC=0, debug, cap_points < n) `begin` runs the whole blocking call.
+// When the speculative form is not available (D3_CL_SPEC=0, cap_points < n) `begin` runs the whole blocking call.
 struct ClRun {
     const int *sem, *idx, *start_len; int n, threshold; void *ws; size_t ws_bytes; void *erec; size_t erec_bytes; long long nActive; int flags;
     int *cluster_idxs; long long cap_points; int *cluster_offsets; long long cap_clusters; void *stream;
@@ -1111,7 +1074,7 @@ extern "C" int d3_bfs_cluster_begin(const int *semantic_label, const int *ball_q
     *ticket = nullptr;
     ClRun *r = new ClRun{semantic_label, ball_query_idxs, start_len, n, threshold, ws, ws_bytes, erec, erec_bytes, nActive, flags,
                          cluster_idxs, cap_points, cluster_offsets, cap_clusters, stream, nullptr, 0, 0, 0, 0, 0};
-    if (n <= 0 || d3_tune(D3T_CL_SPEC) == 0 || d3_tune(D3T_BFS_DEBUG) != 0 || cap_points < n) {
+    if (n <= 0 || d3_tune(D3T_CL_SPEC) == 0 || cap_points < n) {
         int S = 0, P = 0;
         int rc = cl_count(semantic_label, ball_query_idxs, start_len, n, threshold, ws, ws_bytes, &S, &P, flags, stream);
         if (!rc && n > 0) {

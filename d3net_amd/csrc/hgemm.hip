@@ -395,7 +395,7 @@ static int hg_launch_batch(const d3_gemm_prob *probs, int nprobs, hipStream_t s)
     // (dW = dy^T x: 128 x 128 x 4096) ran the weight gradient on FOUR workgroups of the tiled kernel walking 128 (joint step: 384)
     // k slabs one after the other -- 212 us (643 us) per launch, 14 % of the listener step.  A mixed batch is split by class:
     // the deep, few-tile problems go to the K-split kernel (128 x 128 x 4096: ~17 us).
-    if (nprobs > 1 && d3_tune(D3T_HG_CLASS_SPLIT) != 0) {
+    if (nprobs > 1) {
         int cls[HG_MAXP], first = -1;
         bool mixed = false;
         for (int i = 0; i < nprobs; i++) {
@@ -454,8 +454,7 @@ static int hg_launch_batch(const d3_gemm_prob *probs, int nprobs, hipStream_t s)
     } while (0)
     if (maxM <= 32) {            // a decode step: K split over the waves of a workgroup
         if (maxM <= 16) HG_SPLIT(1, 1);
-        else if (d3_tune(D3T_HG_RT1) != 0) HG_SPLIT(1, 2);     // (one row tile per workgroup: twice the workgroups; 0: two tiles)
-        else HG_SPLIT(2, 1);
+        else HG_SPLIT(1, 2);     // (one row tile per workgroup: twice the workgroups of two tiles per workgroup)
     } else {
         const long long tiles16 = (long long)ctiles * ((maxM + 15) / 16);
         if (tiles16 < 2048) {    // few tiles: still split K so that the chip is covered

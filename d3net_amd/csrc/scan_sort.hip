@@ -24,7 +24,7 @@ int d3_exclusive_scan_i32(const int *in, int *out, int n, void *temp, size_t tem
 // rocPRIM's default sorts up to 2^20 items by block sort + merge passes whatever the key width (~35 launches for the 600 k points
 // of a clustering branch, ~200 us); the Onesweep radix path walks only the requested bits, 8 per pass (round 5: 22-bit cell-slot
 // keys = 3 passes behind one histogram launch).  Merge sort stays for the small inputs, where its few passes are cheaper.
-using D3SortConfig = rocprim::radix_sort_config<rocprim::default_config, rocprim::default_config, rocprim::default_config, 0>;      // (never merge: the caller decides by size, D3_SORT_ONESWEEP_MIN)
+using D3SortConfig = rocprim::radix_sort_config<rocprim::default_config, rocprim::default_config, rocprim::default_config, 0>;      // (never merge: the caller decides by size, kSortOnesweepMin)
 
 size_t d3_sort_pairs_temp_bytes(int n) {
     size_t bytes = 0, b2 = 0;
@@ -41,7 +41,10 @@ int d3_sort_pairs_i32(const int *kin, int *kout, const int *vin, int *vout, int 
     if (bits < 1) bits = 1;
     if (bits > 31) bits = 31;
     size_t need = 0;
-    if (n >= d3_tune(D3T_SORT_ONESWEEP_MIN)) {
+    // pair sorts of at least this many items take rocPRIM's Onesweep radix path (requested bits only, 8 per pass) instead of its default
+    // block sort + merge passes (~35 launches up to 2^20 items whatever the key width)
+    constexpr int kSortOnesweepMin = 65536;
+    if (n >= kSortOnesweepMin) {
         D3_CHECK(rocprim::radix_sort_pairs<D3SortConfig>(nullptr, need, kin, kout, vin, vout, (size_t)n, 0, (unsigned)bits, s));
         if (need > temp_bytes) return D3_ERR_WORKSPACE;
         D3_CHECK(rocprim::radix_sort_pairs<D3SortConfig>(temp, need, kin, kout, vin, vout, (size_t)n, 0, (unsigned)bits, s));

@@ -141,7 +141,6 @@ struct Conv2Args {
     int f32;                        // D3_CONV_F32: fp32 weight fragments, v_mfma_f32_16x16x4_f32 (host-side dispatch only)
     unsigned int xbytes;            // extent of x in bytes for the raw buffer gathers (0: beyond 2 GiB / 2^24 rows, refused for the wave-per-tile kernel)
     unsigned int invK;          // ceil(65536 / K): e / K for e < 16*27
-    int interleave;             // wave-per-tile kernel: the workgroups of an XCD take consecutive tile groups in turn (one moving window per L2)
     const unsigned int *tbl16;  // optional 16-bit delta form of tbl (coordmap.hip cm_pack16_kernel; validated by the caller), read as 32-bit
                                 // words by the T16 instances of the wave-per-tile kernel
     // BatchNorm-backward epilogue (data gradient of a BN -> ReLU -> conv unit): the stored value is g = dy * relu'(bn(x))
@@ -268,11 +267,11 @@ __device__ __forceinline__ void spconv_fwd2_body(const Conv2Args &a) {
     const int lb = ((nb & 7) == 0) ? (b & 7) * (nb >> 3) + (b >> 3) : b;
     const int ntg = (a.ntiles + NWT - 1) / NWT;
     const int per = (ntg + nb - 1) / nb;
-    // Round 4: with `interleave` the nb / 8 workgroups of an XCD take the XCD's tile groups IN TURN (iteration i of workgroup j:
+    // Round 4: the nb / 8 workgroups of an XCD take the XCD's tile groups IN TURN (iteration i of workgroup j:
     // group xcd_base + i * (nb / 8) + j) instead of one contiguous range each: at any moment the XCD works on ONE window of
     // (nb / 8) * NW * 16 consecutive rows plus its neighbourhood, which fits its 4 MB L2, where 32 separate windows do not (the
     // stem gathers 272-byte rows from +-1 x-slab: measured 1032 MB of HBM-side traffic per launch against 245 MB algorithmic).
-    const bool il = a.interleave && (nb & 7) == 0;
+    const bool il = (nb & 7) == 0;
     const int tstride = il ? (nb >> 3) : 1;
     const int tg0 = il ? (b & 7) * (nb >> 3) * per + (b >> 3) : lb * per;
     const int tg1 = il ? min(ntg, ((b & 7) + 1) * (nb >> 3) * per) : min(ntg, tg0 + per);
@@ -798,7 +797,8 @@ static Conv2Plan conv2_plan(int Mout, int K, int Cin, int Cout, bool f32 = false
     if (ntiles >= 1024) {
         p.split = 0; p.W = 1;
         // 16 waves around ONE LDS copy of a large weight set (one workgroup per CU), 4 waves per workgroup otherwise
-        const size_t big_from = (size_t)d3_tune(D3T_C2_NW16_KB) * 1024, lds_max = (size_t)160 * 1024;
+        constexpr size_t big_from = (size_t)24 * 1024;      // packed weights of at least this many bytes: 16 waves share one LDS copy
+        const size_t lds_max = (size_t)160 * 1024;
         if (NT <= C2_NW16_MAXNT && wbytes >= big_from && wbytes + C2_WAVE_LDS_BYTES(NT, 16) <= lds_max && wbytes + C2_WAVE_LDS_BYTES(NT, 16) <= 160 * 1024)
             p.nw = 16;
         const int ntg = (ntiles + p.nw - 1) / p.nw;
@@ -916,7 +916,7 @@ static int launch_fwd2_static(const Conv2Args &a, const Conv2Plan &p, hipStream_
 template <int NT>
 static int launch_fwd2(const Conv2Args &a, const Conv2Plan &p, hipStream_t s) {
     if (a.f32) return launch_fwd2_f32<NT>(a, p, s);
-    if (a.xbf16 && a.K == 27 && p.wlds && d3_tune(D3T_C2_STATIC) != 0) {
+    if (a.xbf16 && a.K == 27 && p.wlds) {
         if constexpr (NT == 1) {
             if (a.S == 2 && p.nw == 4) return launch_fwd2_static<1, 4, 2>(a, p, s);      // 16 -> 16
             if (a.S == 4 && p.nw == 16) return launch_fwd2_static<1, 16, 4>(a, p, s);    // 32 -> 16
@@ -1018,7 +1018,6 @@ static int conv2_run(const void *x, int ldx, const int *tbl, const void *Wp, flo
     hipStream_t s = d3_stream(stream);
     // round 6: the big levels' K = 27 layers on the lane table (spconv3.hip) -- bf16 rows, no accumulate-into
     if (tblq && tbl && K == 27 && xbf16 && !f32 && !(flags & D3_CONV_ACCUM) && d3_tune(D3T_C3) != 0 &&
-        (d3_tune(D3T_C3) == 1 || (d3_tune(D3T_C3) == 2 && !bn) || (d3_tune(D3T_C3) == 3 && bn) || (d3_tune(D3T_C3) == 4 && !bn && !res) || (d3_tune(D3T_C3) == 5 && res)) &&      // (2 .. 5: debugging -- forward only / data gradients only / plain forward / residual forward)
         Mout >= C2_GRIDCAP * 16 && d3_spconv_fwd3_nparts(Mout, Cin, Cout) > 0 && !(bn && res)) {
         Conv3Bn b3;
         if (bn) b3 = Conv3Bn{bn->x, bn->mean, bn->var, bn->gamma, bn->beta, bn->ldx, bn->relu, bn->xbf16, bn->eps};
@@ -1033,7 +1032,6 @@ static int conv2_run(const void *x, int ldx, const int *tbl, const void *Wp, flo
     a.ldx = ldx; a.ldo = ldo; a.ldr = ldr; a.Mout = Mout; a.K = K; a.Cout = Cout; a.S = Cin / 8;
     a.inv = (65536u + a.S - 1) / a.S;
     a.invK = (65536u + K - 1) / K;
-    a.interleave = d3_tune(D3T_C2_INTERLEAVE) != 0 ? 1 : 0;
     a.tbl16 = (tbl && tbl16 && K == 27 && !f32 && xbf16) ? (const unsigned int *)tbl16 : nullptr;   // (only the static instances launch with it)
     a.xbf16 = xbf16; a.f32 = f32; a.accum = (flags & D3_CONV_ACCUM) ? 1 : 0; a.ntiles = (Mout + 15) / 16;
     a.obf16 = (flags & D3_CONV_OUTBF16) ? 1 : 0;
@@ -1119,7 +1117,6 @@ extern "C" int d3_spconv_fwd2_bnbwd(const void *x, int ldx, const int *tbl, cons
 // TPO tiles per offset; the 4 waves of a workgroup take alternate chunks and are summed through LDS in wave order;
 // with R > 1 the workgroup writes a partial dW that wgrad2_reduce_kernel sums in split order (deterministic; no
 // atomics).
-#define WG2_LDT 40      // shorts per transposed LDS row: 32 rows + 8 pad (80 B)
 #ifndef WG2_TARGET_WGS
 #define WG2_TARGET_WGS 512   // workgroups per launch the row split aims at
 #endif
@@ -1138,7 +1135,7 @@ struct Wg2Args {
     unsigned int invg, invs;    // ceil(65536 / Cg8), ceil(65536 / Cs8)
     int cpw;                    // chunks per workgroup
     int gx, flipk, Cin, Cout;   // gx: the gathered operand is x (P = dW[k]); else it is dy (P = dW[k]^T)
-    int rsg, dg, rss, dss;      // row-major LDS images (TR kernels): row stride and 8-row shift in bytes, per operand
+    int rsg, dg, rss, dss;      // row-major LDS images: row stride and 8-row shift in bytes, per operand
     int imgg, imgs;             // image sizes in bytes
 };
 
@@ -1175,22 +1172,15 @@ __device__ __forceinline__ uint4 wg2_load8(const void *p, int bf16, long long of
     const float4 f1 = *(const float4 *)((const float *)p + off + 4);
     return make_uint4(pack2bf2(f0.x, f0.y), pack2bf2(f0.z, f0.w), pack2bf2(f1.x, f1.y), pack2bf2(f1.z, f1.w));
 }
-__device__ __forceinline__ void wg2_store_t(unsigned short *T, int c8, int row, uint4 v) {
-    unsigned short *d = T + (c8 * 8) * WG2_LDT + row;
-    d[0 * WG2_LDT] = (unsigned short)(v.x & 0xFFFFu); d[1 * WG2_LDT] = (unsigned short)(v.x >> 16);
-    d[2 * WG2_LDT] = (unsigned short)(v.y & 0xFFFFu); d[3 * WG2_LDT] = (unsigned short)(v.y >> 16);
-    d[4 * WG2_LDT] = (unsigned short)(v.z & 0xFFFFu); d[5 * WG2_LDT] = (unsigned short)(v.z >> 16);
-    d[6 * WG2_LDT] = (unsigned short)(v.w & 0xFFFFu); d[7 * WG2_LDT] = (unsigned short)(v.w >> 16);
-}
 
-template <int TPO, int NU, bool TR>
+template <int TPO, int NU>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WG2_T > 16 ? (NU <= 7 ? 2 : 1) : (NU <= 2 ? 3 : NU <= 7 ? 2 : 1), 8))) void spconv_wgrad2_kernel(const Wg2Args a) {
     constexpr int OPW = WG2_T / TPO;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6, r = lane & 15, g = lane >> 4;
     const int K = a.K;
-    // per-wave LDS: the two operand images (TR: row-major, else transposed mt*16 / nt*16 x LDT bf16), table chunk 32*K ints
-    const size_t gt_bytes = TR ? (size_t)a.imgg : (size_t)a.mt * 16 * WG2_LDT * 2, st_bytes = TR ? (size_t)a.imgs : (size_t)a.nt * 16 * WG2_LDT * 2;
+    // per-wave LDS: the two row-major operand images, table chunk 32*K ints
+    const size_t gt_bytes = (size_t)a.imgg, st_bytes = (size_t)a.imgs;
     const size_t wave_bytes = gt_bytes + st_bytes + (size_t)32 * C2_MAXK * 4;
     unsigned short *Gt = (unsigned short *)(smem + (size_t)wave * wave_bytes);
     unsigned short *St = (unsigned short *)((unsigned char *)Gt + gt_bytes);
@@ -1252,8 +1242,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WG2_T > 16 
                 const int unit = ub + q * 64 + lane;
                 if (unit < 32 * sc8n) {
                     const int row = unit / sc8n, c8 = sc8lo + unit - row * sc8n;
-                    if constexpr (TR) wg2_put_r((unsigned char *)St, a.rss, a.dss, c8, row, sv[q]);
-                    else wg2_store_t(St, c8, row, sv[q]);
+                    wg2_put_r((unsigned char *)St, a.rss, a.dss, c8, row, sv[q]);
                 }
             }
         }
@@ -1299,8 +1288,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WG2_T > 16 
                         const int unit = lane + q * 64;
                         if (unit < 32 * a.Cg8) {
                             const int row = (int)(((unsigned int)unit * a.invg) >> 16), c8 = unit - row * a.Cg8;
-                            if constexpr (TR) wg2_put_r((unsigned char *)Gt, a.rsg, a.dg, c8, row, pre[pf][q]);
-                            else wg2_store_t(Gt, c8, row, pre[pf][q]);
+                            wg2_put_r((unsigned char *)Gt, a.rsg, a.dg, c8, row, pre[pf][q]);
                         }
                     }
                     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -1311,14 +1299,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WG2_T > 16 
                         const int tile = tile0 + i;
                         if (tile < ntl) {   // uniform
                             const int mi = tile / a.nt, ni = tile - mi * a.nt;
-                            bf16x8_t av, bv;
-                            if constexpr (TR) {
-                                av = wg2_frag_tr((const unsigned char *)Gt, lbg, a.rsg, mi);
-                                bv = wg2_frag_tr((const unsigned char *)St, lbs, a.rss, ni);
-                            } else {
-                                av = __builtin_bit_cast(bf16x8_t, *(const uint4 *)&Gt[(mi * 16 + r) * WG2_LDT + g * 8]);
-                                bv = __builtin_bit_cast(bf16x8_t, *(const uint4 *)&St[(ni * 16 + r) * WG2_LDT + g * 8]);
-                            }
+                            const bf16x8_t av = wg2_frag_tr((const unsigned char *)Gt, lbg, a.rsg, mi);
+                            const bf16x8_t bv = wg2_frag_tr((const unsigned char *)St, lbs, a.rss, ni);
                             acc[j < OPW ? j : 0][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, bv, acc[j < OPW ? j : 0][i], 0, 0, 0);
                         }
                     }
@@ -1375,13 +1357,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WG2_T > 16 
 // has a single owner: no cross-wave reduction; row splits write partial dW summed by the fixed-order reduction.
 #define WGW_WAVES 16
 #define WGW_MAXNT 9
-template <int NTV, bool TR>
+template <int NTV>
 __global__ __launch_bounds__(WGW_WAVES * 64) void spconv_wgrad2_wide_kernel(const Wg2Args a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6, r = lane & 15, g = lane >> 4;
     const int K = a.K;
-    const size_t st_bytes = TR ? (size_t)a.imgs : (size_t)NTV * 16 * WG2_LDT * 2;
-    const size_t gslot = TR ? (size_t)a.imgg : (size_t)16 * WG2_LDT * 2;          // one gathered 32 x 16 image
+    const size_t st_bytes = (size_t)a.imgs;
+    const size_t gslot = (size_t)a.imgg;          // one gathered 32 x 16 image
     unsigned short *St = (unsigned short *)smem;                                   // stationary chunk, shared by the waves
     int *tblS = (int *)(smem + st_bytes);                                          // 32 x K
     unsigned short *Gt = (unsigned short *)((unsigned char *)(tblS + 32 * C2_MAXK) + (size_t)wave * 2 * gslot);   // 2 slots per wave
@@ -1414,8 +1396,7 @@ __global__ __launch_bounds__(WGW_WAVES * 64) void spconv_wgrad2_wide_kernel(cons
         if (t < 32 * K) tblS[t] = a.tbl ? tv : (u0 + t < a.Ms ? u0 + t : -1);
         if (t < sunits) {
             const int row = t / a.Cs8, c8 = t - row * a.Cs8;
-            if constexpr (TR) wg2_put_r((unsigned char *)St, a.rss, a.dss, c8, row, sv);
-            else wg2_store_t(St, c8, row, sv);
+            wg2_put_r((unsigned char *)St, a.rss, a.dss, c8, row, sv);
         }
         __syncthreads();
         if (c + 1 < c_end) prefetch(c + 1);
@@ -1436,24 +1417,17 @@ __global__ __launch_bounds__(WGW_WAVES * 64) void spconv_wgrad2_wide_kernel(cons
         }
 #pragma unroll
         for (int j = 0; j < 2; j++)
-            if (any[j]) {
-                if constexpr (TR) wg2_put_r((unsigned char *)Gt + j * gslot, a.rsg, a.dg, lane & 1, lane >> 1, gv[j]);
-                else wg2_store_t(Gt + (size_t)j * 16 * WG2_LDT, lane & 1, lane >> 1, gv[j]);
-            }
+            if (any[j]) wg2_put_r((unsigned char *)Gt + j * gslot, a.rsg, a.dg, lane & 1, lane >> 1, gv[j]);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 #pragma unroll
         for (int j = 0; j < 2; j++) {
             if (!any[j]) continue;      // wave-uniform
-            bf16x8_t av;
-            if constexpr (TR) av = wg2_frag_tr((const unsigned char *)Gt + j * gslot, lbg, a.rsg, 0);
-            else av = __builtin_bit_cast(bf16x8_t, *(const uint4 *)&Gt[(size_t)j * 16 * WG2_LDT + r * WG2_LDT + g * 8]);
+            const bf16x8_t av = wg2_frag_tr((const unsigned char *)Gt + j * gslot, lbg, a.rsg, 0);
 #pragma unroll
             for (int i = 0; i < NTV; i++) {
-                bf16x8_t bv;
-                if constexpr (TR) bv = wg2_frag_tr((const unsigned char *)St, lbs, a.rss, i);
-                else bv = __builtin_bit_cast(bf16x8_t, *(const uint4 *)&St[(i * 16 + r) * WG2_LDT + g * 8]);
+                const bf16x8_t bv = wg2_frag_tr((const unsigned char *)St, lbs, a.rss, i);
                 acc[j][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, bv, acc[j][i], 0, 0, 0);
             }
         }
@@ -1898,16 +1872,12 @@ static int launch_wgf(const WgfArgs &a, const WgfCfg &c, int R, hipStream_t s) {
     return D3_ERR_ARG;
 }
 
-struct Wg2Plan { int tpo, nu, opw, kg, passes, R, cpw, wide, tr; int rsg, dg, imgg, rss, dss, imgs; size_t lds, ws_bytes; const Wg3Cfg *w3; };
-
-// D3_WG2_TR=0 selects the first staging scheme (transposed ds_write_b16 images) for A/B measurements
-static bool wg2_use_tr() { return d3_tune(D3T_WG2_TR) != 0; }
+struct Wg2Plan { int tpo, nu, opw, kg, passes, R, cpw, wide; int rsg, dg, imgg, rss, dss, imgs; size_t lds, ws_bytes; const Wg3Cfg *w3; };
 
 static Wg2Plan wg2_plan(int Ms, int Mg, int K, int Cg, int Cs, int Cin, int Cout, bool gx, bool gbf, bool sbf) {
     Wg2Plan p;
     const int mt = (Cg + 15) / 16, nt = (Cs + 15) / 16, ntl = mt * nt;
     p.wide = 0;
-    p.tr = wg2_use_tr() ? 1 : 0;
     wg2_img(Cg / 8, &p.rsg, &p.dg, &p.imgg);
     wg2_img(Cs / 8, &p.rss, &p.dss, &p.imgs);
     p.imgg = (p.imgg + 15) & ~15; p.imgs = (p.imgs + 15) & ~15;
@@ -1930,8 +1900,7 @@ static Wg2Plan wg2_plan(int Ms, int Mg, int K, int Cg, int Cs, int Cin, int Cout
         int R = 256; if (R > (nchunks + 3) / 4) R = (nchunks + 3) / 4; if (R < 1) R = 1;
         p.cpw = (nchunks + R - 1) / R;
         p.R = (nchunks + p.cpw - 1) / p.cpw;
-        p.lds = p.tr ? (size_t)p.imgs + (size_t)32 * C2_MAXK * 4 + (size_t)WGW_WAVES * 2 * p.imgg
-                     : (size_t)nt * 16 * WG2_LDT * 2 + (size_t)32 * C2_MAXK * 4 + (size_t)WGW_WAVES * 2 * 16 * WG2_LDT * 2;
+        p.lds = (size_t)p.imgs + (size_t)32 * C2_MAXK * 4 + (size_t)WGW_WAVES * 2 * p.imgg;
         p.ws_bytes = (size_t)p.R * K * Cin * Cout * 4;
         return p;
     }
@@ -1951,7 +1920,7 @@ static Wg2Plan wg2_plan(int Ms, int Mg, int K, int Cg, int Cs, int Cin, int Cout
     p.cpw = (nchunks + R - 1) / R;
     p.cpw = (p.cpw + 3) / 4 * 4;
     p.R = (nchunks + p.cpw - 1) / p.cpw;
-    const size_t wave_bytes = (p.tr ? (size_t)p.imgg + p.imgs : (size_t)(mt + nt) * 16 * WG2_LDT * 2) + (size_t)32 * C2_MAXK * 4;
+    const size_t wave_bytes = (size_t)p.imgg + p.imgs + (size_t)32 * C2_MAXK * 4;
     p.lds = 4 * wave_bytes; if (p.lds < 32 * 1024) p.lds = 32 * 1024;
     p.ws_bytes = p.R > 1 ? (size_t)p.R * wsz : 0;
     return p;
@@ -2015,12 +1984,9 @@ static int launch_wg3(const Wg3Args &a, const Wg2Plan &p, bool dybf, hipStream_t
 template <int TPO, int NU>
 static int launch_wg2(const Wg2Args &a, const Wg2Plan &p, hipStream_t s) {
     static bool attr_done_dev[64] = {false};
-    if (c2_attr_needed(attr_done_dev)) {
-        D3_CHECK(hipFuncSetAttribute((const void *)spconv_wgrad2_kernel<TPO, NU, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-        D3_CHECK(hipFuncSetAttribute((const void *)spconv_wgrad2_kernel<TPO, NU, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-    }
-    if (p.tr) spconv_wgrad2_kernel<TPO, NU, true><<<dim3(p.R, p.kg, p.passes), 256, p.lds, s>>>(a);
-    else spconv_wgrad2_kernel<TPO, NU, false><<<dim3(p.R, p.kg, p.passes), 256, p.lds, s>>>(a);
+    if (c2_attr_needed(attr_done_dev))
+        D3_CHECK(hipFuncSetAttribute((const void *)spconv_wgrad2_kernel<TPO, NU>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
+    spconv_wgrad2_kernel<TPO, NU><<<dim3(p.R, p.kg, p.passes), 256, p.lds, s>>>(a);
     D3_LAUNCH_CHECK();
     return 0;
 }
@@ -2117,12 +2083,8 @@ extern "C" int d3_spconv_wgrad2(const void *x, int ldx, const int *tbl, const vo
         const bool set = c2_attr_needed(wide_attr);
 #define WGW_CASE(NTV)                                                                                                              \
         case NTV:                                                                                                                      \
-            if (set) {                                                                                                                 \
-                D3_CHECK(hipFuncSetAttribute((const void *)spconv_wgrad2_wide_kernel<NTV, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024)); \
-                D3_CHECK(hipFuncSetAttribute((const void *)spconv_wgrad2_wide_kernel<NTV, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024)); \
-            }                                                                                                                          \
-            if (p.tr) spconv_wgrad2_wide_kernel<NTV, true><<<p.R, WGW_WAVES * 64, p.lds, s>>>(a);                                      \
-            else spconv_wgrad2_wide_kernel<NTV, false><<<p.R, WGW_WAVES * 64, p.lds, s>>>(a);                                          \
+            if (set) D3_CHECK(hipFuncSetAttribute((const void *)spconv_wgrad2_wide_kernel<NTV>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024)); \
+            spconv_wgrad2_wide_kernel<NTV><<<p.R, WGW_WAVES * 64, p.lds, s>>>(a);                                                      \
             break;
         switch (a.nt) { WGW_CASE(5) WGW_CASE(6) WGW_CASE(7) WGW_CASE(8) WGW_CASE(9) default: return D3_ERR_ARG; }
 #undef WGW_CASE

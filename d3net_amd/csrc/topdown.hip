@@ -282,7 +282,7 @@ __global__ __launch_bounds__(GRU4_NW * 64) void td_gru4_fwd_kernel(const GruArgs
 static int td_gru_fwd(const GruArgs &a, hipStream_t s) {
     if (a.H & 15) return D3_ERR_ARG;
     if (a.N <= 0) return 0;
-    if (d3_tune(D3T_GRU4) != 0 && a.N <= 256) {   // gate-packed columns: 4 hidden units per workgroup
+    if (a.N <= 256) {   // gate-packed columns: 4 hidden units per workgroup
         // launch timing (bench.py): a GRU cell = two skinny fp32 GEMMs (N x 3H x I, N x 3H x H) + gates; bytes = weights + rows once
         const int I = a.gi_pre ? 0 : a.I;
         void *pr = d3_prof_begin(4, 4.0 * (3.0 * a.H * (I + a.H) + (double)a.N * (I + 6.0 * a.H)), 2.0 * a.N * 3.0 * a.H * (I + a.H), s);
@@ -291,9 +291,8 @@ static int td_gru_fwd(const GruArgs &a, hipStream_t s) {
         D3_LAUNCH_CHECK();
         return 0;
     }
-    // (17..64 rows: one 16-row tile per workgroup -- twice the workgroups, half the MFMA chain of each; D3_GRU_RT1=0: two tiles)
-    if (a.N <= 16 || (a.N <= 64 && d3_tune(D3T_GRU_RT1) != 0)) td_gru_fwd_kernel<1><<<dim3(a.H / 16, (a.N + 15) / 16), GRU_NW * 64, 0, s>>>(a);
-    else td_gru_fwd_kernel<2><<<dim3(a.H / 16, (a.N + 31) / 32), GRU_NW * 64, 0, s>>>(a);
+    // more than 256 rows: 16 hidden units x 3 gate tiles per workgroup, two 16-row tiles each
+    td_gru_fwd_kernel<2><<<dim3(a.H / 16, (a.N + 31) / 32), GRU_NW * 64, 0, s>>>(a);
     D3_LAUNCH_CHECK();
     return 0;
 }

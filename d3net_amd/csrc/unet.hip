@@ -691,7 +691,7 @@ struct Net {
     size_t jobs_cap = 0;
     long long pack_total = 0;
     hipStream_t side = nullptr;
-    hipStream_t side2 = nullptr;      // second weight-gradient stream (D3_SIDE2)
+    hipStream_t side2 = nullptr;      // second weight-gradient stream
     std::vector<hipEvent_t> ev;       // pool
     size_t ev_used = 0;
     // gradient chunks (data-parallel overlap): chunk k of the flat parameter-gradient buffer is complete once the backward has
@@ -1266,10 +1266,9 @@ static int net_forward_impl(void *h, const void *const *params, const int *const
                 const int fs_rows = d3_tune(D3T_BN_FUSED_ROWS);
                 // (with the second-level tables the reduction is 16 rows whatever the producer's grid was: no size limit)
                 const long long part_floats = use_p2 ? 0ll : 2ll * ss[0].nparts * ss[0].cn + (o.srcs.size() > 1 ? 2ll * ss[1].nparts * ss[1].cn : 0ll);
-                const int fs_big = d3_tune(D3T_BN_FUSED_BIG);
-                if (M > 0 && (M <= fs_rows || (fs_big && fs_rows > 0)) && C <= UN_FS_MAXC && part_floats <= UN_FS_MAX_PART_FLOATS) {
+                if (M > 0 && fs_rows > 0 && C <= UN_FS_MAXC && part_floats <= UN_FS_MAX_PART_FLOATS) {
                     // statistics + normalisation in one launch (un_bn_fused_small_kernel); big levels: up to 512 workgroups
-                    int G, rows_pb; un_fs_grid(M, C, G, rows_pb, M <= fs_rows ? 32 : (fs_big > 1 ? fs_big : 512));
+                    int G, rows_pb; un_fs_grid(M, C, G, rows_pb, M <= fs_rows ? 32 : 512);
                     float *rm = o.rmean >= 0 ? (float *)params[o.rmean] : nullptr, *rv = o.rvar >= 0 ? (float *)params[o.rvar] : nullptr;
 #define UN_FSF(OBFV, XBFV)                                                                                                             \
                     un_bn_fused_small_kernel<OBFV, XBFV><<<G, UN_FS_T, 0, s>>>(ss[0], ss[1], (const float *)tptr(n, arena, input, o.in), ti.ld, gamma, beta, \
@@ -1352,8 +1351,8 @@ static int net_backward_impl(void *h, const void *const *params, const int *cons
     // gradients stay on the caller's stream (no events).  Big ones use the side stream; the "a side-stream kernel still
     // reads this gradient buffer" hazard gets an event only for the convolutions whose output gradient is later
     // accumulated into in place (residual aliases: known from the program, OpD::wg_hazard).
-    const int side_min_rows = d3_tune(D3T_SIDE_MIN_ROWS);   // (experiments)
-    const bool use_side = n->rows[0] >= side_min_rows;
+    constexpr int kSideMinRows = 32768;      // level-0 rows from which the weight gradients run on the side streams
+    const bool use_side = n->rows[0] >= kSideMinRows;
     hipStream_t ws_stream = use_side ? n->side : s;
     std::map<int, hipEvent_t> pending;   // gradient buffer root -> event after its last side-stream reader
     bool side_used = false;
@@ -1371,7 +1370,9 @@ static int net_backward_impl(void *h, const void *const *params, const int *cons
     // row-split partials -> dW in batched launches on the weight-gradient stream: one when only the last few convolutions of
     // the backward (the first of the network: level 0, small weights) are left, one at the very end -- a single launch at the
     // end left its 137 us exposed behind the stem's weight gradient, after the caller's stream had nothing left to do
-    const int side2_mode = (use_side && n->side2) ? d3_tune(D3T_SIDE2) : 0;
+    // All weight gradients alternate between TWO side streams (speaker step 17.71 -> 17.49 ms in-process against one stream; only the
+    // gradients whose dy buffer is later accumulated into in place on the second stream: 17.57; detector step inside the noise).
+    const bool use_side2 = use_side && n->side2;
     bool side2_dirty = false;                               // side2 holds weight gradients the batched reduction / the join has not been ordered behind yet
     int side2_flip = 0;
     auto join_side2 = [&]() -> int {                        // ws_stream waits for everything enqueued on side2
@@ -1410,10 +1411,10 @@ static int net_backward_impl(void *h, const void *const *params, const int *cons
         red_blocks = 0;
         return 0;
     };
-    const int flush_tail = d3_tune(D3T_RED_TAIL);
+    constexpr int kRedTail = 5;      // flush the batched weight-gradient reduction when this many convolutions are left
     int tail_idx = -1;
-    for (int i = 0, c = 0; i < (int)n->ops.size() && flush_tail > 0; i++)
-        if (n->ops[i].type == OP_CONV && pgrads[n->ops[i].w] != nullptr && ++c == flush_tail) { tail_idx = i; break; }
+    for (int i = 0, c = 0; i < (int)n->ops.size(); i++)
+        if (n->ops[i].type == OP_CONV && pgrads[n->ops[i].w] != nullptr && ++c == kRedTail) { tail_idx = i; break; }
     size_t next_chunk = 0;
     auto chunk_done = [&](int i) -> int {      // op i has been processed: close every chunk that ends here
         while (next_chunk < n->chunk_op.size() && n->chunk_op[next_chunk] >= i) {
@@ -1481,7 +1482,7 @@ static int net_backward_impl(void *h, const void *const *params, const int *cons
                 if (!op_side) main_wgrads = true;
                 hipStream_t wst = ws_stream;                 // the stream of THIS weight gradient
                 if (op_side) {
-                    if (side2_mode == 2 ? (side2_flip++ & 1) : (side2_mode == 1 && root_o >= 0 && o.wg_hazard)) { wst = n->side2; side2_dirty = true; }
+                    if (use_side2 && (side2_flip++ & 1)) { wst = n->side2; side2_dirty = true; }
                     D3_CHECK(hipStreamWaitEvent(wst, e1, 0));
                     side_used = true;
                 }
@@ -1527,10 +1528,10 @@ static int net_backward_impl(void *h, const void *const *params, const int *cons
             const float *x = (const float *)tptr(n, arena, input, o.in);
             int relu = o.relu;
             const int fs_rows_b = d3_tune(D3T_BN_FUSED_ROWS);
-            if (o.fused_by >= 0 && (M <= fs_rows_b || (d3_tune(D3T_BN_FUSED_BIG) && fs_rows_b > 0)) && C <= UN_FS_MAXC &&
+            if (o.fused_by >= 0 && fs_rows_b > 0 && C <= UN_FS_MAXC &&
                 (use_p2 || 2ll * o.bparts * C <= UN_FS_MAX_PART_FLOATS)) {
                 // the epilogue partials -> sums / dgamma / dbeta and the input gradient in one launch
-                int G, rows_pb; un_fs_grid(M, C, G, rows_pb, M <= fs_rows_b ? 32 : (d3_tune(D3T_BN_FUSED_BIG) > 1 ? d3_tune(D3T_BN_FUSED_BIG) : 512));
+                int G, rows_pb; un_fs_grid(M, C, G, rows_pb, M <= fs_rows_b ? 32 : 512);
                 float *gi = nullptr; int ldgi = 0, root_i = -1, gibf = 0;
                 if (o.in_grad_mode) {
                     gi = gptr(n, garena, gout, gin, o.in, ldgi, root_i, &gibf);

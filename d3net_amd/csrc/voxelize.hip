@@ -189,8 +189,7 @@ extern "C" int d3_voxelize_fp2(const float *feats_a, int Ca, const float *feats_
     if (Ca < 1 || Cb < 0) return D3_ERR_ARG;
     const long long total = (long long)nActive * (Ca + Cb);
     if (total <= 0) return 0;
-    const int rows_form = d3_tune(D3T_VOX_ROWS);
-    if (rows_form && Ca + Cb >= 48)      // wide rows: a wave per voxel
+    if (Ca + Cb >= 48)      // wide rows: a wave per voxel
         voxelize_fp2_rows_kernel<<<(nActive + 3) / 4, 256, 0, d3_stream(stream)>>>(feats_a, Ca, feats_b, Cb, output_feats, output_map, nActive,
                                                                                   maxActive, mode == 4);
     else

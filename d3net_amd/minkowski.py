@@ -73,21 +73,6 @@ def exact_for(training, name=None):
     return _EXACT or (not training and (_EVAL_EXACT or (name is not None and name in _EVAL_EXACT_ONLY)))
 
 
-class heads_exact_for:
-    """`with heads_exact_for(training):` -- kept as the one place where the heads' arithmetic would follow the evaluation policy of
-    the U-Nets; the heads' GEMMs are exact fp32 MFMA in every mode (round 4's bf16 x 3 split was measured, not adopted, and removed in
-    round 6), so this is a no-op context."""
-
-    def __init__(self, training):
-        self.training = training
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        return False
-
-
 def _mode_flag():
     return D3_CONV_EXACT if _EXACT else 0
 

@@ -1,7 +1,6 @@
 #!/usr/bin/env python3
-"""A/B micro-benchmark of `spconv_fwd2_kernel` (csrc/spconv2.hip) on the coordinate levels of bench.py's 4-scene batch:
-pre-packed weights, bf16 / fp32 gathers, 4-wave workgroups vs 16 waves around one LDS copy of the weights
-(switch D3_C2_NW16_KB flipped through d3_tuning_set), results cross-checked.
+"""Micro-benchmark of `spconv_fwd2_kernel` (csrc/spconv2.hip) on the coordinate levels of bench.py's 4-scene batch:
+pre-packed weights, bf16 / fp32 gathers, the workgroup shape conv2_plan picks (4 waves, or 16 waves around one LDS copy of the weights).
 usage: python tools/fwd2_bench.py [scenes=4] [iters=30]"""
 import ctypes as C
 import os
@@ -42,9 +41,7 @@ def main():
     batch = S.make_batch(scenes, dev)
     cm = ME.CoordinateManager(batch["voxel_locs"].int().contiguous())
     shapes = {0: [(136, 16), (16, 16), (32, 16)], 1: [(32, 32), (64, 32), (32, 64)], 2: [(48, 48), (96, 48), (48, 96)]}
-    modes = (("nw4", 1 << 20), ("nw16", 24))
-    print("%-18s %8s %8s | %-28s | %9s %9s | %9s %9s | maxrel" % ("layer", "rows", "W KB", "plan nw4 -> nw16 (waves, grid, wlds)", "bf16 nw4", "bf16 nw16",
-                                                                   "fp32 nw4", "fp32 nw16"))
+    print("%-18s %8s %8s | %-24s | %9s %9s | maxrel" % ("layer", "rows", "W KB", "plan (waves, grid, wlds)", "bf16 us", "fp32 us"))
     ts = 1
     for lev in range(3):
         nbr = cm.k3(ts)
@@ -61,20 +58,14 @@ def main():
             def run(x, fl):
                 rc = L.d3_spconv_fwd2(_ptr(x), x.stride(0), _ptr(nbr), _ptr(wp), _ptr(out), cout, None, 0, None, M, M, 27, cin, cout, fl, _stream())
                 assert rc == 0, rc
-            res, plans, outs = {}, [], {}
-            for name, kb in modes:
-                assert L.d3_tuning_set(b"D3_C2_NW16_KB", kb) == 0
-                p = (C.c_int * 6)()
-                assert L.d3_spconv_fwd2_plan(M, 27, cin, cout, p) == 0
-                plans.append("%d/%d/%d" % (p[1], p[2], p[3]))
-                res[name, "bf16"] = timeit(lambda: run(xb, XBF16), iters)
-                outs[name] = out.clone()
-                res[name, "fp32"] = timeit(lambda: run(xf, 0), iters)
-            assert L.d3_tuning_set(b"D3_C2_NW16_KB", 24) == 0
-            rel = float((outs["nw4"] - outs["nw16"]).abs().max() / outs["nw4"].abs().max())
-            print("%-18s %8d %8.1f | %-28s | %9.1f %9.1f | %9.1f %9.1f | %.1e" %
-                  ("L%d k3 %d->%d" % (lev, cin, cout), M, wp.numel() / 1024, " -> ".join(plans), res["nw4", "bf16"], res["nw16", "bf16"],
-                   res["nw4", "fp32"], res["nw16", "fp32"], rel))
+            p = (C.c_int * 6)()
+            assert L.d3_spconv_fwd2_plan(M, 27, cin, cout, p) == 0
+            t_bf = timeit(lambda: run(xb, XBF16), iters)
+            out_bf = out.clone()
+            t_f32 = timeit(lambda: run(xf, 0), iters)
+            rel = float((out_bf - out).abs().max() / out.abs().max())      # bf16 gathers against fp32 gathers
+            print("%-18s %8d %8.1f | %-24s | %9.1f %9.1f | %.1e" %
+                  ("L%d k3 %d->%d" % (lev, cin, cout), M, wp.numel() / 1024, "%d/%d/%d" % (p[1], p[2], p[3]), t_bf, t_f32, rel))
         if lev < 2:
             cm.down(ts)      # creates the next coordinate level
         ts *= 2

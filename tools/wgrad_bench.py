@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Weight-gradient kernels per layer shape on the bench workload's coordinate levels (N scenes of the speaker config):
-third-generation kernel (spconv_wgrad3_kernel) vs the generic kernel with transposing LDS reads vs its first staging scheme,
-selected per call through D3_WG3 / D3_WG2_TR, results cross-checked against the first scheme.
+third-generation kernel (spconv_wgrad3_kernel) vs the generic kernel with transposing LDS reads,
+selected per call through D3_WG3, results cross-checked against the generic kernel.
 usage: python tools/wgrad_bench.py [scenes=4] [levels=3] [iters=20]"""
 import os
 import sys
@@ -12,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from d3net_amd import minkowski as ME, synthetic as S  # noqa: E402
 
-MODES = (("gen3", {"D3_WG3": 1, "D3_WG2_TR": 1}), ("gen2+tr", {"D3_WG3": 0, "D3_WG2_TR": 1}), ("gen2", {"D3_WG3": 0, "D3_WG2_TR": 0}))
+MODES = (("gen3", {"D3_WG3": 1}), ("gen2", {"D3_WG3": 0}))
 
 
 def set_mode(env):
@@ -78,9 +78,9 @@ def main():
             rel_b = float((wb() - res["gen3"]).abs().max() / (res["gen3"].abs().max() + 1e-20))
             alg = 2.0 * Min * Cin + 4.0 * Mout * Cout + 4.0 * K * Cin * Cout + 4.0 * (Min if Cin > Cout else Mout) * K
             ref = res["gen2"]
-            rel = [float((res[m] - ref).abs().max() / (ref.abs().max() + 1e-20)) for m in ("gen3", "gen2+tr")]
-            print("%-22s %8d %8.1f | %s | %8.0f   %.1e %.1e | dy bf16: %7.1f us (vs gen3 %.1e)" %
-                  (name, Mout, alg / 1e6, " ".join("%9.1f" % tms[m] for m, _ in MODES), alg / tms["gen3"] / 1e3, rel[0], rel[1], t_b, rel_b))
+            rel = float((res["gen3"] - ref).abs().max() / (ref.abs().max() + 1e-20))
+            print("%-22s %8d %8.1f | %s | %8.0f   %.1e | dy bf16: %7.1f us (vs gen3 %.1e)" %
+                  (name, Mout, alg / 1e6, " ".join("%9.1f" % tms[m] for m, _ in MODES), alg / tms["gen3"] / 1e3, rel, t_b, rel_b))
         ts *= 2
 
 
