@@ -60,10 +60,3 @@ int d3_sort_pairs_i32(const int *kin, int *kout, const int *vin, int *vout, int 
 size_t d3_sort_pairs_u64_temp_bytes(int n);
 int d3_sort_pairs_u64(const unsigned long long *kin, unsigned long long *kout, const int *vin, int *vout, int n, void *temp,
                       size_t temp_bytes, hipStream_t s);
-
-// internal (C++ linkage, spconv2.hip): the 16-bit delta form and / or the lane table (spconv3.hip) of the kernel map handed to the NEXT
-// d3_spconv_fwd2* / d3_spconv_wgrad2 call of this thread (consumed by that call; NULL: dense table only).  The caller has
-// VALIDATED the tables (d3_kmap_k3_pack16's / d3_kmap_k3_packq's flag read on the host).  csrc/unet.hip sets it per K = 27 launch.
-void d3_spconv_next_tbl16(const void *tbl16, const void *tblq);
-void d3_spconv_set_last_nparts(int n);         // spconv2.hip: what d3_spconv_last_nparts() (include/d3hip.h) returns next
-void d3_spconv_next_part2(double *part2);      // spconv2.hip: second-level BatchNorm partial table of this thread's next forward / data-gradient call

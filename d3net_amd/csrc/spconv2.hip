@@ -21,7 +21,7 @@
 //   * epilogue fusions: residual add, accumulate-into, strided output (writes straight into a concatenated
 //     buffer) and per-channel sum / sum-of-squares partials for the following BatchNorm.
 // Roofline: HBM; algorithmic bytes per launch as in spconv.hip.
-#include "common.h"
+#include "conv.h"
 #include "prof.h"
 #include <cstdlib>
 #include <cstring>
@@ -279,7 +279,7 @@ __device__ __forceinline__ void spconv_fwd2_body(const Conv2Args &a) {
     // 16-bit table (round 4): entries (2d, 2d + 1) of the tile travel as ONE 32-bit word d = lane + it * 64 < 8 K; v[0..3] hold the
     // raw words, the LDS store decodes them (row + delta; 0x8000 = absent).  K is odd: the word that straddles the end of the
     // table's last row reads one of the two pad entries behind it.
-    constexpr bool t16 = T16;                                  // (the host validated the table: d3_spconv_next_tbl16)
+    constexpr bool t16 = T16;                                  // (the host validated the table: ConvExtras, conv.h)
 #define C2_LOAD_TBL(TILE)                                                                                     \
     {                                                                                                         \
         const int tile_ = (TILE);                                                                             \
@@ -828,7 +828,6 @@ static Conv2Plan conv2_plan(int Mout, int K, int Cin, int Cout, bool f32 = false
     return p;
 }
 
-extern "C" int d3_spconv_fwd3_nparts(int Mout, int Cin, int Cout);
 // rows of the BatchNorm partial table a forward / data-gradient call may write: the larger of the two kernels that can serve the
 // shape (which one runs depends on the tables the call is handed); d3_spconv_last_nparts() says how many the call did write
 extern "C" int d3_spconv_fwd2_nparts(int Mout, int K, int Cin, int Cout) {
@@ -863,14 +862,13 @@ static bool c2_attr_needed(bool *done) {
 #include <atomic>
 static std::atomic<long long> g_t16_launches{0};       // launches that read a 16-bit kernel map (tests: the path really ran)
 extern "C" long long d3_spconv_t16_launches(void) { return g_t16_launches.load(); }
-// template arguments of the instance the last launch_fwd2* call of this thread ran: {NT, WLDS, XBF, NW, F32M, KT, ST} for
+// inst[7] (the caller's): template arguments of the instance a launch_fwd2* call runs: {NT, WLDS, XBF, NW, F32M, KT, ST} for
 // spconv_fwd2_kernel, {NTW, XBF, F32M} for spconv_fwd2_split_kernel -- the profiling record names the kernel as rocprofv3 prints it
-static thread_local int g_c2_inst[7];
-static inline void c2_inst(int a0, int a1, int a2, int a3, int a4, int a5, int a6) {
-    g_c2_inst[0] = a0; g_c2_inst[1] = a1; g_c2_inst[2] = a2; g_c2_inst[3] = a3; g_c2_inst[4] = a4; g_c2_inst[5] = a5; g_c2_inst[6] = a6;
+static inline void c2_inst(int *inst, int a0, int a1, int a2, int a3, int a4, int a5, int a6) {
+    inst[0] = a0; inst[1] = a1; inst[2] = a2; inst[3] = a3; inst[4] = a4; inst[5] = a5; inst[6] = a6;
 }
 template <int NT>
-static int launch_fwd2_f32(const Conv2Args &a, const Conv2Plan &p, hipStream_t s) {
+static int launch_fwd2_f32(const Conv2Args &a, const Conv2Plan &p, int *inst, hipStream_t s) {
     static bool attr_done_dev[64] = {false};
     if (c2_attr_needed(attr_done_dev)) {
         D3_CHECK(hipFuncSetAttribute((const void *)spconv_fwd2_kernel<NT, true, false, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
@@ -879,9 +877,9 @@ static int launch_fwd2_f32(const Conv2Args &a, const Conv2Plan &p, hipStream_t s
             D3_CHECK(hipFuncSetAttribute((const void *)spconv_fwd2_kernel<NT, true, false, 16, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     }
     if constexpr (NT <= C2_NW16_MAXNT) {
-        if (p.nw == 16) { c2_inst(NT, 1, 0, 16, 1, 0, 0); spconv_fwd2_kernel<NT, true, false, 16, true><<<p.grid, 1024, p.lds, s>>>(a); D3_LAUNCH_CHECK(); return 0; }
+        if (p.nw == 16) { c2_inst(inst, NT, 1, 0, 16, 1, 0, 0); spconv_fwd2_kernel<NT, true, false, 16, true><<<p.grid, 1024, p.lds, s>>>(a); D3_LAUNCH_CHECK(); return 0; }
     }
-    c2_inst(NT, p.wlds ? 1 : 0, 0, 4, 1, 0, 0);
+    c2_inst(inst, NT, p.wlds ? 1 : 0, 0, 4, 1, 0, 0);
     if (p.wlds) spconv_fwd2_kernel<NT, true, false, 4, true><<<p.grid, 256, p.lds, s>>>(a);
     else spconv_fwd2_kernel<NT, false, false, 4, true><<<p.grid, 256, p.lds, s>>>(a);
     D3_LAUNCH_CHECK();
@@ -889,7 +887,7 @@ static int launch_fwd2_f32(const Conv2Args &a, const Conv2Plan &p, hipStream_t s
 }
 // the statically shaped instances (K = 27, bf16 rows, weights in LDS)
 template <int NT, int NW, int ST>
-static int launch_fwd2_static(const Conv2Args &a, const Conv2Plan &p, hipStream_t s) {
+static int launch_fwd2_static(const Conv2Args &a, const Conv2Plan &p, int *inst, hipStream_t s) {
     static bool attr_done_dev[64] = {false};
     if (c2_attr_needed(attr_done_dev))
         D3_CHECK(hipFuncSetAttribute((const void *)spconv_fwd2_kernel<NT, true, true, NW, false, 27, ST>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
@@ -902,30 +900,30 @@ static int launch_fwd2_static(const Conv2Args &a, const Conv2Plan &p, hipStream_
             D3_CHECK(hipFuncSetAttribute((const void *)spconv_fwd2_c_kernel<NT, NW, ST, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
             D3_CHECK(hipFuncSetAttribute((const void *)spconv_fwd2_c_kernel<NT, NW, ST, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         }
-        c2_inst(NT, 1, 1, NW, 0, 27, ST + (a.tbl16 ? 1000 : 0) + 4000);     // (+ 4000: spconv_fwd2_c_kernel, see bench.py's kernel naming)
+        c2_inst(inst, NT, 1, 1, NW, 0, 27, ST + (a.tbl16 ? 1000 : 0) + 4000);     // (+ 4000: spconv_fwd2_c_kernel, see bench.py's kernel naming)
         if (a.tbl16) { spconv_fwd2_c_kernel<NT, NW, ST, true><<<p.grid, 64 * NW, p.lds, s>>>(a); g_t16_launches++; }
         else spconv_fwd2_c_kernel<NT, NW, ST, false><<<p.grid, 64 * NW, p.lds, s>>>(a);
         D3_LAUNCH_CHECK();
         return 0;
     }
-    c2_inst(NT, 1, 1, NW, 0, 27, ST);
+    c2_inst(inst, NT, 1, 1, NW, 0, 27, ST);
     spconv_fwd2_kernel<NT, true, true, NW, false, 27, ST><<<p.grid, 64 * NW, p.lds, s>>>(a);
     D3_LAUNCH_CHECK();
     return 0;
 }
 template <int NT>
-static int launch_fwd2(const Conv2Args &a, const Conv2Plan &p, hipStream_t s) {
-    if (a.f32) return launch_fwd2_f32<NT>(a, p, s);
+static int launch_fwd2(const Conv2Args &a, const Conv2Plan &p, int *inst, hipStream_t s) {
+    if (a.f32) return launch_fwd2_f32<NT>(a, p, inst, s);
     if (a.xbf16 && a.K == 27 && p.wlds) {
         if constexpr (NT == 1) {
-            if (a.S == 2 && p.nw == 4) return launch_fwd2_static<1, 4, 2>(a, p, s);      // 16 -> 16
-            if (a.S == 4 && p.nw == 16) return launch_fwd2_static<1, 16, 4>(a, p, s);    // 32 -> 16
-            if (a.S == 17 && p.nw == 16) return launch_fwd2_static<1, 16, 17>(a, p, s);  // the stem: 134 (+2) -> 16
+            if (a.S == 2 && p.nw == 4) return launch_fwd2_static<1, 4, 2>(a, p, inst, s);      // 16 -> 16
+            if (a.S == 4 && p.nw == 16) return launch_fwd2_static<1, 16, 4>(a, p, inst, s);    // 32 -> 16
+            if (a.S == 17 && p.nw == 16) return launch_fwd2_static<1, 16, 17>(a, p, inst, s);  // the stem: 134 (+2) -> 16
         }
         if constexpr (NT == 2) {
-            if (a.S == 2 && p.nw == 16) return launch_fwd2_static<2, 16, 2>(a, p, s);    // 16 -> 32
-            if (a.S == 4 && p.nw == 16) return launch_fwd2_static<2, 16, 4>(a, p, s);    // 32 -> 32
-            if (a.S == 8 && p.nw == 16) return launch_fwd2_static<2, 16, 8>(a, p, s);    // 64 -> 32
+            if (a.S == 2 && p.nw == 16) return launch_fwd2_static<2, 16, 2>(a, p, inst, s);    // 16 -> 32
+            if (a.S == 4 && p.nw == 16) return launch_fwd2_static<2, 16, 4>(a, p, inst, s);    // 32 -> 32
+            if (a.S == 8 && p.nw == 16) return launch_fwd2_static<2, 16, 8>(a, p, inst, s);    // 64 -> 32
         }
         // (48 -> 48 with the offset loop rolled: measured no faster than the generic instance -- 36 k rows are one tile per wave)
         // (32 -> 64 spills at 128 registers even with the rolled loop: generic instance)
@@ -944,14 +942,14 @@ static int launch_fwd2(const Conv2Args &a, const Conv2Plan &p, hipStream_t s) {
                 D3_CHECK(hipFuncSetAttribute((const void *)spconv_fwd2_kernel<NT, true, true, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
                 D3_CHECK(hipFuncSetAttribute((const void *)spconv_fwd2_kernel<NT, true, false, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
             }
-            c2_inst(NT, 1, a.xbf16 ? 1 : 0, 16, 0, 0, 0);
+            c2_inst(inst, NT, 1, a.xbf16 ? 1 : 0, 16, 0, 0, 0);
             if (a.xbf16) spconv_fwd2_kernel<NT, true, true, 16><<<p.grid, 1024, p.lds, s>>>(a);
             else spconv_fwd2_kernel<NT, true, false, 16><<<p.grid, 1024, p.lds, s>>>(a);
             D3_LAUNCH_CHECK();
             return 0;
         }
     }
-    c2_inst(NT, p.wlds ? 1 : 0, a.xbf16 ? 1 : 0, 4, 0, 0, 0);
+    c2_inst(inst, NT, p.wlds ? 1 : 0, a.xbf16 ? 1 : 0, 4, 0, 0, 0);
     if (a.xbf16) {
         if (p.wlds) spconv_fwd2_kernel<NT, true, true><<<p.grid, 256, p.lds, s>>>(a);
         else spconv_fwd2_kernel<NT, false, true><<<p.grid, 256, p.lds, s>>>(a);
@@ -963,13 +961,13 @@ static int launch_fwd2(const Conv2Args &a, const Conv2Plan &p, hipStream_t s) {
     return 0;
 }
 template <int NTW>
-static int launch_fwd2_split(const Conv2Args &a, const Conv2Plan &p, hipStream_t s) {
+static int launch_fwd2_split(const Conv2Args &a, const Conv2Plan &p, int *inst, hipStream_t s) {
     static bool attr_done_dev[64] = {false};
     if (c2_attr_needed(attr_done_dev)) {
         D3_CHECK(hipFuncSetAttribute((const void *)spconv_fwd2_split_kernel<NTW, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
         D3_CHECK(hipFuncSetAttribute((const void *)spconv_fwd2_split_kernel<NTW, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
     }
-    c2_inst(NTW, a.f32 ? 0 : (a.xbf16 ? 1 : 0), a.f32 ? 1 : 0, -1, 0, 0, 0);
+    c2_inst(inst, NTW, a.f32 ? 0 : (a.xbf16 ? 1 : 0), a.f32 ? 1 : 0, -1, 0, 0, 0);
     if (a.f32) {
         static bool attr32_done_dev[64] = {false};
         if (c2_attr_needed(attr32_done_dev))
@@ -982,31 +980,13 @@ static int launch_fwd2_split(const Conv2Args &a, const Conv2Plan &p, hipStream_t
     return 0;
 }
 
-static thread_local const void *g_next_tbl16 = nullptr;
-static thread_local const void *g_next_tblq = nullptr;
-void d3_spconv_next_tbl16(const void *tbl16, const void *tblq) { g_next_tbl16 = tbl16; g_next_tblq = tblq; }
-static thread_local int g_last_nparts = 0;
-extern "C" int d3_spconv_last_nparts(void) { return g_last_nparts; }
-void d3_spconv_set_last_nparts(int n) { g_last_nparts = n; }
-// spconv3.hip
-struct Conv3Bn { const void *x; const float *mean, *var, *gamma, *beta; int ldx, relu, xbf16; float eps; };
-int d3_conv3_run(const void *x, int ldx, const void *tq, const void *Wp, void *out, int ldo, const float *res, int ldr, float *part,
-                 double *part2, int Min, int Mout, int Cin, int Cout, int obf16, const Conv3Bn *bn, int *nparts_out, hipStream_t s);
-extern "C" int d3_spconv_fwd3_nparts(int Mout, int Cin, int Cout);
-// second-level partial table of the NEXT forward / data-gradient call of this thread (same hand-over as the 16-bit map hint):
-// [C2_P2_ROWS][2][ceil(Cout / 16) * 16] doubles, zeroed by the caller; ignored when the call takes no partials
-static thread_local double *g_next_part2 = nullptr;
-void d3_spconv_next_part2(double *part2) { g_next_part2 = part2; }
-
-struct Conv2Bn { const float *x, *mean, *var, *gamma, *beta; int ldx, relu; float eps; int xbf16; };
-
-static int conv2_run(const void *x, int ldx, const int *tbl, const void *Wp, float *out, int ldo, const float *res, int ldr,
-                     float *part, int Min, int Mout, int K, int Cin, int Cout, int flags, const Conv2Bn *bn, void *stream) {
+// internal forward / data-gradient entry (conv.h)
+int d3_conv2_run(const void *x, int ldx, const int *tbl, const void *Wp, float *out, int ldo, const float *res, int ldr, float *part,
+                 int Min, int Mout, int K, int Cin, int Cout, int flags, const ConvBn *bn, const ConvExtras &ex, int *nparts, void *stream) {
     D3_CLEAR();
-    const void *tbl16 = g_next_tbl16, *tblq = g_next_tblq;      // the hints belong to THIS call, whatever it does with them
-    g_next_tbl16 = nullptr; g_next_tblq = nullptr;
-    double *part2 = g_next_part2;
-    g_next_part2 = nullptr;
+    *nparts = 0;
+    const void *tbl16 = ex.tbl16, *tblq = ex.tblq;
+    double *part2 = ex.part2;
     if (Mout <= 0) return 0;
     if (K < 1 || K > C2_MAXK || Cin < 8 || (Cin & 7) || Cout < 1 || Cout > 224) return D3_ERR_ARG;
     if (tbl == nullptr && K != 1) return D3_ERR_ARG;
@@ -1019,12 +999,9 @@ static int conv2_run(const void *x, int ldx, const int *tbl, const void *Wp, flo
     // round 6: the big levels' K = 27 layers on the lane table (spconv3.hip) -- bf16 rows, no accumulate-into
     if (tblq && tbl && K == 27 && xbf16 && !f32 && !(flags & D3_CONV_ACCUM) && d3_tune(D3T_C3) != 0 &&
         Mout >= C2_GRIDCAP * 16 && d3_spconv_fwd3_nparts(Mout, Cin, Cout) > 0 && !(bn && res)) {
-        Conv3Bn b3;
-        if (bn) b3 = Conv3Bn{bn->x, bn->mean, bn->var, bn->gamma, bn->beta, bn->ldx, bn->relu, bn->xbf16, bn->eps};
-        int np = 0;
         const int rc3 = d3_conv3_run(x, ldx, tblq, Wp, out, ldo, res, ldr, part, part ? part2 : nullptr, Min, Mout, Cin, Cout,
-                                     (flags & D3_CONV_OUTBF16) ? 1 : 0, bn ? &b3 : nullptr, &np, s);
-        if (rc3 != D3_ERR_ARG) { g_last_nparts = np; return rc3; }
+                                     (flags & D3_CONV_OUTBF16) ? 1 : 0, bn, nparts, s);
+        if (rc3 != D3_ERR_ARG) return rc3;
     }
     Conv2Args a;
     a.x = x; a.tbl = tbl; a.Wp = (const unsigned short *)Wp; a.out = out; a.res = res; a.part = part;
@@ -1044,38 +1021,39 @@ static int conv2_run(const void *x, int ldx, const int *tbl, const void *Wp, flo
     a.bnx = nullptr; a.bn_mean = a.bn_var = a.bn_gamma = a.bn_beta = nullptr; a.ldbx = 0; a.bn_relu = 0; a.bn_eps = 0.f; a.bnx_bf16 = 0;
     if (bn) {
         if (bn->ldx & 3) return D3_ERR_ARG;
-        a.bnx = bn->x; a.bn_mean = bn->mean; a.bn_var = bn->var; a.bn_gamma = bn->gamma; a.bn_beta = bn->beta;
+        a.bnx = (const float *)bn->x; a.bn_mean = bn->mean; a.bn_var = bn->var; a.bn_gamma = bn->gamma; a.bn_beta = bn->beta;
         a.ldbx = bn->ldx; a.bn_relu = bn->relu; a.bn_eps = bn->eps; a.bnx_bf16 = bn->xbf16;
     }
     const Conv2Plan p = conv2_plan(Mout, K, Cin, Cout, f32 != 0);
-    g_last_nparts = p.grid;
+    *nparts = p.grid;
     if (!p.split && a.xbytes == 0u) return D3_ERR_RANGE;   // the wave-per-tile kernel addresses x through a raw buffer: <= 2 GiB, < 2^24 rows
     const double bytes = (xbf16 ? 2.0 : 4.0) * (double)Min * Cin + (a.obf16 ? 2.0 : 4.0) * (double)Mout * Cout + (f32 ? 4.0 : 2.0) * (double)K * Cin * Cout +
                          (tbl ? 4.0 * (double)Mout * K : 0.0) + (res ? 4.0 * (double)Mout * Cout : 0.0);
     void *pr = d3_prof_begin(p.split ? 2 : 0, bytes, 0.0, s);
+    int inst[7] = {0, 0, 0, 0, 0, 0, 0};      // filled by launch_fwd2*
     auto tag_rec = [&]() {
         if (!pr) return;
         const int dims[5] = {Min, Mout, K, Cin, Cout};
         for (int i = 0; i < 5; i++) d3_prof_tag(pr, i, dims[i]);
-        for (int i = 0; i < 7; i++) d3_prof_tag(pr, 5 + i, g_c2_inst[i]);
+        for (int i = 0; i < 7; i++) d3_prof_tag(pr, 5 + i, inst[i]);
     };
     int rc;
     a.NT = (Cout + 15) / 16;
     if (p.split) {
         switch (p.ntw) {
-            case 1: rc = launch_fwd2_split<1>(a, p, s); break;
-            case 2: rc = launch_fwd2_split<2>(a, p, s); break;
-            case 3: rc = launch_fwd2_split<3>(a, p, s); break;
-            case 4: rc = launch_fwd2_split<4>(a, p, s); break;
-            case 5: rc = launch_fwd2_split<5>(a, p, s); break;
-            case 6: rc = launch_fwd2_split<6>(a, p, s); break;
-            default: rc = launch_fwd2_split<7>(a, p, s); break;
+            case 1: rc = launch_fwd2_split<1>(a, p, inst, s); break;
+            case 2: rc = launch_fwd2_split<2>(a, p, inst, s); break;
+            case 3: rc = launch_fwd2_split<3>(a, p, inst, s); break;
+            case 4: rc = launch_fwd2_split<4>(a, p, inst, s); break;
+            case 5: rc = launch_fwd2_split<5>(a, p, inst, s); break;
+            case 6: rc = launch_fwd2_split<6>(a, p, inst, s); break;
+            default: rc = launch_fwd2_split<7>(a, p, inst, s); break;
         }
         tag_rec();
         d3_prof_end(pr, s);
         return rc;
     }
-#define C2_CASE(NTV) case NTV: rc = launch_fwd2<NTV>(a, p, s); break;
+#define C2_CASE(NTV) case NTV: rc = launch_fwd2<NTV>(a, p, inst, s); break;
     switch ((Cout + 15) / 16) {
         C2_CASE(1) C2_CASE(2) C2_CASE(3) C2_CASE(4) C2_CASE(5) C2_CASE(6) C2_CASE(7) C2_CASE(8) C2_CASE(9)
         C2_CASE(10) C2_CASE(11) C2_CASE(12) C2_CASE(13) C2_CASE(14)
@@ -1090,7 +1068,7 @@ static int conv2_run(const void *x, int ldx, const int *tbl, const void *Wp, flo
 extern "C" int d3_spconv_fwd2(const void *x, int ldx, const int *tbl, const void *Wp, float *out, int ldo,
                               const float *res, int ldr, float *part, int Min, int Mout, int K, int Cin, int Cout,
                               int flags, void *stream) {
-    return conv2_run(x, ldx, tbl, Wp, out, ldo, res, ldr, part, Min, Mout, K, Cin, Cout, flags, nullptr, stream);
+    return d3_conv2_run(x, ldx, tbl, Wp, out, ldo, res, ldr, part, Min, Mout, K, Cin, Cout, flags, nullptr, ConvExtras{}, &d3_conv_last_nparts, stream);
 }
 
 // Data gradient of a BatchNorm -> ReLU -> convolution unit with the BatchNorm backward reductions fused in: the stored
@@ -1101,8 +1079,8 @@ extern "C" int d3_spconv_fwd2_bnbwd(const void *x, int ldx, const int *tbl, cons
                                     const float *bnx, int ldbx, const float *mean, const float *var, const float *gamma,
                                     const float *beta, float eps, int relu, int Min, int Mout, int K, int Cin, int Cout,
                                     int flags, void *stream) {
-    Conv2Bn bn{bnx, mean, var, gamma, beta, ldbx, relu, eps, (flags & D3_CONV_BNXBF16) ? 1 : 0};
-    return conv2_run(x, ldx, tbl, Wp, out, ldo, nullptr, 0, part, Min, Mout, K, Cin, Cout, flags, &bn, stream);
+    ConvBn bn{bnx, mean, var, gamma, beta, ldbx, relu, (flags & D3_CONV_BNXBF16) ? 1 : 0, eps};
+    return d3_conv2_run(x, ldx, tbl, Wp, out, ldo, nullptr, 0, part, Min, Mout, K, Cin, Cout, flags, &bn, ConvExtras{}, &d3_conv_last_nparts, stream);
 }
 
 // ------------------------------------------------------------------------------ weight gradient
@@ -1493,7 +1471,7 @@ struct Wg3Args {
     int Ms, Cs8, cpw, flipk, Cin, Cout, K;
     unsigned int invs;                     // ceil(65536 / Cs8)
     int rss, dss, imgs;                    // stationary image (wg2_img)
-    const void *tbl16; const int *ok16; unsigned int t16bytes;   // optional 16-bit delta form of tbl (KV = 27; see spconv_fwd2_kernel)
+    const void *tbl16; unsigned int t16bytes;   // optional 16-bit delta form of tbl (KV = 27; see spconv_fwd2_kernel)
 };
 
 typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
@@ -1995,12 +1973,10 @@ static int launch_wg2(const Wg2Args &a, const Wg2Plan &p, hipStream_t s) {
 // (the forward map, or with D3_CONV_XSTAT the transposed map); dW (K,CinW,Cout) fp32 (CinW <= Cin: x may carry
 // zero-padded channels), written (or accumulated into
 // with D3_CONV_ACCUM).  ws >= d3_spconv_wgrad2_ws_bytes().  Cin % 8 == 0 and Cout % 8 == 0, else D3_ERR_ARG.
-extern "C" int d3_spconv_wgrad2(const void *x, int ldx, const int *tbl, const void *dy, int ldy, float *dW, int Min,
-                                int Mout, int K, int Cin, int Cout, int CinW, int flags, void *ws, size_t ws_bytes,
-                                void *stream) {
+// tbl16 (internal entry, conv.h): the validated 16-bit delta form of tbl, or NULL
+int d3_conv2_wgrad(const void *x, int ldx, const int *tbl, const void *tbl16, const void *dy, int ldy, float *dW, int Min, int Mout,
+                   int K, int Cin, int Cout, int CinW, int flags, void *ws, size_t ws_bytes, void *stream) {
     D3_CLEAR();
-    const void *tbl16 = g_next_tbl16; const int *ok16 = nullptr;      // (the hint of d3_spconv_next_tbl16 belongs to this call)
-    g_next_tbl16 = nullptr; g_next_tblq = nullptr;
     if (K < 1 || K > C2_MAXK || Cin < 8 || Cout < 8 || (Cin & 7) || (Cout & 7) || Cin > 224 || Cout > 224) return D3_ERR_ARG;
     if (tbl == nullptr && K != 1) return D3_ERR_ARG;
     hipStream_t s = d3_stream(stream);
@@ -2060,7 +2036,7 @@ extern "C" int d3_spconv_wgrad2(const void *x, int ldx, const int *tbl, const vo
         Wg3Args b;
         b.G = a.G; b.Sm = a.Sm; b.tbl = tbl; b.dst = (float *)ws;
         b.gbytes = (unsigned int)gb; b.sbytes = (unsigned int)sb; b.tbytes = (unsigned int)((long long)Ms * K * 4);
-        b.tbl16 = (tbl16 && K == 27) ? tbl16 : nullptr; b.ok16 = ok16; b.t16bytes = (unsigned int)((long long)Ms * K * 2);
+        b.tbl16 = (tbl16 && K == 27) ? tbl16 : nullptr; b.t16bytes = (unsigned int)((long long)Ms * K * 2);
         if (b.tbl16) g_t16_launches++;
         b.growb = a.ldg * (a.gbf16 ? 2 : 4); b.srowb = a.lds * (a.sbf16 ? 2 : 4);
         b.Ms = Ms; b.Cs8 = Cs / 8; b.cpw = p.cpw; b.flipk = a.flipk; b.Cin = CinW; b.Cout = Cout; b.K = K;
@@ -2114,4 +2090,9 @@ extern "C" int d3_spconv_wgrad2(const void *x, int ldx, const int *tbl, const vo
     }
     d3_prof_end(pr, s);
     return rc;
+}
+extern "C" int d3_spconv_wgrad2(const void *x, int ldx, const int *tbl, const void *dy, int ldy, float *dW, int Min,
+                                int Mout, int K, int Cin, int Cout, int CinW, int flags, void *ws, size_t ws_bytes,
+                                void *stream) {
+    return d3_conv2_wgrad(x, ldx, tbl, nullptr, dy, ldy, dW, Min, Mout, K, Cin, Cout, CinW, flags, ws, ws_bytes, stream);
 }

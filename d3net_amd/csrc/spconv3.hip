@@ -27,7 +27,7 @@
 // Per 16-row tile of a 16 -> 16 layer: 1 table load, 7 decodes (2 VALU), 14 gathers, 14 LDS reads, 14 MFMAs + the epilogue --
 // ~95 instructions against 388.
 // Roofline: HBM: 2 (Nin Cin + Nout Cout) + 2 K Cin Cout + 8 P bytes per launch.
-#include "common.h"
+#include "conv.h"
 #include "prof.h"
 #include <atomic>
 
@@ -373,7 +373,7 @@ static Conv3Plan conv3_plan(int Mout, int Cin, int Cout) {
 }
 
 // upper bound of the partial rows a launch writes (0: no instance for the shape); the launch itself may use fewer workgroups
-// (d3_spconv_fwd3_last_nparts)
+// (d3_spconv_last_nparts)
 extern "C" int d3_spconv_fwd3_nparts(int Mout, int Cin, int Cout) {
     const Conv3Plan p = conv3_plan(Mout, Cin, Cout);
     return p.ok ? p.maxgrid : 0;
@@ -414,11 +414,10 @@ static int c3_launch_shape(const Conv3Args &a, const Conv3Plan &p, int epi, bool
     return bxbf ? c3_launch_inst<ST, NT, C3_EPI_BNBWD, false, true, NW, QC>(a, p, grid_out, s) : c3_launch_inst<ST, NT, C3_EPI_BNBWD, false, false, NW, QC>(a, p, grid_out, s);
 }
 
-struct Conv3Bn { const void *x; const float *mean, *var, *gamma, *beta; int ldx, relu, xbf16; float eps; };
-
-// internal entry (spconv2.hip's dispatcher and the C ABI below).  Returns D3_ERR_ARG for shapes without an instance.
+// internal entry (conv.h: spconv2.hip's dispatcher and the C ABI below).  Returns D3_ERR_ARG for shapes without an instance.
 int d3_conv3_run(const void *x, int ldx, const void *tq, const void *Wp, void *out, int ldo, const float *res, int ldr, float *part,
-                 double *part2, int Min, int Mout, int Cin, int Cout, int obf16, const Conv3Bn *bn, int *nparts_out, hipStream_t s) {
+                 double *part2, int Min, int Mout, int Cin, int Cout, int obf16, const ConvBn *bn, int *nparts, hipStream_t s) {
+    *nparts = 0;
     const Conv3Plan p = conv3_plan(Mout, Cin, Cout);
     if (!p.ok || !x || !tq || !Wp || !out) return D3_ERR_ARG;
     if ((ldx & 7) || ldx < Cin || ldo < Cout || (ldo & 3) || (res && (ldr & 3)) || (res && bn) || (res && obf16)) return D3_ERR_ARG;
@@ -441,7 +440,7 @@ int d3_conv3_run(const void *x, int ldx, const void *tq, const void *Wp, void *o
 #define C3_CASE(STV, NTV, NWV, QCV) if (rc == D3_ERR_ARG && ST == STV && NT == NTV && p.nw == NWV && p.qc == QCV) rc = c3_launch_shape<STV, NTV, NWV, QCV>(a, p, epi, obf, bxbf, &grid, s);
     C3_SHAPES(C3_CASE)
 #undef C3_CASE
-    if (nparts_out) *nparts_out = grid;
+    *nparts = grid;
     if (pr) {
         const int dims[12] = {Min, Mout, 27, Cin, Cout, NT, epi, (obf ? 1 : 0) | (bxbf ? 2 : 0), p.nw, p.qc, 27, ST + 8000};      // (+ 8000: spconv_fwd3_kernel; EPI / OBF | BXBF << 1 / QC in the
                                                                                                                                //  WLDS / XBF / F32M slots: bench.py's kernel naming)
@@ -451,6 +450,9 @@ int d3_conv3_run(const void *x, int ldx, const void *tq, const void *Wp, void *o
     return rc;
 }
 
+thread_local int d3_conv_last_nparts = 0;
+extern "C" int d3_spconv_last_nparts(void) { return d3_conv_last_nparts; }
+
 // C ABI (tests, tools): one K = 27 forward / data-gradient launch on the lane table.
 //   flags: D3_CONV_OUTBF16 (out is bf16; not with a residual); x is bf16 always.
 //   part (optional): [d3_spconv_fwd3_nparts()][2][Cout] fp32 partial sums / sums of squares; part2 (optional, zeroed by the caller):
@@ -458,10 +460,9 @@ int d3_conv3_run(const void *x, int ldx, const void *tq, const void *Wp, void *o
 extern "C" int d3_spconv_fwd3(const void *x, int ldx, const void *tq, const void *Wp, void *out, int ldo, const float *res, int ldr,
                               float *part, double *part2, int Min, int Mout, int Cin, int Cout, int flags, void *stream) {
     D3_CLEAR();
-    if (Mout <= 0) return 0;
     int np = 0;
-    const int rc = d3_conv3_run(x, ldx, tq, Wp, out, ldo, res, ldr, part, part2, Min, Mout, Cin, Cout, (flags & D3_CONV_OUTBF16) ? 1 : 0, nullptr, &np, d3_stream(stream));
-    d3_spconv_set_last_nparts(np);
+    const int rc = Mout <= 0 ? 0 : d3_conv3_run(x, ldx, tq, Wp, out, ldo, res, ldr, part, part2, Min, Mout, Cin, Cout, (flags & D3_CONV_OUTBF16) ? 1 : 0, nullptr, &np, d3_stream(stream));
+    d3_conv_last_nparts = np;
     return rc;
 }
 // data gradient of a BatchNorm -> ReLU -> convolution unit (as d3_spconv_fwd2_bnbwd); bnx: the BatchNorm input, fp32, or bf16 with
@@ -470,10 +471,9 @@ extern "C" int d3_spconv_fwd3_bnbwd(const void *x, int ldx, const void *tq, cons
                                     const void *bnx, int ldbx, const float *mean, const float *var, const float *gamma, const float *beta,
                                     float eps, int relu, int Min, int Mout, int Cin, int Cout, int flags, void *stream) {
     D3_CLEAR();
-    if (Mout <= 0) return 0;
-    Conv3Bn bn{bnx, mean, var, gamma, beta, ldbx, relu, (flags & D3_CONV_BNXBF16) ? 1 : 0, eps};
+    ConvBn bn{bnx, mean, var, gamma, beta, ldbx, relu, (flags & D3_CONV_BNXBF16) ? 1 : 0, eps};
     int np = 0;
-    const int rc = d3_conv3_run(x, ldx, tq, Wp, out, ldo, nullptr, 0, part, part2, Min, Mout, Cin, Cout, (flags & D3_CONV_OUTBF16) ? 1 : 0, &bn, &np, d3_stream(stream));
-    d3_spconv_set_last_nparts(np);
+    const int rc = Mout <= 0 ? 0 : d3_conv3_run(x, ldx, tq, Wp, out, ldo, nullptr, 0, part, part2, Min, Mout, Cin, Cout, (flags & D3_CONV_OUTBF16) ? 1 : 0, &bn, &np, d3_stream(stream));
+    d3_conv_last_nparts = np;
     return rc;
 }

@@ -19,8 +19,8 @@
 //   * REFERENCE PRECISION: a program whose buffers are all fp32 (netexec.py builds it for minkowski.set_exact(True)) runs the
 //     same schedule with fp32 activations / gradients, fp32 weight fragments and the D3_CONV_F32 kernels of spconv2.hip
 //     (exact fp32 products on v_mfma_f32_16x16x4_f32) -- MinkowskiEngine's own precision (model/common.py:32-41).
-// Kernels used: spconv2.hip (d3_spconv_fwd2 / d3_spconv_wgrad2) and the strided BatchNorm kernels below.
-#include "common.h"
+// Kernels used: spconv2.hip (d3_conv2_run / d3_conv2_wgrad, conv.h) and the strided BatchNorm kernels below.
+#include "conv.h"
 #include <vector>
 #include <map>
 #include <string.h>
@@ -702,7 +702,7 @@ struct Net {
     int xp_tensor = -1;                // the PADCAST op's output tensor (the stem's zero-padded bf16 input), -1: none
     const void *xp_ext = nullptr;      // its values prepared by the caller (d3_net_padcast) for the next forward / backward call, or NULL
     std::vector<const void *> k3_16;   // per level: 16-bit delta form of the k3 table for the next forward / backward call (or NULL)
-    std::vector<const void *> ok16;    // per level: the lane table (spconv3.hip) for the next forward / backward call (or NULL)
+    std::vector<const void *> k3_q;    // per level: the lane table (spconv3.hip) for the next forward / backward call (or NULL)
     std::vector<int> chunk_op;
     std::vector<hipEvent_t> chunk_ev_side, chunk_ev_main;
     RedJob *red_host = nullptr, *red_dev = nullptr;   // pinned staging (ring of RED_RING slots) + device copies of the reduce jobs
@@ -714,18 +714,6 @@ struct Net {
 };
 
 static int esize(int dtype) { return dtype == 1 ? 2 : 4; }
-
-extern "C" int d3_spconv_fwd2_nparts(int Mout, int K, int Cin, int Cout);
-extern "C" int d3_spconv_fwd2(const void *x, int ldx, const int *tbl, const void *Wp, float *out, int ldo, const float *res,
-                              int ldr, float *part, int Min, int Mout, int K, int Cin, int Cout, int flags, void *stream);
-extern "C" int d3_spconv_fwd2_bnbwd(const void *x, int ldx, const int *tbl, const void *Wp, float *out, int ldo, float *part,
-                                    const float *bnx, int ldbx, const float *mean, const float *var, const float *gamma,
-                                    const float *beta, float eps, int relu, int Min, int Mout, int K, int Cin, int Cout,
-                                    int flags, void *stream);
-extern "C" size_t d3_spconv_wgrad2_ws_bytes(int Min, int Mout, int K, int Cin, int Cout, int flags);
-extern "C" int d3_spconv_wgrad2_splits(int Min, int Mout, int K, int Cin, int Cout, int flags);
-extern "C" int d3_spconv_wgrad2(const void *x, int ldx, const int *tbl, const void *dy, int ldy, float *dW, int Min, int Mout,
-                                int K, int Cin, int Cout, int CinW, int flags, void *ws, size_t ws_bytes, void *stream);
 
 // prog: nops x 16 int64, tensors: nt x 6, bufs: nb x 3 (see d3net_amd/netexec.py, which builds them)
 extern "C" void *d3_net_create(const int64_t *prog, int nops, const int64_t *tensors, int ntensors, const int64_t *bufs,
@@ -997,11 +985,11 @@ extern "C" int d3_net_set_k3_16(void *h, const void *const *k3_16, const int *co
     Net *n = (Net *)h;
     if (!n) return D3_ERR_ARG;
     n->k3_16.assign((size_t)n->nlevels, nullptr);
-    n->ok16.assign((size_t)n->nlevels, nullptr);
+    n->k3_q.assign((size_t)n->nlevels, nullptr);
     if (d3_tune(D3T_KMAP16) != 0 && !n->f32)
         for (int l = 0; l < n->nlevels; l++) {
             if (k3_16 && k3_16[l]) n->k3_16[(size_t)l] = k3_16[l];
-            if (ok16 && ok16[l]) n->ok16[(size_t)l] = (const void *)ok16[l];      // (second array: the lane tables, round 6)
+            if (ok16 && ok16[l]) n->k3_q[(size_t)l] = (const void *)ok16[l];      // (second array: the lane tables, round 6)
         }
     return 0;
 }
@@ -1148,12 +1136,9 @@ static inline char *tptr(const Net *n, char *arena, const void *input, int tenso
 
 // The 16-bit tables handed over by d3_net_set_k3_16 serve exactly ONE forward or backward call (a caller that freed
 // its coordinate manager and ran again without re-setting them read freed tables): every return path of the two entry points
-// drops them, and the thread-local hint of d3_spconv_next_tbl16 with them (an error return taken between setting the hint and
-// the convolution that consumes it must not hand the table to an unrelated K = 27 convolution on this thread).
+// drops them.
 static void net_drop_k3_16(Net *n) {
-    if (n) { n->k3_16.assign(n->k3_16.size(), nullptr); n->ok16.assign(n->ok16.size(), nullptr); n->xp_ext = nullptr; }
-    d3_spconv_next_tbl16(nullptr, nullptr);
-    d3_spconv_next_part2(nullptr);
+    if (n) { n->k3_16.assign(n->k3_16.size(), nullptr); n->k3_q.assign(n->k3_q.size(), nullptr); n->xp_ext = nullptr; }
 }
 static int net_forward_impl(void *h, const void *const *params, const int *const *k3, const int *const *child,
                             const int *const *up, const void *input, void *arena_, int training, void *stream);
@@ -1241,14 +1226,18 @@ static int net_forward_impl(void *h, const void *const *params, const int *const
             const float *res = nullptr; int ldr = 0;
             if (o.res >= 0) { res = (const float *)tptr(n, arena, input, o.res); ldr = n->T[o.res].ld; }
             float *part = (o.stats && training) ? (float *)(arena + o.part_off) : nullptr;
-            if (o.map == MAP_K3 && (size_t)o.mlevel < n->k3_16.size() && (n->k3_16[(size_t)o.mlevel] || n->ok16[(size_t)o.mlevel]))
-                d3_spconv_next_tbl16(n->k3_16[(size_t)o.mlevel], use_p2 || !part ? n->ok16[(size_t)o.mlevel] : nullptr);
-            if (part && use_p2) d3_spconv_next_part2((double *)(arena + o.part2_off));
-            int rc;
-            rc = d3_spconv_fwd2(tptr(n, arena, input, o.in), ti.ld, tf, arena + o.wp_fwd, (float *)tptr(n, arena, input, o.out), to.ld,
-                                res, ldr, part, Min, Mout, o.K, o.Cin, o.Cout, (ti.dtype == 1 ? D3_CONV_XBF16 : 0) | (n->f32 ? D3_CONV_F32 : 0) | (to.dtype == 1 ? D3_CONV_OUTBF16 : 0), stream);
+            ConvExtras ex;
+            if (o.map == MAP_K3 && (size_t)o.mlevel < n->k3_16.size()) {
+                ex.tbl16 = n->k3_16[(size_t)o.mlevel];
+                if (use_p2 || !part) ex.tblq = n->k3_q[(size_t)o.mlevel];
+            }
+            if (part && use_p2) ex.part2 = (double *)(arena + o.part2_off);
+            int np = 0;
+            const int rc = d3_conv2_run(tptr(n, arena, input, o.in), ti.ld, tf, arena + o.wp_fwd, (float *)tptr(n, arena, input, o.out), to.ld,
+                                        res, ldr, part, Min, Mout, o.K, o.Cin, o.Cout, (ti.dtype == 1 ? D3_CONV_XBF16 : 0) | (n->f32 ? D3_CONV_F32 : 0) | (to.dtype == 1 ? D3_CONV_OUTBF16 : 0),
+                                        nullptr, ex, &np, stream);
             if (rc) return rc;
-            if (part) o.nparts = d3_spconv_last_nparts();      // (rows actually written: the kernel depends on the tables at hand)
+            if (part) o.nparts = np;      // (rows actually written: the kernel depends on the tables at hand)
         } else if (o.type == OP_BNACT) {
             const TensorD &ti = n->T[o.in], &to = n->T[o.out];
             const int M = n->rows[ti.level], C = ti.C;
@@ -1450,21 +1439,24 @@ static int net_backward_impl(void *h, const void *const *params, const int *cons
                 int ldgi, root_i, gibf; float *gi = gptr(n, garena, gout, gin, o.in, ldgi, root_i, &gibf);
                 const int obf = gibf ? D3_CONV_OUTBF16 : 0;
                 if (root_i >= 0) wait_pending(root_i);
-                const bool t16 = o.map == MAP_K3 && (size_t)o.mlevel < n->k3_16.size() && (n->k3_16[(size_t)o.mlevel] || n->ok16[(size_t)o.mlevel]);
-                if (t16) d3_spconv_next_tbl16(n->k3_16[(size_t)o.mlevel], (use_p2 || o.bn_of_in < 0) ? n->ok16[(size_t)o.mlevel] : nullptr);
-                int rc;
+                ConvExtras ex;
+                if (o.map == MAP_K3 && (size_t)o.mlevel < n->k3_16.size()) {
+                    ex.tbl16 = n->k3_16[(size_t)o.mlevel];
+                    if (use_p2 || o.bn_of_in < 0) ex.tblq = n->k3_q[(size_t)o.mlevel];
+                }
+                int rc, np = 0;
                 if (o.bn_of_in >= 0) {
                     const OpD &b = n->ops[o.bn_of_in];
                     const TensorD &tx = n->T[b.in];
                     float *mean = (float *)(arena + b.state_off), *var = mean + tx.C;
-                    if (use_p2) d3_spconv_next_part2((double *)(garena + b.bpart2_off));
-                    rc = d3_spconv_fwd2_bnbwd(go, ldgo, tb, arena + o.wp_bwd, gi, ldgi, (float *)(garena + b.bpart_off),
-                                              (const float *)tptr(n, arena, input, b.in), tx.ld, mean, var, (const float *)params[b.gamma],
-                                              (const float *)params[b.beta], b.eps, b.relu, Mout, Min, o.K, o.Cout, o.CinW, (gobf ? D3_CONV_XBF16 : 0) | (n->f32 ? D3_CONV_F32 : 0) | obf | (tx.dtype == 1 ? D3_CONV_BNXBF16 : 0), stream);
-                    if (!rc) n->ops[o.bn_of_in].bparts = d3_spconv_last_nparts();
+                    if (use_p2) ex.part2 = (double *)(garena + b.bpart2_off);
+                    const ConvBn bn{tptr(n, arena, input, b.in), mean, var, (const float *)params[b.gamma], (const float *)params[b.beta], tx.ld, b.relu, tx.dtype == 1 ? 1 : 0, b.eps};
+                    rc = d3_conv2_run(go, ldgo, tb, arena + o.wp_bwd, gi, ldgi, nullptr, 0, (float *)(garena + b.bpart_off), Mout, Min, o.K, o.Cout, o.CinW,
+                                      (gobf ? D3_CONV_XBF16 : 0) | (n->f32 ? D3_CONV_F32 : 0) | obf, &bn, ex, &np, stream);
+                    if (!rc) n->ops[o.bn_of_in].bparts = np;
                 } else {
-                    rc = d3_spconv_fwd2(go, ldgo, tb, arena + o.wp_bwd, gi, ldgi, nullptr, 0, nullptr, Mout, Min, o.K, o.Cout, o.CinW,
-                                        (o.in_grad_mode == 2 ? D3_CONV_ACCUM : 0) | (gobf ? D3_CONV_XBF16 : 0) | (n->f32 ? D3_CONV_F32 : 0) | obf, stream);
+                    rc = d3_conv2_run(go, ldgo, tb, arena + o.wp_bwd, gi, ldgi, nullptr, 0, nullptr, Mout, Min, o.K, o.Cout, o.CinW,
+                                      (o.in_grad_mode == 2 ? D3_CONV_ACCUM : 0) | (gobf ? D3_CONV_XBF16 : 0) | (n->f32 ? D3_CONV_F32 : 0) | obf, nullptr, ex, &np, stream);
                 }
                 if (rc) return rc;
             }
@@ -1493,10 +1485,9 @@ static int net_backward_impl(void *h, const void *const *params, const int *cons
                 float *dW = pgrads[o.w];
                 // (the stem's x carries zero-padded channels: dW has CinW rows per offset)
                 char *wpart = garena + o.wpart_off;
-                if (o.map == MAP_K3 && (size_t)o.mlevel < n->k3_16.size() && n->k3_16[(size_t)o.mlevel])
-                    d3_spconv_next_tbl16(n->k3_16[(size_t)o.mlevel], nullptr);
-                int rc = d3_spconv_wgrad2(tptr(n, arena, input, o.in), ti.ld, tw, go, ldgo, dW, Min, Mout, o.K, o.Cin, o.Cout, o.CinW,
-                                          flags | D3_CONV_NOREDUCE, wpart, o.wpart_bytes, (void *)(op_side ? wst : s));
+                const void *tw16 = (o.map == MAP_K3 && (size_t)o.mlevel < n->k3_16.size()) ? n->k3_16[(size_t)o.mlevel] : nullptr;
+                int rc = d3_conv2_wgrad(tptr(n, arena, input, o.in), ti.ld, tw, tw16, go, ldgo, dW, Min, Mout, o.K, o.Cin, o.Cout, o.CinW,
+                                        flags | D3_CONV_NOREDUCE, wpart, o.wpart_bytes, (void *)(op_side ? wst : s));
                 if (o.wsplits > 1 || paccum[o.w] || n->f32) {   // (a single bf16-path split without accumulation was written to dW directly)
                     RedJob j;
                     memset(&j, 0, sizeof(j));

@@ -295,7 +295,8 @@ int d3_spconv_pack(const float *W, void *Wp, int K, int Cin, int Cout, int flags
 int d3_spconv_fwd2_nparts(int Mout, int K, int Cin, int Cout);
 int d3_spconv_fwd2_nparts_ex(int Mout, int K, int Cin, int Cout, int flags);   /* flags & D3_CONV_F32: that call's partial rows */
 /* both are UPPER BOUNDS since round 6 (the kernel that serves a K = 27 shape depends on the tables the call is handed);
- * d3_spconv_last_nparts(): the partial rows the last d3_spconv_fwd2* / d3_spconv_fwd3* call of this thread wrote */
+ * d3_spconv_last_nparts(): the partial rows the last d3_spconv_fwd2* / d3_spconv_fwd3* call of this thread through THIS interface
+ * wrote (0 after a call with Mout <= 0 or one that failed before its launch); the U-Net executor's own convolutions do not touch it */
 int d3_spconv_last_nparts(void);
 /* which kernel fwd2 runs for a shape (tests assert the variant they mean to cover): out[6] = {split (1 = the few-row
  * spconv_fwd2_split_kernel, 0 = the persistent wave-per-tile spconv_fwd2_kernel), waves per workgroup, grid.x,

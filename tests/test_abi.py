@@ -60,6 +60,16 @@ def test_product_never_imports_oracle():
     assert not bad, bad
 
 
+def test_convolutions_hand_nothing_over_through_globals():
+    """the convolution dispatchers and the U-Net executor pass tables and partial-row counts as arguments (csrc/conv.h): no
+    thread-local hint, no second copy of the BatchNorm argument struct"""
+    csrc = os.path.join(ROOT, "d3net_amd", "csrc")
+    banned = ("d3_spconv_next_", "d3_spconv_set_last_nparts", "g_c2_inst", "struct Conv3Bn", "struct Conv2Bn")
+    bad = [(f, w) for f in sorted(os.listdir(csrc)) for w in banned if w in open(os.path.join(csrc, f), errors="ignore").read()]
+    assert not bad, bad
+    assert "thread_local" not in open(os.path.join(csrc, "spconv2.hip")).read()
+
+
 def test_switch_table_stays_small(built_lib):
     """the library's measurement / cross-check switches live in ONE table (csrc/tuning.hip): at most 12, every name unique"""
     from d3net_amd import _lib

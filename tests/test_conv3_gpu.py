@@ -262,3 +262,32 @@ def test_fwd3_ragged_tail_and_empty(dev):
     assert bool((out[M:] == 5.0).all()), "rows beyond Mout were written"
     assert L.d3_spconv_fwd3(_ptr(x.to(dev)), 16, _ptr(tq), _ptr(wp), _ptr(out), 16, None, 0, None, None, M, 0, 16, 16, 0, _stream()) == 0
     assert L.d3_spconv_fwd3(_ptr(x.to(dev)), 16, _ptr(tq), _ptr(wp), _ptr(out), 16, None, 0, None, None, M, M, 24, 16, 0, _stream()) == -3   # no instance: D3_ERR_ARG
+
+
+def test_last_nparts_is_zero_after_an_empty_call(dev):
+    """d3_spconv_last_nparts() reports THIS thread's last C-ABI convolution: the grid of d3_spconv_fwd2_plan after a call that took
+    partials, and 0 after a call with Mout = 0 (an empty level must not inherit the count of an earlier, unrelated convolution)"""
+    from d3net_amd import _lib
+    from d3net_amd.pointgroup_ops import _ptr, _stream
+    L = _lib.lib()
+    M, c = 64, 16
+    rng = np.random.default_rng(6)
+    x = torch.from_numpy(rng.standard_normal((M, c)).astype(np.float32)).to(dev)
+    wp = _pack(L, torch.from_numpy(rng.standard_normal((1, c, c)).astype(np.float32)).to(dev), 0, dev)
+    out = torch.zeros((M, c), device=dev)
+    part = torch.zeros((L.d3_spconv_fwd2_nparts(M, 1, c, c), 2, c), device=dev)
+    plan = (C.c_int * 6)()
+    assert L.d3_spconv_fwd2_plan(M, 1, c, c, plan) == 0 and plan[2] > 0
+
+    def fwd2(mout):
+        return L.d3_spconv_fwd2(_ptr(x), c, None, _ptr(wp), _ptr(out), c, None, 0, _ptr(part), M, mout, 1, c, c, 0, _stream())
+
+    assert fwd2(M) == 0
+    assert L.d3_spconv_last_nparts() == plan[2]
+    assert fwd2(0) == 0
+    assert L.d3_spconv_last_nparts() == 0
+    assert fwd2(M) == 0 and L.d3_spconv_last_nparts() == plan[2]
+    xb = x.bfloat16()
+    assert L.d3_spconv_fwd3(_ptr(xb), c, _ptr(wp), _ptr(wp), _ptr(out), c, None, 0, _ptr(part), None, M, 0, c, c, 0, _stream()) == 0
+    assert L.d3_spconv_last_nparts() == 0
+    torch.cuda.synchronize()
