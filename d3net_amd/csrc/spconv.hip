@@ -16,11 +16,10 @@
 // scatter, no atomics, deterministic.  Offsets no row of the tile uses are skipped.
 // Roofline: HBM.  Algorithmic bytes per launch = 4*(Min*Cin + Mout*Cout) + 4*K*Cin*Cout + 4*Mout*K
 // (features once, weights once, table once); FLOPs = 2*pairs*Cin*Cout, AI 8..56 FLOP/B << 300.
-#include "common.h"
+#include "conv.h"
 #include "prof.h"
 
 typedef short bf16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ unsigned short f2bf(float f) {  // round to nearest even
     unsigned int u = __float_as_uint(f);

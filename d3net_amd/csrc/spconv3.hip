@@ -31,18 +31,6 @@
 #include "prof.h"
 #include <atomic>
 
-typedef __bf16 c3_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 c3_bf16x2 __attribute__((ext_vector_type(2)));
-typedef float c3_f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int c3_u32x4 __attribute__((ext_vector_type(4)));
-
-#define C3_RSRC_FLAGS 0x00020000          // raw buffer, 32-bit data format (gfx90a / gfx94x / gfx950)
-#define C3_P2_ROWS 16                     // rows of the second-level fp64 BatchNorm partial table (= C2_P2_ROWS / UN_P2_ROWS)
-
-__device__ __forceinline__ unsigned int c3_pack2(float lo, float hi) {   // v_cvt_pk_bf16_f32: round to nearest even
-    const c3_bf16x2 p = {(__bf16)lo, (__bf16)hi};
-    return __builtin_bit_cast(unsigned int, p);
-}
 __device__ __forceinline__ float c3_bf_lo(unsigned int w) { return __uint_as_float(w << 16); }
 __device__ __forceinline__ float c3_bf_hi(unsigned int w) { return __uint_as_float(w & 0xFFFF0000u); }
 
@@ -129,7 +117,7 @@ struct Conv3Args {
     void *out;                  // (Mout, ldo) fp32 or bf16
     const float *res;           // EPI 1: residual (Mout, ldr) fp32
     float *part;                // optional BatchNorm partials [grid][2][NT*16]
-    double *part2;              // optional second-level table [C3_P2_ROWS][2][NT*16] (zeroed by the caller)
+    double *part2;              // optional second-level table [D3_P2_ROWS][2][NT*16] (zeroed by the caller)
     int ldx, ldo, ldr, Mout, ntiles;
     unsigned long long xbytes;  // extent of x in bytes: ((Min - 1) * ldx + Cin) * 2
     // EPI 2 (BatchNorm-backward epilogue): the stored value is g = acc * relu'(bn(bnx)), partials (sum g, sum g * xhat)
@@ -146,16 +134,16 @@ enum { C3_EPI_PLAIN = 0, C3_EPI_RES = 1, C3_EPI_BNBWD = 2 };
 
 // The reduction of one tile with LQ live gather groups: straight-line code per LQ (the waits count exactly the loads behind them).
 template <int LQ, int ST, int NT, int QC>
-__device__ __forceinline__ void c3_reduce(c3_f32x4 (&acc)[NT], const __amdgpu_buffer_rsrc_t rx, const unsigned int (&words)[4],
+__device__ __forceinline__ void c3_reduce(f32x4 (&acc)[NT], const __amdgpu_buffer_rsrc_t rx, const unsigned int (&words)[4],
                                           const unsigned int (&ids)[7], const unsigned int rowb, const uint4 *wS, const int wlane,
                                           const int g8, uint4 &tw_next, unsigned int (&ids_next)[8], const uint4 *tq_next, const unsigned int *rec_next,
                                           const bool has_next) {
     constexpr int NCH = (LQ + QC - 1) / QC;
-    c3_u32x4 buf[NCH > 1 ? 2 : 1][QC * ST];
+    u32x4_t buf[NCH > 1 ? 2 : 1][QC * ST];
     int wq[LQ > 0 ? LQ : 1];                // fragment base of (offset k_{4q+g}, c8 0, n 0) for this lane
 #pragma unroll
     for (int q = 0; q < LQ; q++) wq[q] = (int)__umul24((ids[q] >> g8) & 0xFFu, (unsigned int)(ST * NT * 16)) + wlane;
-    auto issue = [&](const int c, c3_u32x4 (&dst)[QC * ST]) __attribute__((always_inline)) {
+    auto issue = [&](const int c, u32x4_t (&dst)[QC * ST]) __attribute__((always_inline)) {
 #pragma unroll
         for (int j = 0; j < QC; j++) {
             const int q = c * QC + j;
@@ -166,19 +154,19 @@ __device__ __forceinline__ void c3_reduce(c3_f32x4 (&acc)[NT], const __amdgpu_bu
             for (int c8 = 0; c8 < ST; c8++) dst[j * ST + c8] = __builtin_amdgcn_raw_buffer_load_b128(rx, off + (unsigned int)c8 * 16u, 0, 0);
         }
     };
-    auto products = [&](const int c, const c3_u32x4 (&src)[QC * ST]) __attribute__((always_inline)) {
+    auto products = [&](const int c, const u32x4_t (&src)[QC * ST]) __attribute__((always_inline)) {
 #pragma unroll
         for (int j = 0; j < QC; j++) {
             const int q = c * QC + j;
             if (q >= LQ) continue;
 #pragma unroll
             for (int c8 = 0; c8 < ST; c8++) {
-                const c3_bf16x8 B = __builtin_bit_cast(c3_bf16x8, src[j * ST + c8]);
+                const bf16x8_t B = __builtin_bit_cast(bf16x8_t, src[j * ST + c8]);
 #pragma unroll
                 for (int n = 0; n < NT; n++) {
                     const uint4 w = wS[wq[q] + (c8 * NT + n) * 16];
                     // transposed product: D[m = channel][n = row] += W^T[channel][k] * X^T[k][row]
-                    acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(c3_bf16x8, w), B, acc[n], 0, 0, 0);
+                    acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, w), B, acc[n], 0, 0, 0);
                 }
             }
         }
@@ -238,9 +226,9 @@ __global__ __launch_bounds__(NW * 64) void spconv_fwd3_kernel(const Conv3Args a,
         tg0 = (b & 7) * nx * per + (b >> 3); tstride = nx;
         tg1 = min(ntg, ((b & 7) + 1) * nx * per);
     } else { tg0 = b; tstride = nb; tg1 = ntg; }
-    c3_f32x4 ssum[NT], ssq[NT];
+    f32x4 ssum[NT], ssq[NT];
 #pragma unroll
-    for (int n = 0; n < NT; n++) { ssum[n] = (c3_f32x4){0.f, 0.f, 0.f, 0.f}; ssq[n] = (c3_f32x4){0.f, 0.f, 0.f, 0.f}; }
+    for (int n = 0; n < NT; n++) { ssum[n] = (f32x4){0.f, 0.f, 0.f, 0.f}; ssq[n] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
     const unsigned int rowb = (unsigned int)a.ldx * 2u;
     const int g8 = g * 8;
     const int wave_u = __builtin_amdgcn_readfirstlane(wave);
@@ -262,28 +250,28 @@ __global__ __launch_bounds__(NW * 64) void spconv_fwd3_kernel(const Conv3Args a,
         const long long base_b = ((long long)row0 - 32768) * (long long)rowb;
         const long long avail = (long long)a.xbytes - base_b;
         const long long win = 65535ll * (long long)rowb;
-        const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void *)((const char *)a.x + base_b), 0, (int)(avail < win ? avail : win), C3_RSRC_FLAGS);
+        const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void *)((const char *)a.x + base_b), 0, (int)(avail < win ? avail : win), D3_RSRC_FLAGS);
         const unsigned int words[4] = {tw.x, tw.y, tw.z, tw.w};
         unsigned int idq[7];
 #pragma unroll
         for (int i = 0; i < 7; i++) idq[i] = (unsigned int)__builtin_amdgcn_readfirstlane((int)ids[i]);
         const int lq = __builtin_amdgcn_readfirstlane((int)ids[7]);
         // ---- epilogue operands that do not depend on the products: requested ahead of the gathers
-        c3_f32x4 e_res[NT];
+        f32x4 e_res[NT];
         uint2 e_bx16[NT];
         const bool rowok = urow < a.Mout;
 #pragma unroll
         for (int n = 0; n < NT; n++) {
-            e_res[n] = (c3_f32x4){0.f, 0.f, 0.f, 0.f}; e_bx16[n] = make_uint2(0u, 0u);
-            if (EPI == C3_EPI_RES && rowok) e_res[n] = *(const c3_f32x4 *)(a.res + (long long)urow * a.ldr + n * 16 + g * 4);
+            e_res[n] = (f32x4){0.f, 0.f, 0.f, 0.f}; e_bx16[n] = make_uint2(0u, 0u);
+            if (EPI == C3_EPI_RES && rowok) e_res[n] = *(const f32x4 *)(a.res + (long long)urow * a.ldr + n * 16 + g * 4);
             if (EPI == C3_EPI_BNBWD && rowok) {
                 if (BXBF) e_bx16[n] = *(const uint2 *)((const unsigned short *)a.bnx + (long long)urow * a.ldbx + n * 16 + g * 4);
-                else e_res[n] = *(const c3_f32x4 *)((const float *)a.bnx + (long long)urow * a.ldbx + n * 16 + g * 4);
+                else e_res[n] = *(const f32x4 *)((const float *)a.bnx + (long long)urow * a.ldbx + n * 16 + g * 4);
             }
         }
-        c3_f32x4 acc[NT];
+        f32x4 acc[NT];
 #pragma unroll
-        for (int n = 0; n < NT; n++) acc[n] = (c3_f32x4){0.f, 0.f, 0.f, 0.f};
+        for (int n = 0; n < NT; n++) acc[n] = (f32x4){0.f, 0.f, 0.f, 0.f};
         const int ntile = __builtin_amdgcn_readfirstlane(tile + tstride * NW);
         const bool has_next = tg + tstride < tg1 && ntile < a.ntiles;
         const int ptile = __builtin_amdgcn_readfirstlane(has_next ? ntile : tile);       // (provably uniform: the record is a scalar load)
@@ -300,10 +288,10 @@ __global__ __launch_bounds__(NW * 64) void spconv_fwd3_kernel(const Conv3Args a,
 #pragma unroll
         for (int n = 0; n < NT; n++) {
             const int col = n * 16 + g * 4;
-            c3_f32x4 vv = acc[n];
+            f32x4 vv = acc[n];
             if (EPI == C3_EPI_RES) vv += e_res[n];
             if (EPI == C3_EPI_BNBWD) {
-                c3_f32x4 bx, xh;
+                f32x4 bx, xh;
                 if (BXBF) { bx[0] = c3_bf_lo(e_bx16[n].x); bx[1] = c3_bf_hi(e_bx16[n].x); bx[2] = c3_bf_lo(e_bx16[n].y); bx[3] = c3_bf_hi(e_bx16[n].y); }
                 else bx = e_res[n];
 #pragma unroll
@@ -315,8 +303,8 @@ __global__ __launch_bounds__(NW * 64) void spconv_fwd3_kernel(const Conv3Args a,
                 ssum[n] += vv; ssq[n] += vv * xh;      // (rows beyond Mout: vv = 0)
             } else { ssum[n] += vv; ssq[n] += vv * vv; }
             if (rowok) {
-                if (OBF) *(uint2 *)((unsigned short *)a.out + (long long)urow * a.ldo + col) = make_uint2(c3_pack2(vv[0], vv[1]), c3_pack2(vv[2], vv[3]));
-                else *(c3_f32x4 *)((float *)a.out + (long long)urow * a.ldo + col) = vv;
+                if (OBF) *(uint2 *)((unsigned short *)a.out + (long long)urow * a.ldo + col) = make_uint2(pack2bf2(vv[0], vv[1]), pack2bf2(vv[2], vv[3]));
+                else *(f32x4 *)((float *)a.out + (long long)urow * a.ldo + col) = vv;
             }
         }
     }
@@ -337,17 +325,12 @@ __global__ __launch_bounds__(NW * 64) void spconv_fwd3_kernel(const Conv3Args a,
 #pragma unroll
             for (int w = 0; w < NW; w++) s += redS[w * 2 * NT * 16 + t];
             a.part[(long long)b * 2 * NT * 16 + t] = s;
-            if (a.part2) unsafeAtomicAdd(&a.part2[(b % C3_P2_ROWS) * 2 * NT * 16 + t], (double)s);
+            if (a.part2) unsafeAtomicAdd(&a.part2[(b % D3_P2_ROWS) * 2 * NT * 16 + t], (double)s);
         }
     }
 }
 
 // ------------------------------------------------------------------------------ host side
-static int c3_ncu() {
-    static int n = 0;
-    if (!n) { int dev = 0; hipDeviceProp_t pr; n = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0) ? pr.multiProcessorCount : 256; }
-    return n;
-}
 // one row per instantiated shape: ST = Cin / 8, NT = Cout / 16, waves per workgroup, gather groups per chunk
 struct Conv3Shape { int st, nt, nw, qc; };
 #define C3_SHAPES(X) X(2, 1, 4, 7) X(2, 2, 8, 7) X(4, 1, 8, 2) X(4, 2, 8, 2) X(4, 4, 16, 2) X(6, 3, 16, 1) X(8, 2, 16, 1)
@@ -367,7 +350,7 @@ static Conv3Plan conv3_plan(int Mout, int Cin, int Cout) {
     if (!pick) return p;
     p.nw = pick->nw; p.qc = pick->qc; p.lds = c3_lds_bytes(ST, NT, p.nw);
     if (p.lds > 160 * 1024) return p;
-    p.maxgrid = c3_ncu() * (16 / p.nw);          // upper bound of the grid (the partial table's rows): 16 waves per CU
+    p.maxgrid = d3_conv_ncu() * (16 / p.nw);          // upper bound of the grid (the partial table's rows): 16 waves per CU
     p.ok = 1;
     return p;
 }
@@ -395,7 +378,7 @@ static int c3_launch_inst(const Conv3Args &a, const Conv3Plan &p, int *grid_out,
     }
     // persistent workgroups: every resident slot of the chip once, fewer when there are fewer tile groups
     const int ntg = (a.ntiles + NW - 1) / NW;
-    const int cap = c3_ncu() * occ_dev[dev];
+    const int cap = d3_conv_ncu() * occ_dev[dev];
     const int per = (ntg + cap - 1) / cap;
     int grid = (ntg + per - 1) / per;
     if (grid >= 8) grid = (grid + 7) / 8 * 8;      // (XCD-interleaved ranges want a multiple of 8; a surplus workgroup finds no tile and writes a zero partial row)

@@ -17,18 +17,14 @@
 //     copy, gradient accumulation is fused into the kernels that produce the second contribution;
 //   * all weights are re-packed to bf16 MFMA fragment order by ONE launch per forward;
 //   * REFERENCE PRECISION: a program whose buffers are all fp32 (netexec.py builds it for minkowski.set_exact(True)) runs the
-//     same schedule with fp32 activations / gradients, fp32 weight fragments and the D3_CONV_F32 kernels of spconv2.hip
+//     same schedule with fp32 activations / gradients, fp32 weight fragments and the D3_CONV_F32 kernels of spconv2.hip / wgrad.hip
 //     (exact fp32 products on v_mfma_f32_16x16x4_f32) -- MinkowskiEngine's own precision (model/common.py:32-41).
-// Kernels used: spconv2.hip (d3_conv2_run / d3_conv2_wgrad, conv.h) and the strided BatchNorm kernels below.
+// Kernels used: spconv2.hip and wgrad.hip (d3_conv2_run / d3_conv2_wgrad, conv.h) and the strided BatchNorm kernels below.
 #include "conv.h"
 #include <vector>
 #include <map>
 #include <string.h>
 #include <stdlib.h>
-
-extern "C" size_t d3_spconv_pack_bytes(int K, int Cin, int Cout);
-extern "C" size_t d3_spconv_pack_bytes_ex(int K, int Cin, int Cout, int flags);
-extern "C" int d3_spconv_fwd2_nparts_ex(int Mout, int K, int Cin, int Cout, int flags);
 
 // ------------------------------------------------------------------------------ small kernels
 __device__ __forceinline__ unsigned int un_pack2bf(float lo, float hi) {
@@ -108,7 +104,6 @@ __global__ void un_padcast_kernel(const float *__restrict__ x, unsigned short *_
 
 #define UN_T 256
 // per-channel sum / sum of squares of x (M, ld) -> partials [block][2][C] (fp32; summed in fp64 by the finalize)
-#define UN_P2_ROWS 16      // rows of a second-level fp64 partial table (== C2_P2_ROWS of spconv2.hip: the producers add row = workgroup % 16)
 __global__ __launch_bounds__(UN_T) void un_stats_parts_kernel(const float *__restrict__ x, int ld, int M, int C, float *part, double *part2) {
     __shared__ float s1[UN_T], s2[UN_T];
     const int t = threadIdx.x;
@@ -129,13 +124,13 @@ __global__ __launch_bounds__(UN_T) void un_stats_parts_kernel(const float *__res
         part[(size_t)blockIdx.x * 2 * C + t] = da;
         part[(size_t)blockIdx.x * 2 * C + C + t] = db;
         if (part2) {
-            unsafeAtomicAdd(&part2[(size_t)(blockIdx.x % UN_P2_ROWS) * 2 * C + t], (double)da);
-            unsafeAtomicAdd(&part2[(size_t)(blockIdx.x % UN_P2_ROWS) * 2 * C + C + t], (double)db);
+            unsafeAtomicAdd(&part2[(size_t)(blockIdx.x % D3_P2_ROWS) * 2 * C + t], (double)da);
+            unsafeAtomicAdd(&part2[(size_t)(blockIdx.x % D3_P2_ROWS) * 2 * C + C + t], (double)db);
         }
     }
 }
 
-// p2 (optional): the producer's second-level table [UN_P2_ROWS][2][width] of fp64 sums (spconv2.hip C2_P2_ROWS)
+// p2 (optional): the producer's second-level table [D3_P2_ROWS][2][width] of fp64 sums
 struct StatSrc { const float *part; int nparts, width, c0, cn; const double *p2; };
 
 // mean / biased variance of C channels from up to two partial sets (a concatenated input has two producers), and
@@ -401,7 +396,7 @@ __device__ __forceinline__ void un_fs_reduce(const StatSrc &s0, const StatSrc &s
     sa = 0.; sb = 0.;
     if (t < C) for (int k = 0; k < S; k++) { sa += acc[((size_t)k * C + t) * 2]; sb += acc[((size_t)k * C + t) * 2 + 1]; }
 }
-// The same sums from the producers' second-level tables (round 5): UN_P2_ROWS rows per source, ONE round trip -- thread `col` of
+// The same sums from the producers' second-level tables (round 5): D3_P2_ROWS rows per source, ONE round trip -- thread `col` of
 // the 2 C columns (sum | sum of squares) requests its 16 values together and adds them in row order.  acc: >= 2 C doubles.
 __device__ __forceinline__ void un_fs_reduce2(const StatSrc &s0, const StatSrc &s1, int C, double *acc, double &sa, double &sb) {
     const int t = threadIdx.x;
@@ -410,12 +405,12 @@ __device__ __forceinline__ void un_fs_reduce2(const StatSrc &s0, const StatSrc &
         const bool first = (c >= s0.c0 && c < s0.c0 + s0.cn);
         const StatSrc &src = first ? s0 : s1;
         const double *p = src.p2 + (size_t)st * src.width + (c - src.c0);
-        double v[UN_P2_ROWS];
+        double v[D3_P2_ROWS];
 #pragma unroll
-        for (int r = 0; r < UN_P2_ROWS; r++) v[r] = p[(size_t)r * 2 * src.width];
+        for (int r = 0; r < D3_P2_ROWS; r++) v[r] = p[(size_t)r * 2 * src.width];
         double a = 0.;
 #pragma unroll
-        for (int r = 0; r < UN_P2_ROWS; r++) a += v[r];
+        for (int r = 0; r < D3_P2_ROWS; r++) a += v[r];
         acc[col] = a;
     }
     __syncthreads();
@@ -603,7 +598,7 @@ __global__ void un_add_kernel(float *__restrict__ dst, int ldd, const float *__r
 }
 
 // Row-split partials of ALL weight gradients of a backward -> dW, one launch (one 6 us reduction per layer otherwise, 69
-// of them on the side stream).  Same arithmetic as spconv2.hip's wgrad2_reduce_kernel: 32 elements x 8 split groups per
+// of them on the side stream).  Same arithmetic as wgrad.hip's wgrad2_reduce_kernel: 32 elements x 8 split groups per
 // workgroup, group sums combined in group order.
 struct RedJob { const float *part; float *dW; long long n; int R, accum; long long start; };   // start: first workgroup
 __global__ __launch_bounds__(256) void un_wgrad_reduce_batched_kernel(const RedJob *__restrict__ jobs, int njobs) {
@@ -663,7 +658,7 @@ struct OpD {
     int bn_of_in;                     // CONV: index of the BNACT op that produced `in` (-1: none) -> fused BN-backward dgrad
     int fused_by;                     // BNACT: index of the CONV whose dgrad epilogue already did this op's reductions
     size_t bpart_off; int bparts;     // BNACT: gradient-arena offset / count of those partials
-    size_t part2_off, bpart2_off;     // second-level fp64 tables (UN_P2_ROWS rows; inside the per-call zeroed regions): producer ops / BNACT backward
+    size_t part2_off, bpart2_off;     // second-level fp64 tables (D3_P2_ROWS rows; inside the per-call zeroed regions): producer ops / BNACT backward
     int wg_hazard;                    // CONV: its output gradient buffer is accumulated into in place later in the backward
     size_t wpart_off, wpart_bytes; int wsplits;   // CONV: weight-gradient partials in the gradient arena
     int use_shadow;                   // CONV: reads its output gradient from the bf16 shadow of that (fp32) gradient buffer
@@ -1092,14 +1087,14 @@ extern "C" int d3_net_plan(void *h, const int *rows, size_t *arena_bytes, size_t
     off = d3_align(off);
     // second-level partial tables (round 5) live in the same zeroed-once-per-call region as the ticket counters: no extra fill launch
     for (auto &o : n->ops)
-        if ((o.type == OP_CONV || o.type == OP_STATS) && o.nparts > 0) { o.part2_off = off; off += d3_align((size_t)UN_P2_ROWS * 2 * o.partw * 8); }
+        if ((o.type == OP_CONV || o.type == OP_STATS) && o.nparts > 0) { o.part2_off = off; off += d3_align((size_t)D3_P2_ROWS * 2 * o.partw * 8); }
     n->cnt_bytes = off - n->cnt_off0;
     n->bcnt_off0 = goff;
     goff = d3_align(goff);
     for (auto &o : n->ops) {
         if (o.type != OP_BNACT || o.fused_by < 0) continue;
         const OpD &cv = n->ops[o.fused_by];
-        o.bpart2_off = goff; goff += d3_align((size_t)UN_P2_ROWS * 2 * ((cv.CinW + 15) / 16 * 16) * 8);
+        o.bpart2_off = goff; goff += d3_align((size_t)D3_P2_ROWS * 2 * ((cv.CinW + 15) / 16 * 16) * 8);
     }
     n->bcnt_bytes = goff - n->bcnt_off0;
     n->arena_bytes = off;

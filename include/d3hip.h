@@ -279,8 +279,8 @@ int d3_spconv_fwd(const float *x, const int *tbl, const float *W, float *out, in
 int d3_spconv_wgrad(const float *x, const int *tbl, const float *dy, float *dW, int Min, int Mout, int K, int Cin,
                     int Cout, int flags, void *stream);
 
-/* Second-generation MFMA kernels (csrc/spconv2.hip): wave-autonomous register gather, v_mfma_f32_16x16x32_bf16,
- * weights pre-packed into bf16 MFMA fragment order.  Same contraction and flags as d3_spconv_fwd / d3_spconv_wgrad
+/* Second-generation MFMA kernels (csrc/spconv2.hip; weight gradients: csrc/wgrad.hip): wave-autonomous register gather,
+ * v_mfma_f32_16x16x32_bf16, weights pre-packed into bf16 MFMA fragment order.  Same contraction and flags as d3_spconv_fwd / d3_spconv_wgrad
  * (D3_CONV_FLIPK / D3_CONV_TRANSW are applied by the pack step); Cin % 8 == 0 (wgrad2: Cout % 8 == 0 too).
  *   pack   : W (K,Cin,Cout) f32 [(K,Cout,Cin) with TRANSW] -> Wp, d3_spconv_pack_bytes() bytes.
  *   fwd2   : out[u, 0:Cout] (row stride ldo) = sum_k x[tbl[u,k]] @ Wk (+ res[u] (row stride ldr)) (+ out with

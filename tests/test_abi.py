@@ -67,7 +67,8 @@ def test_convolutions_hand_nothing_over_through_globals():
     banned = ("d3_spconv_next_", "d3_spconv_set_last_nparts", "g_c2_inst", "struct Conv3Bn", "struct Conv2Bn")
     bad = [(f, w) for f in sorted(os.listdir(csrc)) for w in banned if w in open(os.path.join(csrc, f), errors="ignore").read()]
     assert not bad, bad
-    assert "thread_local" not in open(os.path.join(csrc, "spconv2.hip")).read()
+    for f in ("spconv2.hip", "wgrad.hip"):
+        assert "thread_local" not in open(os.path.join(csrc, f)).read(), f
 
 
 def test_switch_table_stays_small(built_lib):

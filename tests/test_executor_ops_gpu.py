@@ -344,7 +344,7 @@ def test_few_row_batchnorm_in_one_launch_matches_the_separate_kernels(dev):
 
 
 def test_second_level_batchnorm_partials_match_the_full_table_reduction(dev):
-    """Round 5 (csrc/spconv2.hip C2_P2_ROWS, csrc/unet.hip un_fs_reduce2, D3_BN_PART2): every producer workgroup also adds its
+    """Round 5 (csrc/conv.h D3_P2_ROWS, csrc/unet.hip un_fs_reduce2, D3_BN_PART2): every producer workgroup also adds its
     BatchNorm partial row into a 16-row fp64 table (hardware fp64 atomics, row = workgroup % 16) and the BatchNorm launches
     reduce those 16 rows instead of the producer's whole per-workgroup table.  Both paths add the SAME fp32 partial values in fp64;
     such sums are exact (hence order-independent) unless one channel's addends span more than 2^29 in magnitude, so the two

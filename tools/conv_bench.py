@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-layer micro-benchmark of the sparse convolution kernels on the canonical scene's coordinate levels:
-forward / data gradient / weight gradient, first-generation (spconv.hip) vs second-generation (spconv2.hip) kernels,
+forward / data gradient / weight gradient, first-generation (spconv.hip) vs second-generation (spconv2.hip; weight gradients: wgrad.hip) kernels,
 with a cross-check of the two results.  usage: python tools/conv_bench.py [levels] [iters]"""
 import os
 import sys

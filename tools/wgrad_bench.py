@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Weight-gradient kernels per layer shape on the bench workload's coordinate levels (N scenes of the speaker config):
-third-generation kernel (spconv_wgrad3_kernel) vs the generic kernel with transposing LDS reads,
+third-generation kernel (spconv_wgrad3_kernel) vs the generic kernel with transposing LDS reads (both csrc/wgrad.hip),
 selected per call through D3_WG3, results cross-checked against the generic kernel.
 usage: python tools/wgrad_bench.py [scenes=4] [levels=3] [iters=20]"""
 import os
