@@ -166,6 +166,10 @@ SIGNATURES = {
     "d3_scene_emit": (i32, [vp, vp, vp, i32, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
     "d3_scene_relabel": (i32, [vp, i32, i32, vp, sz, vp]),
     "d3_scene_instances": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+    "d3_lang_features_ws_bytes": (sz, [i32, i32]),
+    "d3_lang_features": (i32, [vp, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp, sz, vp]),
+    "d3_ref_targets_ws_bytes": (sz, [i32]),
+    "d3_ref_targets": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, sz, vp]),
     "d3_multiview_limits": (i32, [pi, pi, pi]),
     "d3_multiview_project_ws_bytes": (sz, [i32, i32]),
     "d3_multiview_project": (i32, [vp, i32, vp, vp, vp, i32, C.POINTER(f64), i32, i32, vp, vp, vp, sz, vp]),

@@ -779,6 +779,37 @@ int d3_scene_instances(const double *y, const int *ids, const int *sem, int n, i
                        float *info, int *num_point, int *gt_idx, int *gt_off, double *boxes, int *counts, void *ws,
                        size_t ws_bytes, void *stream);
 
+/* ---- description batches (csrc/lang_prep.hip, driven by d3net_amd/lang_prep.py) ------------------------------------------------
+ * The description half of PipelineDataset.__getitem__ (lib/dataset/pipeline.py:69-138, :250-318) from device-resident tables:
+ * tokens (Nd,L) int32 = the sos / eos-wrapped, trimmed token ids of every description (_tranform_des, :504-552, ids only), zero
+ * padded; lens (Nd) int32 = min(len(token) + 2, L) (:104-105); glove (V,D) float32.
+ * d3_lang_features, over S = B * C slots (replaces the (L,300) float64 arrays of :531-549, the deepcopy of :103, the erase of
+ * :554-565, the stores of :133-135, the casts of :301-303 and the stacking of scannet_collate_fn):
+ *   rows_host (S): description of each slot, -1 = SYNTHETIC (all zeros, lang_len 0, :121-124); erase_ptr_host (S+1) /
+ *   erase_pos_host: CSR list of each slot's erased positions; all three in HOST memory, copied into ws on the stream by the
+ *   call (keep them valid until that copy has run; for pageable memory that is before the call returns).
+ *   lang_feat (S,L,D): position p < lens[row] = glove[tokens[row,p]], an erased position = glove[unk], every other exactly 0;
+ *   lang_ids (S,L) int64 (never erased), lang_len (S) int64.  One launch, 16-byte accesses, flat over (slot, position, quad).
+ *   D % 4 != 0, unk outside [0,V) or an erase position outside [0,L): D3_ERR_ARG; a row outside [-1,Nd): D3_ERR_RANGE; all
+ *   checked on the host before any copy or launch.  Token ids are the caller's to check against V (DescriptionIndex does).
+ *   ws: d3_lang_features_ws_bytes(S, E), E = erase_ptr_host[S] (0: outside the limits). */
+size_t d3_lang_features_ws_bytes(int S, int E);
+int d3_lang_features(const int *tokens, const int *lens, int Nd, const float *glove, int V, int D, int L, int unk,
+                     const int *rows_host, const int *erase_ptr_host, const int *erase_pos_host, int S, float *lang_feat,
+                     long long *lang_ids, long long *lang_len, void *ws, size_t ws_bytes, void *stream);
+/* d3_ref_targets (pipeline.py:250-278) from the stacked gt_bbox_object_id / gt_bbox_label (B,R) int64, gt_bbox (B,R,8,3) float32 and
+ * object_id (B,C) int64:
+ *   ref_label (B,C,R) int64: 1 where gt_label == 1 and the id equals the slot's object id; ref_corner (B,C,8,3): gt_bbox of the
+ *   highest matching row (get_3d_box without heading == get_3d_box_batch with heading 0, bit for bit), zeros when none matches;
+ *   rots (B,R,3,3) float32 / rot_masks (B,R) int64: the Scan2CAD matrix of a row with gt_label == 1 whose id is in its scene's
+ *   table, else zeros.  Table: rot_off (Ns+1), rot_ids (T) int32, rot_mats (T,3,3) float32 on the device (NULL when Ns == 0);
+ *   scene_host (B), HOST memory: each scene's table index, -1 = none; outside [-1,Ns): D3_ERR_RANGE before any launch.
+ *   One wave per (scene, slot) and per (scene, row), plain stores.  ws: d3_ref_targets_ws_bytes(B). */
+size_t d3_ref_targets_ws_bytes(int B);
+int d3_ref_targets(const long long *gt_ids, const long long *gt_label, const float *gt_bbox, const long long *object_id, int B, int C,
+                   int R, const int *rot_off, const int *rot_ids, const float *rot_mats, int Ns, const int *scene_host,
+                   long long *ref_label, float *ref_corner, float *rots, long long *rot_masks, void *ws, size_t ws_bytes, void *stream);
+
 /* ---- multiview feature projection (csrc/multiview.hip, driven by d3net_amd/multiview.py) --------------------------------------
  * The reference's ProjectionHelper.compute_projection / project (lib/utils/projection.py:180-256) and the per-scene loop of
  * data/scannet/project_multiview_features.py:88-205.  One scene: points (N,3) float32 mesh vertices; F frames in the caller's order:
