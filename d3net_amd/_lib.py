@@ -99,6 +99,7 @@ SIGNATURES = {
     "d3_net_destroy": (None, [vp]),
     "d3_net_plan": (i32, [vp, vp, C.POINTER(sz), C.POINTER(sz)]),
     "d3_net_tensor_offset": (i64, [vp, i32]),
+    "d3_net_describe": (i64, [vp, vp, i64]),
     "d3_net_forward": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, vp]),
     "d3_net_backward": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "d3_tall_wgrad_ws_bytes": (sz, [i32, i32]),

@@ -640,31 +640,67 @@ __global__ __launch_bounds__(256) void un_wgrad_reduce_batched_kernel(const RedJ
 // ------------------------------------------------------------------------------ the network object
 enum { OP_CONV = 1, OP_BNACT = 2, OP_PADCAST = 3, OP_STATS = 4 };
 enum { MAP_K1 = 0, MAP_K3 = 1, MAP_DOWN = 2, MAP_UP = 3 };
+enum { GV_GIN = 0, GV_GOUT = 1, GV_ARENA = 2 };      // where a gradient lives: the caller's gin / the caller's gout / the gradient arena
 
+struct Region { size_t off = 0, bytes = 0; };        // a 256-byte aligned piece of an arena, placed by d3_net_plan (bytes 0: none)
 struct TensorD { int level, C, ld, coff, dtype, buf; };
-struct BufD { int level, width, dtype; size_t off, goff; int need_grad; };
+struct BufD { int level, width, dtype; int need_grad = 1; Region act, grad, shadow; };   // activation arena / gradient arena / bf16 shadow of the gradient
 struct SrcRef { int op, c0, cn; };
+// gradient view of a tensor (residual aliases followed to their root): root = the gradient buffer (-1: gin, -2: gout), row stride and
+// column offset in elements, off = the view's first byte in the gradient arena (d3_net_plan)
+struct GradView { int kind = GV_ARENA, root = -1, ld = 0, coff = 0, bf16 = 0; size_t off = 0; };
 struct OpD {
-    int type, in, out, res, w, gamma, beta, rmean, rvar, map, mlevel, K, CinW, stats, relu;
-    float eps, momentum;
-    // derived
-    int Cin, Cout;                    // padded channel counts of the call
-    size_t wp_fwd, wp_bwd, part_off, state_off;   // arena offsets (bytes)
-    int nparts, partw;
+    int type = 0, in = -1, out = -1, res = -1, w = -1, gamma = -1, beta = -1, rmean = -1, rvar = -1, map = 0, mlevel = 0, K = 1, CinW = 0, stats = 0, relu = 0;
+    float eps = 0.f, momentum = 0.f;
+    // ---- decided by d3_net_create
+    int Cin = 0, Cout = 0;            // padded channel counts of the call
     std::vector<SrcRef> srcs;         // BNACT: producers of the input's batch statistics
-    int in_grad_mode;                 // backward: 0 = input needs no gradient, 1 = write, 2 = accumulate
-    int res_mode;                     // backward: 0 none, 1 alias (no work), 2 add, 3 copy (first contribution)
-    int needs_dgrad_pack;
-    int bn_of_in;                     // CONV: index of the BNACT op that produced `in` (-1: none) -> fused BN-backward dgrad
-    int fused_by;                     // BNACT: index of the CONV whose dgrad epilogue already did this op's reductions
-    size_t bpart_off; int bparts;     // BNACT: gradient-arena offset / count of those partials
-    size_t part2_off, bpart2_off;     // second-level fp64 tables (D3_P2_ROWS rows; inside the per-call zeroed regions): producer ops / BNACT backward
-    int wg_hazard;                    // CONV: its output gradient buffer is accumulated into in place later in the backward
-    size_t wpart_off, wpart_bytes; int wsplits;   // CONV: weight-gradient partials in the gradient arena
-    int use_shadow;                   // CONV: reads its output gradient from the bf16 shadow of that (fp32) gradient buffer
-    int write_shadow;                 // BNACT: its backward apply also writes the bf16 shadow of the buffer it finalises
+    int in_grad_mode = 0;             // backward: 0 = input needs no gradient, 1 = write, 2 = accumulate
+    int res_mode = 0;                 // backward: 0 none, 1 alias (no work), 2 add, 3 copy (first contribution)
+    int needs_dgrad_pack = 0;
+    int bn_of_in = -1;                // CONV: index of the BNACT op that produced `in` (-1: none) -> fused BN-backward dgrad
+    int fused_by = -1;                // BNACT: index of the CONV whose dgrad epilogue already did this op's reductions
+    int wg_hazard = 0;                // CONV: its output gradient buffer is accumulated into in place later in the backward
+    int use_shadow = 0;               // CONV: reads its output gradient from the bf16 shadow of that (fp32) gradient buffer
+    int write_shadow = 0;             // BNACT: its backward apply also writes the bf16 shadow of the buffer it finalises
+    // CONV: the flag words of its three calls.  dgrad_flags lacks D3_CONV_ACCUM (in_grad_mode == 2 adds it where the call has no fused
+    // BatchNorm), wgrad_flags the per-call D3_CONV_ACCUM of paccum; D3_CONV_XSTAT in wgrad_flags also means "reads the transposed map"
+    int fwd_flags = 0, dgrad_flags = 0, wgrad_flags = 0;
+    int k3_tables = 0;                // CONV: its calls may take the level's 16-bit map / lane table
+    int dy_view = -1;                 // CONV: index into Net::gv of the view its backward reads dy from (the tensor's, or the shadow's)
+    // ---- laid out by d3_net_plan
+    Region wp_fwd, wp_bwd, part, part2, state;   // activation arena; part2 / bpart2: second-level fp64 tables (D3_P2_ROWS rows) inside the per-call zeroed areas
+    Region bpart, bpart2, wpart;                 // gradient arena: BNACT backward partials (of the fusing conv's dgrad), CONV weight-gradient partials
+    int nparts_max = 0, bparts_max = 0;          // upper bounds of the partial rows a forward / a backward writes (a call's own counts are local to it)
+    int partw = 0, wsplits = 1;
 };
 #define RED_RING 32
+// what a forward / backward call changes: job tables, events, streams and the one-call hand-overs (the plan itself is read-only there)
+struct NetRun {
+    // packing jobs (device copy refreshed when a parameter pointer or the arena moves)
+    std::vector<PackJob> jobs;
+    PackJob *jobs_dev = nullptr;
+    size_t jobs_cap = 0;
+    hipStream_t side = nullptr;
+    hipStream_t side2 = nullptr;      // second weight-gradient stream
+    std::vector<hipEvent_t> ev;       // pool
+    size_t ev_used = 0;
+    const void *xp_ext = nullptr;      // the stem's padded input prepared by the caller (d3_net_padcast) for the next forward / backward call, or NULL
+    std::vector<const void *> k3_16;   // per level: 16-bit delta form of the k3 table for the next forward / backward call (or NULL)
+    std::vector<const void *> k3_q;    // per level: the lane table (spconv3.hip) for the next forward / backward call (or NULL)
+    // gradient chunks (data-parallel overlap): chunk k of the flat parameter-gradient buffer is complete once the backward has
+    // processed op chunk_op[k] (ops run in reverse program order, parameters are registered in program order: a chunk is a
+    // contiguous tail range); two events per chunk -- side stream (weight-gradient reductions) and caller's stream
+    // (BatchNorm parameter gradients) -- let a collective stream start the chunk's all-reduce while the backward goes on
+    std::vector<int> chunk_op;
+    std::vector<hipEvent_t> chunk_ev_side, chunk_ev_main;
+    RedJob *red_host = nullptr, *red_dev = nullptr;   // pinned staging (ring of RED_RING slots) + device copies of the reduce jobs
+    size_t red_cap = 0; int red_flip = 0;
+    hipEvent_t next_event() {
+        if (ev_used == ev.size()) { hipEvent_t e; if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return nullptr; ev.push_back(e); }
+        return ev[ev_used++];
+    }
+};
 struct Net {
     std::vector<TensorD> T;
     std::vector<BufD> B;
@@ -675,40 +711,59 @@ struct Net {
     std::vector<int> gbf;             // per buffer: its gradient is stored as bf16 (single producer conv, single BatchNorm consumer)
     std::vector<int> gabf;            // per buffer: the gradient of an activation buffer (one BatchNorm writer, one convolution reader) is stored as bf16
     std::vector<int> gshadow;         // per buffer: width of the bf16 shadow of (a column window of) its fp32 gradient, 0 = none
-    std::vector<size_t> gshadow_off;  //   its offset in the gradient arena
-    size_t arena_bytes = 0, grad_bytes = 0, ws_bytes = 0, bnscr_off = 0, wgws_off = 0, bnscr_bytes = 0, wgws_bytes = 0;
+    std::vector<GradView> gv;         // per tensor: its gradient view; then per buffer (index ntensors + buffer): the view of its shadow
+    size_t arena_bytes = 0, grad_bytes = 0;
+    Region bnscr, wgws;               // gradient arena: scratch of the unfused BatchNorm backward; 16 spare bytes
     bool planned = false;
     bool f32 = false;                 // every buffer fp32: reference-precision program (D3_CONV_F32 kernels, no bf16 gradients)
     size_t cnt_off0 = 0, cnt_bytes = 0, bcnt_off0 = 0, bcnt_bytes = 0;   // the second-level partial tables' regions (zeroed once per call)
-    // packing jobs (device copy refreshed when a parameter pointer or the arena moves)
-    std::vector<PackJob> jobs;
-    PackJob *jobs_dev = nullptr;
-    size_t jobs_cap = 0;
-    long long pack_total = 0;
-    hipStream_t side = nullptr;
-    hipStream_t side2 = nullptr;      // second weight-gradient stream
-    std::vector<hipEvent_t> ev;       // pool
-    size_t ev_used = 0;
-    // gradient chunks (data-parallel overlap): chunk k of the flat parameter-gradient buffer is complete once the backward has
-    // processed op chunk_op[k] (ops run in reverse program order, parameters are registered in program order: a chunk is a
-    // contiguous tail range); two events per chunk -- side stream (weight-gradient reductions) and caller's stream
-    // (BatchNorm parameter gradients) -- let a collective stream start the chunk's all-reduce while the backward goes on
     int xp_op = -1;                    // index of the PADCAST op of the stem input (there is at most one)
     int xp_tensor = -1;                // the PADCAST op's output tensor (the stem's zero-padded bf16 input), -1: none
-    const void *xp_ext = nullptr;      // its values prepared by the caller (d3_net_padcast) for the next forward / backward call, or NULL
-    std::vector<const void *> k3_16;   // per level: 16-bit delta form of the k3 table for the next forward / backward call (or NULL)
-    std::vector<const void *> k3_q;    // per level: the lane table (spconv3.hip) for the next forward / backward call (or NULL)
-    std::vector<int> chunk_op;
-    std::vector<hipEvent_t> chunk_ev_side, chunk_ev_main;
-    RedJob *red_host = nullptr, *red_dev = nullptr;   // pinned staging (ring of RED_RING slots) + device copies of the reduce jobs
-    size_t red_cap = 0; int red_flip = 0;
-    hipEvent_t next_event() {
-        if (ev_used == ev.size()) { hipEvent_t e; if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return nullptr; ev.push_back(e); }
-        return ev[ev_used++];
-    }
+    NetRun run;
 };
 
 static int esize(int dtype) { return dtype == 1 ? 2 : 4; }
+
+// per-buffer facts of the program that several decisions of d3_net_create ask for
+struct BufFacts { bool by_padcast = false, aliased_into = false, res_read = false; };   // produced by PADCAST / a residual gradient aliases into it / read as a residual
+
+// The gradient view of a tensor: THE place that follows galias (the aliased buffer is a whole-buffer view of the target tensor)
+static GradView grad_view(const Net *n, int tensor) {
+    GradView v;
+    const TensorD *t = &n->T[tensor];
+    for (size_t guard = 0; guard <= n->B.size(); guard++) {
+        if (t->buf < 0) { v.kind = GV_GIN; v.root = -1; v.ld = t->ld; return v; }
+        if (tensor == n->out_tensor) { v.kind = GV_GOUT; v.root = -2; v.ld = t->ld; return v; }
+        if (n->galias[t->buf] < 0) break;
+        tensor = n->galias[t->buf];
+        t = &n->T[tensor];
+    }
+    v.root = t->buf; v.ld = n->B[t->buf].width; v.coff = t->coff;
+    v.bf16 = (n->gbf[t->buf] || n->gabf[t->buf]) ? 1 : 0;          // (whole-buffer views only: coff == 0)
+    return v;
+}
+
+// Is buffer b's gradient written once and read once, by whole-buffer views: one producer of type `prod` (a convolution with a fused
+// residual never counts), one differentiated consumer of type `cons` that writes (not accumulates) its input gradient?
+static bool single_writer_reader(const Net *n, const std::vector<BufFacts> &facts, int b, int prod, int cons) {
+    if (n->galias[b] >= 0 || facts[b].aliased_into || facts[b].by_padcast || facts[b].res_read) return false;
+    if (n->out_tensor >= 0 && n->T[n->out_tensor].buf == b) return false;
+    int nprod = 0, ncons = 0;
+    for (auto &o : n->ops) {
+        if (o.type != OP_CONV && o.type != OP_BNACT) continue;
+        if (n->T[o.out].buf == b) {
+            const TensorD &t = n->T[o.out];
+            nprod++;
+            if (o.type != prod || (o.type == OP_CONV && o.res >= 0) || t.coff != 0 || t.C != n->B[b].width || (t.C & 7)) return false;
+        }
+        if (n->T[o.in].buf == b) {
+            const TensorD &t = n->T[o.in];
+            ncons++;
+            if (o.type != cons || o.in_grad_mode != 1 || t.coff != 0 || t.C != n->B[b].width || (o.type == OP_CONV && o.CinW != t.C)) return false;
+        }
+    }
+    return nprod == 1 && ncons == 1;
+}
 
 // prog: nops x 16 int64, tensors: nt x 6, bufs: nb x 3 (see d3net_amd/netexec.py, which builds them)
 extern "C" void *d3_net_create(const int64_t *prog, int nops, const int64_t *tensors, int ntensors, const int64_t *bufs,
@@ -721,7 +776,7 @@ extern "C" void *d3_net_create(const int64_t *prog, int nops, const int64_t *ten
     }
     for (int i = 0; i < nbufs; i++) {
         const int64_t *b = bufs + (size_t)i * 3;
-        n->B.push_back(BufD{(int)b[0], (int)b[1], (int)b[2], 0, 0, 1});
+        n->B.push_back(BufD{(int)b[0], (int)b[1], (int)b[2]});
     }
     n->f32 = true;
     for (auto &b : n->B) if (b.dtype == 1) n->f32 = false;
@@ -729,10 +784,6 @@ extern "C" void *d3_net_create(const int64_t *prog, int nops, const int64_t *ten
         const int64_t *p = prog + (size_t)i * 16;
         OpD o;
         o.type = (int)p[0]; o.in = (int)p[1]; o.out = (int)p[2]; o.res = (int)p[3];
-        o.w = o.gamma = o.beta = o.rmean = o.rvar = -1; o.map = 0; o.mlevel = 0; o.K = 1; o.CinW = 0; o.stats = 0; o.relu = 0;
-        o.eps = 0.f; o.momentum = 0.f; o.Cin = o.Cout = 0; o.wp_fwd = o.wp_bwd = o.part_off = o.state_off = 0;
-        o.nparts = 0; o.partw = 0; o.in_grad_mode = 0; o.res_mode = 0; o.needs_dgrad_pack = 0;
-        o.bn_of_in = -1; o.fused_by = -1; o.bpart_off = 0; o.bparts = 0; o.part2_off = 0; o.bpart2_off = 0; o.wg_hazard = 0; o.wpart_off = 0; o.wpart_bytes = 0; o.wsplits = 1; o.use_shadow = 0; o.write_shadow = 0;
         if (o.type == OP_CONV) {
             o.w = (int)p[4]; o.map = (int)p[5]; o.mlevel = (int)p[6]; o.K = (int)p[7]; o.CinW = (int)p[8]; o.stats = (int)p[9];
             o.Cin = n->T[o.in].C; o.Cout = n->T[o.out].C;
@@ -758,6 +809,11 @@ extern "C" void *d3_net_create(const int64_t *prog, int nops, const int64_t *ten
             if (tp.coff >= ti.coff && tp.coff + tp.C <= ti.coff + ti.C) o.srcs.push_back(SrcRef{(int)j, tp.coff - ti.coff, tp.C});
         }
     }
+    std::vector<BufFacts> facts(n->B.size());
+    for (auto &o : n->ops) {
+        if (o.type == OP_PADCAST) { facts[n->T[o.out].buf].by_padcast = true; n->B[n->T[o.out].buf].need_grad = 0; }
+        if (o.type == OP_CONV && o.res >= 0 && n->T[o.res].buf >= 0) facts[n->T[o.res].buf].res_read = true;
+    }
     // backward plan: gradient write / accumulate modes and residual aliases (reverse walk)
     std::vector<int> ginit(n->B.size(), 0);
     int ginit_ext = 0;   // gradient of the external input
@@ -767,14 +823,8 @@ extern "C" void *d3_net_create(const int64_t *prog, int nops, const int64_t *ten
         OpD &o = n->ops[i];
         if (o.type == OP_CONV || o.type == OP_BNACT) {
             const int bi = n->T[o.in].buf;
-            bool need = true;
-            if (bi < 0) need = n->input_needs_grad != 0;
-            else {
-                // the producer of a buffer that nobody differentiates (the stem's padded input) needs no gradient
-                bool produced_by_padcast = false;
-                for (auto &q : n->ops) if (q.type == OP_PADCAST && n->T[q.out].buf == bi) produced_by_padcast = true;
-                if (produced_by_padcast) need = false;
-            }
+            // the producer of a buffer that nobody differentiates (the stem's padded input) needs no gradient
+            const bool need = bi < 0 ? n->input_needs_grad != 0 : !facts[bi].by_padcast;
             if (!need) o.in_grad_mode = 0;
             else if (bi < 0) { o.in_grad_mode = ginit_ext ? 2 : 1; ginit_ext = 1; }
             else { o.in_grad_mode = ginit[bi] ? 2 : 1; ginit[bi] = 1; }
@@ -788,30 +838,8 @@ extern "C" void *d3_net_create(const int64_t *prog, int nops, const int64_t *ten
             }
         }
     }
-    for (auto &o : n->ops)
-        if (o.type == OP_PADCAST) n->B[n->T[o.out].buf].need_grad = 0;
-    // which convolutions' output gradients are written in place after their weight gradient was issued?
-    auto groot = [&](int tensor) {
-        for (int guard = 0; guard < 1000; guard++) {
-            const TensorD &t = n->T[tensor];
-            if (t.buf < 0) return -1;
-            if (tensor == n->out_tensor) return -2;
-            if (n->galias[t.buf] < 0) return t.buf;
-            tensor = n->galias[t.buf];
-        }
-        return -3;
-    };
-    for (int i = 0; i < (int)n->ops.size(); i++) {
-        OpD &o = n->ops[i];
-        if (o.type != OP_CONV) continue;
-        const int r = groot(o.out);
-        if (r < 0) continue;
-        for (int j = i - 1; j >= 0 && !o.wg_hazard; j--) {   // ops processed after op i in the backward
-            const OpD &q = n->ops[j];
-            if ((q.type == OP_CONV || q.type == OP_BNACT) && q.in_grad_mode == 2 && groot(q.in) == r) o.wg_hazard = 1;
-            if (q.type == OP_CONV && q.res_mode == 2 && groot(q.res) == r) o.wg_hazard = 1;
-        }
-    }
+    for (size_t x = 0; x < n->B.size(); x++)
+        if (n->galias[x] >= 0 && n->T[n->galias[x]].buf >= 0) facts[n->T[n->galias[x]].buf].aliased_into = true;
     // BN -> ReLU -> conv units: the conv's data gradient does the BatchNorm-backward reductions in its epilogue
     for (size_t i = 0; i < n->ops.size(); i++) {
         OpD &o = n->ops[i];
@@ -821,71 +849,36 @@ extern "C" void *d3_net_create(const int64_t *prog, int nops, const int64_t *ten
             if (b.type == OP_BNACT && b.out == o.in && b.fused_by < 0 && (n->T[b.out].dtype == 1 || n->f32)) { o.bn_of_in = (int)j; b.fused_by = (int)i; break; }
         }
     }
-    // Gradients with a single writer and a single reader pair are stored as bf16: the output gradient of a convolution whose
-    // output feeds exactly one BatchNorm (the first conv of every residual block) is written once by that BatchNorm's backward
-    // apply and read only by the convolution's own data- and weight-gradient kernels -- as MFMA operands, i.e. rounded to bf16
-    // on load anyway.  Rounding at the store instead is numerically identical and halves the bytes of the data gradient's
-    // 27-fold gather and of the weight gradient's dy operand.  D3_GRAD_BF16=0 keeps them in fp32 (A/B measurements).
+    const bool grad_bf16 = d3_tune(D3T_GRAD_BF16) != 0 && !n->f32;
     n->gbf.assign(n->B.size(), 0);
-    {
-        const bool on = d3_tune(D3T_GRAD_BF16) != 0 && !n->f32;
-        for (size_t b = 0; on && b < n->B.size(); b++) {
-            if (n->galias[b] >= 0) continue;
-            if (n->out_tensor >= 0 && n->T[n->out_tensor].buf == (int)b) continue;
-            bool ok = true;
-            for (size_t x = 0; x < n->B.size(); x++)
-                if (n->galias[x] >= 0 && n->T[n->galias[x]].buf == (int)b) ok = false;      // a residual gradient aliases into it
-            int nprod = 0, ncons = 0;
-            for (auto &o : n->ops) {
-                if (o.type == OP_PADCAST && n->T[o.out].buf == (int)b) ok = false;
-                if (o.type == OP_STATS) continue;
-                if (o.type == OP_CONV && o.res >= 0 && n->T[o.res].buf == (int)b) ok = false;
-                if ((o.type == OP_CONV || o.type == OP_BNACT) && n->T[o.out].buf == (int)b) {
-                    const TensorD &t = n->T[o.out];
-                    nprod++;
-                    if (o.type != OP_CONV || o.res >= 0 || t.coff != 0 || t.C != n->B[b].width || (t.C & 7)) ok = false;
-                }
-                if ((o.type == OP_CONV || o.type == OP_BNACT) && n->T[o.in].buf == (int)b) {
-                    const TensorD &t = n->T[o.in];
-                    ncons++;
-                    if (o.type != OP_BNACT || o.in_grad_mode != 1 || t.coff != 0 || t.C != n->B[b].width) ok = false;
-                }
-            }
-            if (ok && nprod == 1 && ncons == 1) n->gbf[b] = 1;
-        }
-    }
-    // The same for the gradient of an ACTIVATION buffer (BatchNorm -> ReLU output, bf16 in the forward): written once by the data
-    // gradient of the one convolution that reads the activation, read once by that BatchNorm's backward.  The convolution's epilogue
-    // takes the BatchNorm-backward partial sums from the unrounded values and stores bf16 (D3_CONV_OUTBF16); the apply pass reads 2
-    // bytes per element instead of 4.  Round 4 measured it neutral (the BatchNorm backward was bound by its reduction of the partial
-    // table then) and left it off; with the second-level tables and the lane-table data gradient it is worth 3 - 7 % on both kernels of
-    // levels 0 - 1 (rocprofv3, gpurun_out/r06_j34: 20.4 -> 19.4 us and 25.7 -> 24.0 us) and 0.7 GB less traffic per backward: on since round 6.
     n->gabf.assign(n->B.size(), 0);
-    {
-        const bool on = !n->f32;
-        for (size_t b = 0; on && b < n->B.size(); b++) {
-            if (n->galias[b] >= 0 || n->gbf[b]) continue;
-            if (n->out_tensor >= 0 && n->T[n->out_tensor].buf == (int)b) continue;
-            bool ok = n->B[b].dtype == 1;
-            for (size_t x = 0; x < n->B.size(); x++)
-                if (n->galias[x] >= 0 && n->T[n->galias[x]].buf == (int)b) ok = false;
-            int nprod = 0, ncons = 0;
-            for (auto &o : n->ops) {
-                if (o.type == OP_PADCAST && n->T[o.out].buf == (int)b) ok = false;
-                if (o.type == OP_STATS) continue;
-                if (o.type == OP_CONV && o.res >= 0 && n->T[o.res].buf == (int)b) ok = false;
-                if ((o.type == OP_CONV || o.type == OP_BNACT) && n->T[o.out].buf == (int)b) {
-                    const TensorD &t = n->T[o.out];
-                    nprod++;
-                    if (o.type != OP_BNACT || t.coff != 0 || t.C != n->B[b].width || (t.C & 7)) ok = false;
-                }
-                if ((o.type == OP_CONV || o.type == OP_BNACT) && n->T[o.in].buf == (int)b) {
-                    const TensorD &t = n->T[o.in];
-                    ncons++;
-                    if (o.type != OP_CONV || o.in_grad_mode != 1 || t.coff != 0 || t.C != n->B[b].width || o.CinW != t.C) ok = false;
-                }
-            }
-            if (ok && nprod == 1 && ncons == 1) n->gabf[b] = 1;
+    for (int b = 0; b < (int)n->B.size(); b++) {
+        // Gradients with a single writer and a single reader pair are stored as bf16: the output gradient of a convolution whose
+        // output feeds exactly one BatchNorm (the first conv of every residual block) is written once by that BatchNorm's backward
+        // apply and read only by the convolution's own data- and weight-gradient kernels -- as MFMA operands, i.e. rounded to bf16
+        // on load anyway.  Rounding at the store instead is numerically identical and halves the bytes of the data gradient's
+        // 27-fold gather and of the weight gradient's dy operand.  D3_GRAD_BF16=0 keeps them in fp32 (A/B measurements).
+        if (grad_bf16 && single_writer_reader(n, facts, b, OP_CONV, OP_BNACT)) n->gbf[b] = 1;
+        // The same for the gradient of an ACTIVATION buffer (BatchNorm -> ReLU output, bf16 in the forward): written once by the data
+        // gradient of the one convolution that reads the activation, read once by that BatchNorm's backward.  The convolution's epilogue
+        // takes the BatchNorm-backward partial sums from the unrounded values and stores bf16 (D3_CONV_OUTBF16); the apply pass reads 2
+        // bytes per element instead of 4.  Round 4 measured it neutral (the BatchNorm backward was bound by its reduction of the partial
+        // table then) and left it off; with the second-level tables and the lane-table data gradient it is worth 3 - 7 % on both kernels of
+        // levels 0 - 1 (rocprofv3, gpurun_out/r06_j34: 20.4 -> 19.4 us and 25.7 -> 24.0 us) and 0.7 GB less traffic per backward: on since round 6.
+        else if (!n->f32 && n->B[b].dtype == 1 && single_writer_reader(n, facts, b, OP_BNACT, OP_CONV)) n->gabf[b] = 1;
+    }
+    n->gv.assign(n->T.size() + n->B.size(), GradView());
+    for (int t = 0; t < (int)n->T.size(); t++) n->gv[t] = grad_view(n, t);
+    // which convolutions' output gradients are written in place after their weight gradient was issued?
+    for (int i = 0; i < (int)n->ops.size(); i++) {
+        OpD &o = n->ops[i];
+        if (o.type != OP_CONV) continue;
+        const int r = n->gv[o.out].root;
+        if (r < 0) continue;
+        for (int j = i - 1; j >= 0 && !o.wg_hazard; j--) {   // ops processed after op i in the backward
+            const OpD &q = n->ops[j];
+            if ((q.type == OP_CONV || q.type == OP_BNACT) && q.in_grad_mode == 2 && n->gv[q.in].root == r) o.wg_hazard = 1;
+            if (q.type == OP_CONV && q.res_mode == 2 && n->gv[q.res].root == r) o.wg_hazard = 1;
         }
     }
     // Residual-stream gradients stay fp32 (they are accumulated in place and feed fp32 consumers), but the convolution that
@@ -894,51 +887,50 @@ extern "C" void *d3_net_create(const int64_t *prog, int nops, const int64_t *ten
     // residual block adding its contribution), that kernel also writes the finished values as bf16 into a shadow buffer and
     // the convolution's data- and weight-gradient kernels read the shadow: identical operands, half the gathered bytes.
     n->gshadow.assign(n->B.size(), 0);
-    n->gshadow_off.assign(n->B.size(), 0);
     {
-        const bool on = d3_tune(D3T_GRAD_BF16) != 0 && !n->f32;
-        auto root_of = [&](int tensor, int &coff, int &C) {          // as gptr(): follow residual aliases
-            const TensorD *t = &n->T[tensor];
-            coff = t->coff; C = t->C;
-            for (int guard = 0; guard < 1000; guard++) {
-                if (t->buf < 0) return -1;
-                if (tensor == n->out_tensor) return -2;
-                if (n->galias[t->buf] < 0) return t->buf;
-                tensor = n->galias[t->buf];
-                t = &n->T[tensor];
-                coff = t->coff;
-            }
-            return -3;
-        };
         // root buffer -> (BNACT op whose apply was the last writer of the buffer, column window it wrote) or op -1.  A window is
         // the whole buffer (residual streams) or one column half of a concatenation buffer's gradient (the skip connection:
         // its last writer is the BatchNorm in front of the stride-2 convolution, accumulating into the left half only).
         struct LastBn { int op, coff, C; };
         std::map<int, LastBn> last_bn;
-        for (int i = (int)n->ops.size() - 1; on && i >= 0; i--) {
+        for (int i = (int)n->ops.size() - 1; grad_bf16 && i >= 0; i--) {
             OpD &o = n->ops[i];
-            int coff, C;
             if (o.type == OP_CONV) {
-                const int ro = root_of(o.out, coff, C);
+                const GradView &vo = n->gv[o.out];
+                const int ro = vo.root, C = n->T[o.out].C;
                 if (ro >= 0 && !n->gbf[ro] && !(C & 7)) {
                     auto it = last_bn.find(ro);
-                    if (it != last_bn.end() && it->second.op >= 0 && it->second.coff == coff && it->second.C == C &&
+                    if (it != last_bn.end() && it->second.op >= 0 && it->second.coff == vo.coff && it->second.C == C &&
                         (!n->gshadow[ro] || n->gshadow[ro] == C)) {       // (one shadow window per buffer)
                         o.use_shadow = 1; n->ops[it->second.op].write_shadow = 1; n->gshadow[ro] = C;
                     }
                 }
-                if (o.in_grad_mode) { const int ri = root_of(o.in, coff, C); if (ri >= 0) last_bn[ri] = LastBn{-1, 0, 0}; }
-                if (o.res >= 0 && o.res_mode >= 2) { const int rr = root_of(o.res, coff, C); if (rr >= 0) last_bn[rr] = LastBn{-1, 0, 0}; }
+                if (o.in_grad_mode) { const int ri = n->gv[o.in].root; if (ri >= 0) last_bn[ri] = LastBn{-1, 0, 0}; }
+                if (o.res >= 0 && o.res_mode >= 2) { const int rr = n->gv[o.res].root; if (rr >= 0) last_bn[rr] = LastBn{-1, 0, 0}; }
             } else if (o.type == OP_BNACT && o.in_grad_mode) {
-                const int ri = root_of(o.in, coff, C);
-                if (ri >= 0) last_bn[ri] = n->gbf[ri] ? LastBn{-1, 0, 0} : LastBn{i, coff, C};
+                const GradView &vi = n->gv[o.in];
+                if (vi.root >= 0) last_bn[vi.root] = n->gbf[vi.root] ? LastBn{-1, 0, 0} : LastBn{i, vi.coff, n->T[o.in].C};
             }
         }
     }
+    for (size_t b = 0; b < n->B.size(); b++)      // the shadows' views: dense (M, C) bf16
+        if (n->gshadow[b]) { GradView &v = n->gv[n->T.size() + b]; v.root = (int)b; v.ld = n->gshadow[b]; v.bf16 = 1; }
+    // every convolution's calls: what the launchers pass and what d3_net_plan sizes the weight-gradient partials from
+    for (auto &o : n->ops) {
+        if (o.type != OP_CONV) continue;
+        const TensorD &ti = n->T[o.in], &to = n->T[o.out];
+        o.dy_view = o.use_shadow ? (int)n->T.size() + n->gv[o.out].root : o.out;
+        const int pf = n->f32 ? D3_CONV_F32 : 0, xbf = ti.dtype == 1 ? D3_CONV_XBF16 : 0, dybf = n->gv[o.dy_view].bf16;
+        o.fwd_flags = xbf | pf | (to.dtype == 1 ? D3_CONV_OUTBF16 : 0);
+        if (o.in_grad_mode) o.dgrad_flags = (dybf ? D3_CONV_XBF16 : 0) | pf | (n->gv[o.in].bf16 ? D3_CONV_OUTBF16 : 0);
+        o.wgrad_flags = xbf | (dybf ? D3_CONV_DYBF16 : 0) | pf;
+        if (o.Cin > o.Cout) o.wgrad_flags |= D3_CONV_XSTAT | (o.map == MAP_K3 ? D3_CONV_FLIPK : 0);
+        o.k3_tables = o.map == MAP_K3 ? 1 : 0;
+    }
     {   // weight gradients run on their own (plain-priority) streams.  A lowest-priority stream won 0.3 ms in round 2 and was starved once
         // the process owned more streams in round 3 (18.3 -> 21.7 ms per step): plain it is
-        hipStreamCreateWithFlags(&n->side, hipStreamNonBlocking);
-        hipStreamCreateWithFlags(&n->side2, hipStreamNonBlocking);
+        hipStreamCreateWithFlags(&n->run.side, hipStreamNonBlocking);
+        hipStreamCreateWithFlags(&n->run.side2, hipStreamNonBlocking);
     }
     return n;
 }
@@ -946,14 +938,15 @@ extern "C" void *d3_net_create(const int64_t *prog, int nops, const int64_t *ten
 extern "C" void d3_net_destroy(void *h) {
     Net *n = (Net *)h;
     if (!n) return;
-    if (n->jobs_dev) hipFree(n->jobs_dev);
-    if (n->red_host) hipHostFree(n->red_host);
-    if (n->red_dev) hipFree(n->red_dev);
-    for (auto e : n->ev) hipEventDestroy(e);
-    for (auto e : n->chunk_ev_side) hipEventDestroy(e);
-    for (auto e : n->chunk_ev_main) hipEventDestroy(e);
-    if (n->side) hipStreamDestroy(n->side);
-    if (n->side2) hipStreamDestroy(n->side2);
+    NetRun &r = n->run;
+    if (r.jobs_dev) hipFree(r.jobs_dev);
+    if (r.red_host) hipHostFree(r.red_host);
+    if (r.red_dev) hipFree(r.red_dev);
+    for (auto e : r.ev) hipEventDestroy(e);
+    for (auto e : r.chunk_ev_side) hipEventDestroy(e);
+    for (auto e : r.chunk_ev_main) hipEventDestroy(e);
+    if (r.side) hipStreamDestroy(r.side);
+    if (r.side2) hipStreamDestroy(r.side2);
     delete n;
 }
 
@@ -967,24 +960,26 @@ extern "C" int d3_net_set_chunks(void *h, const int *op_idx, int nchunks) {
     for (int k = 0; k < nchunks; k++) {
         if (op_idx[k] < 0 || op_idx[k] >= (int)n->ops.size() || (k > 0 && op_idx[k] >= op_idx[k - 1])) return D3_ERR_ARG;
     }
-    n->chunk_op.assign(op_idx, op_idx + nchunks);
-    while ((int)n->chunk_ev_side.size() < nchunks) {
+    NetRun &r = n->run;
+    r.chunk_op.assign(op_idx, op_idx + nchunks);
+    while ((int)r.chunk_ev_side.size() < nchunks) {
         hipEvent_t a, b;
         D3_CHECK(hipEventCreateWithFlags(&a, hipEventDisableTiming));
         D3_CHECK(hipEventCreateWithFlags(&b, hipEventDisableTiming));
-        n->chunk_ev_side.push_back(a); n->chunk_ev_main.push_back(b);
+        r.chunk_ev_side.push_back(a); r.chunk_ev_main.push_back(b);
     }
     return 0;
 }
 extern "C" int d3_net_set_k3_16(void *h, const void *const *k3_16, const int *const *ok16) {
     Net *n = (Net *)h;
     if (!n) return D3_ERR_ARG;
-    n->k3_16.assign((size_t)n->nlevels, nullptr);
-    n->k3_q.assign((size_t)n->nlevels, nullptr);
+    NetRun &r = n->run;
+    r.k3_16.assign((size_t)n->nlevels, nullptr);
+    r.k3_q.assign((size_t)n->nlevels, nullptr);
     if (d3_tune(D3T_KMAP16) != 0 && !n->f32)
         for (int l = 0; l < n->nlevels; l++) {
-            if (k3_16 && k3_16[l]) n->k3_16[(size_t)l] = k3_16[l];
-            if (ok16 && ok16[l]) n->k3_q[(size_t)l] = (const void *)ok16[l];      // (second array: the lane tables, round 6)
+            if (k3_16 && k3_16[l]) r.k3_16[(size_t)l] = k3_16[l];
+            if (ok16 && ok16[l]) r.k3_q[(size_t)l] = (const void *)ok16[l];      // (second array: the lane tables, round 6)
         }
     return 0;
 }
@@ -1011,15 +1006,15 @@ extern "C" int d3_net_padcast(void *h, const void *input, void *out, long long M
 extern "C" int d3_net_set_padded_input(void *h, const void *xp) {
     Net *n = (Net *)h;
     if (!n) return D3_ERR_ARG;
-    n->xp_ext = d3_net_padded_channels(h) > 0 ? xp : nullptr;
+    n->run.xp_ext = d3_net_padded_channels(h) > 0 ? xp : nullptr;
     return 0;
 }
 // make `stream` wait until chunk k of the LAST d3_net_backward call is complete (its events were recorded by that call)
 extern "C" int d3_net_chunk_wait(void *h, int k, void *stream) {
     Net *n = (Net *)h;
-    if (!n || k < 0 || k >= (int)n->chunk_op.size()) return D3_ERR_ARG;
-    D3_CHECK(hipStreamWaitEvent(d3_stream(stream), n->chunk_ev_side[k], 0));
-    D3_CHECK(hipStreamWaitEvent(d3_stream(stream), n->chunk_ev_main[k], 0));
+    if (!n || k < 0 || k >= (int)n->run.chunk_op.size()) return D3_ERR_ARG;
+    D3_CHECK(hipStreamWaitEvent(d3_stream(stream), n->run.chunk_ev_side[k], 0));
+    D3_CHECK(hipStreamWaitEvent(d3_stream(stream), n->run.chunk_ev_main[k], 0));
     return 0;
 }
 
@@ -1036,41 +1031,46 @@ static void conv_dims(const Net *n, const OpD &o, int &Min, int &Mout) {
     Min = n->rows[n->T[o.in].level]; Mout = n->rows[n->T[o.out].level];
 }
 
+static inline void place(Region &r, size_t &cursor, size_t bytes) { r.off = cursor; r.bytes = d3_align(bytes); cursor += r.bytes; }
+
 // rows[nlevels] -> arena / gradient-arena / workspace sizes; offsets are fixed until the next plan
 extern "C" int d3_net_plan(void *h, const int *rows, size_t *arena_bytes, size_t *grad_bytes) {
     Net *n = (Net *)h;
     n->rows.assign(rows, rows + n->nlevels);
     size_t off = 0, goff = 0;
-    for (auto &b : n->B) {
-        b.off = off; off += d3_align((size_t)n->rows[b.level] * b.width * esize(b.dtype));
-        const size_t bi = &b - &n->B[0];
-        b.goff = goff; if (b.need_grad) goff += d3_align((size_t)n->rows[b.level] * b.width * ((n->gbf[bi] || n->gabf[bi]) ? 2 : 4));
-        if (n->gshadow[bi]) { n->gshadow_off[bi] = goff; goff += d3_align((size_t)n->rows[b.level] * n->gshadow[bi] * 2); }
+    for (size_t bi = 0; bi < n->B.size(); bi++) {
+        BufD &b = n->B[bi];
+        const size_t elems = (size_t)n->rows[b.level] * b.width;
+        place(b.act, off, elems * esize(b.dtype));
+        place(b.grad, goff, b.need_grad ? elems * ((n->gbf[bi] || n->gabf[bi]) ? 2 : 4) : 0);
+        if (n->gshadow[bi]) place(b.shadow, goff, (size_t)n->rows[b.level] * n->gshadow[bi] * 2);
     }
-    size_t bnscr = 0, wgws = 16;
+    for (size_t t = 0; t < n->gv.size(); t++) {
+        GradView &v = n->gv[t];
+        if (t >= n->T.size()) v.off = n->B[t - n->T.size()].shadow.off;
+        else if (v.kind == GV_ARENA) v.off = n->B[v.root].grad.off + (size_t)v.coff * (v.bf16 ? 2 : 4);
+    }
+    const int pf = n->f32 ? D3_CONV_F32 : 0;
+    size_t bnscr = 0;
     for (auto &o : n->ops) {
         if (o.type == OP_CONV) {
             int Min, Mout; conv_dims(n, o, Min, Mout);
-            const int pf = n->f32 ? D3_CONV_F32 : 0;
-            o.wp_fwd = off; off += d3_align(d3_spconv_pack_bytes_ex(o.K, o.Cin, o.Cout, pf));
-            o.wp_bwd = off; if (o.needs_dgrad_pack) off += d3_align(d3_spconv_pack_bytes_ex(o.K, o.Cout, o.Cin, pf));
+            place(o.wp_fwd, off, d3_spconv_pack_bytes_ex(o.K, o.Cin, o.Cout, pf));
+            place(o.wp_bwd, off, o.needs_dgrad_pack ? d3_spconv_pack_bytes_ex(o.K, o.Cout, o.Cin, pf) : 0);
             if (o.stats) {
-                o.nparts = d3_spconv_fwd2_nparts_ex(Mout, o.K, o.Cin, o.Cout, pf);
+                o.nparts_max = d3_spconv_fwd2_nparts_ex(Mout, o.K, o.Cin, o.Cout, pf);
                 o.partw = (o.Cout + 15) / 16 * 16;
-                o.part_off = off; off += d3_align((size_t)o.nparts * 2 * o.partw * 4);
+                place(o.part, off, (size_t)o.nparts_max * 2 * o.partw * 4);
             }
-            const int xstat = ((o.Cin > o.Cout) ? D3_CONV_XSTAT : 0) | (n->T[o.in].dtype == 1 ? D3_CONV_XBF16 : 0) |
-                              ((n->T[o.out].buf >= 0 && n->gbf[n->T[o.out].buf]) || o.use_shadow ? D3_CONV_DYBF16 : 0) |
-                              (n->f32 ? D3_CONV_F32 : 0);   // as in d3_net_backward
-            o.wsplits = d3_spconv_wgrad2_splits(Min, Mout, o.K, o.Cin, o.Cout, xstat);
-            o.wpart_bytes = d3_align((size_t)o.wsplits * o.K * o.Cin * o.Cout * 4 + 256);
+            o.wsplits = d3_spconv_wgrad2_splits(Min, Mout, o.K, o.Cin, o.Cout, o.wgrad_flags);
+            o.wpart.bytes = d3_align((size_t)o.wsplits * o.K * o.Cin * o.Cout * 4 + 256);
         } else if (o.type == OP_STATS) {
             const TensorD &t = n->T[o.in];
-            o.nparts = bn_blocks2(n->rows[t.level], t.C); o.partw = t.C;
-            o.part_off = off; off += d3_align((size_t)o.nparts * 2 * t.C * 4);
+            o.nparts_max = bn_blocks2(n->rows[t.level], t.C); o.partw = t.C;
+            place(o.part, off, (size_t)o.nparts_max * 2 * t.C * 4);
         } else if (o.type == OP_BNACT) {
             const TensorD &t = n->T[o.in];
-            o.state_off = off; off += d3_align((size_t)4 * t.C * 4);   // mean, var, bwd sums (2C)
+            place(o.state, off, (size_t)4 * t.C * 4);   // mean, var, bwd sums (2C)
             const size_t s = (size_t)bn_blocks2(n->rows[t.level], t.C) * 2 * t.C * 4;
             if (s > bnscr) bnscr = s;
         }
@@ -1079,27 +1079,26 @@ extern "C" int d3_net_plan(void *h, const int *rows, size_t *arena_bytes, size_t
         if (o.type != OP_BNACT || o.fused_by < 0) continue;
         const OpD &cv = n->ops[o.fused_by];
         int Min, Mout; conv_dims(n, cv, Min, Mout);
-        o.bparts = d3_spconv_fwd2_nparts_ex(Min, cv.K, cv.Cout, cv.CinW, n->f32 ? D3_CONV_F32 : 0);
-        o.bpart_off = goff; goff += d3_align((size_t)o.bparts * 2 * ((cv.CinW + 15) / 16 * 16) * 4);
+        o.bparts_max = d3_spconv_fwd2_nparts_ex(Min, cv.K, cv.Cout, cv.CinW, pf);
+        place(o.bpart, goff, (size_t)o.bparts_max * 2 * ((cv.CinW + 15) / 16 * 16) * 4);
     }
-    for (auto &o : n->ops) if (o.type == OP_CONV) { o.wpart_off = goff; goff += o.wpart_bytes; }
+    for (auto &o : n->ops) if (o.type == OP_CONV) { o.wpart.off = goff; goff += o.wpart.bytes; }
     n->cnt_off0 = off;
     off = d3_align(off);
     // second-level partial tables (round 5) live in the same zeroed-once-per-call region as the ticket counters: no extra fill launch
     for (auto &o : n->ops)
-        if ((o.type == OP_CONV || o.type == OP_STATS) && o.nparts > 0) { o.part2_off = off; off += d3_align((size_t)D3_P2_ROWS * 2 * o.partw * 8); }
+        if ((o.type == OP_CONV || o.type == OP_STATS) && o.nparts_max > 0) place(o.part2, off, (size_t)D3_P2_ROWS * 2 * o.partw * 8);
     n->cnt_bytes = off - n->cnt_off0;
     n->bcnt_off0 = goff;
     goff = d3_align(goff);
     for (auto &o : n->ops) {
         if (o.type != OP_BNACT || o.fused_by < 0) continue;
-        const OpD &cv = n->ops[o.fused_by];
-        o.bpart2_off = goff; goff += d3_align((size_t)D3_P2_ROWS * 2 * ((cv.CinW + 15) / 16 * 16) * 8);
+        place(o.bpart2, goff, (size_t)D3_P2_ROWS * 2 * ((n->ops[o.fused_by].CinW + 15) / 16 * 16) * 8);
     }
     n->bcnt_bytes = goff - n->bcnt_off0;
     n->arena_bytes = off;
-    n->bnscr_off = goff; goff += d3_align(bnscr); n->bnscr_bytes = bnscr;
-    n->wgws_off = goff; goff += d3_align(wgws); n->wgws_bytes = wgws;
+    place(n->bnscr, goff, bnscr);
+    place(n->wgws, goff, 16);
     n->grad_bytes = goff;
     n->planned = true;
     *arena_bytes = n->arena_bytes; *grad_bytes = n->grad_bytes;
@@ -1110,48 +1109,94 @@ extern "C" long long d3_net_tensor_offset(void *h, int tensor) {
     Net *n = (Net *)h;
     const TensorD &t = n->T[tensor];
     if (t.buf < 0) return -1;
-    return (long long)(n->B[t.buf].off + (size_t)t.coff * esize(t.dtype));
+    return (long long)(n->B[t.buf].act.off + (size_t)t.coff * esize(t.dtype));
+}
+
+// The plan as numbers (include/d3hip.h names the records; d3net_amd/netexec.py the fields): pure host code
+extern "C" long long d3_net_describe(void *h, int64_t *out, long long cap) {
+    const Net *n = (const Net *)h;
+    if (!n) return 0;
+    constexpr int HW = 20, OW = 45, TW = 6, BW = 11;
+    const long long total = HW + (long long)n->ops.size() * OW + (long long)n->T.size() * TW + (long long)n->B.size() * BW;
+    if (!out || cap < total) return total;
+    const bool pl = n->planned;
+    int64_t *w = out;
+    auto put = [&](std::initializer_list<int64_t> v) { for (int64_t x : v) *w++ = x; };
+    auto region = [&](const Region &r) { put({(int64_t)(pl ? r.off : 0), (int64_t)(pl ? r.bytes : 0)}); };
+    put({1, (int64_t)n->ops.size(), (int64_t)n->T.size(), (int64_t)n->B.size(), n->nlevels, pl ? 1 : 0, OW, TW, BW, n->f32 ? 1 : 0,
+         (int64_t)n->arena_bytes, (int64_t)n->grad_bytes, (int64_t)n->cnt_off0, (int64_t)n->cnt_bytes, (int64_t)n->bcnt_off0, (int64_t)n->bcnt_bytes});
+    region(n->bnscr); region(n->wgws);
+    for (auto &o : n->ops) {
+        put({o.type, o.in_grad_mode, o.res_mode, o.needs_dgrad_pack, o.bn_of_in, o.fused_by, o.wg_hazard, o.use_shadow, o.write_shadow, (int64_t)o.srcs.size()});
+        for (size_t q = 0; q < 2; q++) {
+            if (q < o.srcs.size()) put({o.srcs[q].op, o.srcs[q].c0, o.srcs[q].cn});
+            else put({-1, 0, 0});
+        }
+        put({o.fwd_flags, o.dgrad_flags, o.wgrad_flags, (o.wgrad_flags & D3_CONV_XSTAT) ? 1 : 0, (o.wgrad_flags & D3_CONV_FLIPK) ? 1 : 0, o.k3_tables, o.Cin, o.Cout, o.dy_view});
+        put({pl ? o.wsplits : 0, pl ? o.nparts_max : 0, pl ? o.bparts_max : 0, pl ? o.partw : 0});
+        region(o.wp_fwd); region(o.wp_bwd); region(o.part); region(o.part2); region(o.state); region(o.bpart); region(o.bpart2); region(o.wpart);
+    }
+    for (size_t t = 0; t < n->T.size(); t++) {
+        const GradView &v = n->gv[t];
+        put({v.kind, v.root, v.ld, v.coff, v.bf16, (pl && v.kind == GV_ARENA) ? (int64_t)v.off : -1});
+    }
+    for (size_t b = 0; b < n->B.size(); b++) {
+        put({n->galias[b], n->gbf[b], n->gabf[b], n->gshadow[b], n->B[b].need_grad});
+        region(n->B[b].act); region(n->B[b].grad); region(n->B[b].shadow);
+    }
+    return total;
 }
 
 struct Maps { const int *const *k3; const int *const *child; const int *const *up; };
 
-static void conv_tables(const OpD &o, const Maps &m, const int *&tf, const int *&tb, int &bwd_flip) {
-    tf = tb = nullptr; bwd_flip = 0;
-    if (o.map == MAP_K3) { tf = tb = m.k3[o.mlevel]; bwd_flip = 1; }
+static void conv_tables(const OpD &o, const Maps &m, const int *&tf, const int *&tb) {
+    tf = tb = nullptr;
+    if (o.map == MAP_K3) tf = tb = m.k3[o.mlevel];
     else if (o.map == MAP_DOWN) { tf = m.child[o.mlevel]; tb = m.up[o.mlevel]; }
     else if (o.map == MAP_UP) { tf = m.up[o.mlevel]; tb = m.child[o.mlevel]; }
 }
 
-static inline char *tptr(const Net *n, char *arena, const void *input, int tensor) {
+static inline char *tptr(const Net *n, const NetRun &r, char *arena, const void *input, int tensor) {
     const TensorD &t = n->T[tensor];
     if (t.buf < 0) return (char *)input;
-    if (tensor == n->xp_tensor && n->xp_ext) return (char *)n->xp_ext;      // (prepared outside the call: d3_net_set_padded_input)
-    return arena + n->B[t.buf].off + (size_t)t.coff * esize(t.dtype);
+    if (tensor == n->xp_tensor && r.xp_ext) return (char *)r.xp_ext;      // (prepared outside the call: d3_net_set_padded_input)
+    return arena + n->B[t.buf].act.off + (size_t)t.coff * esize(t.dtype);
+}
+
+// where a gradient view points in this call
+static inline float *gptr(const GradView &v, char *garena, const float *gout, float *gin) {
+    return v.kind == GV_GIN ? gin : v.kind == GV_GOUT ? (float *)gout : (float *)(garena + v.off);
+}
+
+// The optional tables of one call of convolution `o` -- forward, data gradient or weight gradient (which reads tbl16 only).  `partials`:
+// the call writes BatchNorm partial rows; the lane-table kernel takes those only through the second-level table (`use_p2`: D3_BN_PART2,
+// read per call), which `part2` is then.
+static ConvExtras conv_extras(const NetRun &r, const OpD &o, bool partials, bool use_p2, char *part2) {
+    ConvExtras ex;
+    if (o.k3_tables && (size_t)o.mlevel < r.k3_16.size()) {
+        ex.tbl16 = r.k3_16[(size_t)o.mlevel];
+        if (use_p2 || !partials) ex.tblq = r.k3_q[(size_t)o.mlevel];
+    }
+    if (partials && use_p2) ex.part2 = (double *)part2;
+    return ex;
 }
 
 // The 16-bit tables handed over by d3_net_set_k3_16 serve exactly ONE forward or backward call (a caller that freed
 // its coordinate manager and ran again without re-setting them read freed tables): every return path of the two entry points
 // drops them.
-static void net_drop_k3_16(Net *n) {
-    if (n) { n->k3_16.assign(n->k3_16.size(), nullptr); n->k3_q.assign(n->k3_q.size(), nullptr); n->xp_ext = nullptr; }
+static void net_drop_k3_16(NetRun &r) {
+    r.k3_16.assign(r.k3_16.size(), nullptr); r.k3_q.assign(r.k3_q.size(), nullptr); r.xp_ext = nullptr;
 }
-static int net_forward_impl(void *h, const void *const *params, const int *const *k3, const int *const *child,
-                            const int *const *up, const void *input, void *arena_, int training, void *stream);
-extern "C" int d3_net_forward(void *h, const void *const *params, const int *const *k3, const int *const *child,
-                              const int *const *up, const void *input, void *arena_, int training, void *stream) {
-    if (!h) return D3_ERR_ARG;
-    const int rc = net_forward_impl(h, params, k3, child, up, input, arena_, training, stream);
-    net_drop_k3_16((Net *)h);
-    return rc;
-}
-static int net_forward_impl(void *h, const void *const *params, const int *const *k3, const int *const *child,
+static int net_forward_impl(const Net *n, NetRun &r, const void *const *params, const int *const *k3, const int *const *child,
                             const int *const *up, const void *input, void *arena_, int training, void *stream) {
     D3_CLEAR();
-    Net *n = (Net *)h;
     if (!n->planned) return D3_ERR_ARG;
     hipStream_t s = d3_stream(stream);
     char *arena = (char *)arena_;
     Maps maps{k3, child, up};
+    auto tp = [&](int tensor) { return tptr(n, r, arena, input, tensor); };
+    std::vector<int> nparts(n->ops.size());      // partial rows each producer wrote in THIS call (the kernel depends on the tables at hand)
+    for (size_t i = 0; i < n->ops.size(); i++) nparts[i] = n->ops[i].nparts_max;
     if (training && n->cnt_bytes) D3_CHECK(hipMemsetAsync(arena + n->cnt_off0, 0, n->cnt_bytes, s));
     const bool use_p2 = training && d3_tune(D3T_BN_PART2) != 0;      // second-level fp64 partial tables (zeroed with the counters above)
     // ---- all weights -> bf16 fragment order, one launch
@@ -1165,7 +1210,7 @@ static int net_forward_impl(void *h, const void *const *params, const int *const
                 PackJob j;
                 memset(&j, 0, sizeof(j));   // padding bytes too: the job table is compared with memcmp
                 j.W = (const float *)params[o.w];
-                j.dst_off = (dir == 0 ? o.wp_fwd : o.wp_bwd);
+                j.dst_off = (dir == 0 ? o.wp_fwd.off : o.wp_bwd.off);
                 j.K = o.K;
                 if (dir == 0) { j.Cin = o.Cin; j.S = o.Cin / 8; j.CinW = o.CinW; j.Cout = o.Cout; j.flipk = 0; j.transw = 0; }
                 else {   // data gradient: reduction over the layer's Cout, output = the layer's (real) Cin columns
@@ -1178,74 +1223,68 @@ static int net_forward_impl(void *h, const void *const *params, const int *const
                 jobs.push_back(j);
             }
         }
-        bool same = jobs.size() == n->jobs.size() && n->jobs_dev != nullptr &&
-                    memcmp(jobs.data(), n->jobs.data(), jobs.size() * sizeof(PackJob)) == 0;
+        bool same = jobs.size() == r.jobs.size() && r.jobs_dev != nullptr &&
+                    memcmp(jobs.data(), r.jobs.data(), jobs.size() * sizeof(PackJob)) == 0;
         if (!same) {
-            if (jobs.size() > n->jobs_cap) {
-                if (n->jobs_dev) D3_CHECK(hipFree(n->jobs_dev));
-                D3_CHECK(hipMalloc((void **)&n->jobs_dev, jobs.size() * sizeof(PackJob)));
-                n->jobs_cap = jobs.size();
+            if (jobs.size() > r.jobs_cap) {
+                if (r.jobs_dev) D3_CHECK(hipFree(r.jobs_dev));
+                D3_CHECK(hipMalloc((void **)&r.jobs_dev, jobs.size() * sizeof(PackJob)));
+                r.jobs_cap = jobs.size();
             }
-            D3_CHECK(hipMemcpyAsync(n->jobs_dev, jobs.data(), jobs.size() * sizeof(PackJob), hipMemcpyHostToDevice, s));
+            D3_CHECK(hipMemcpyAsync(r.jobs_dev, jobs.data(), jobs.size() * sizeof(PackJob), hipMemcpyHostToDevice, s));
             D3_CHECK(hipStreamSynchronize(s));   // the host vector is about to be replaced
-            n->jobs = jobs;
+            r.jobs = jobs;
         }
-        n->pack_total = start;
         if (start > 0) {
-            un_pack_batched_kernel<<<(int)((start + 255) / 256), 256, 0, s>>>(n->jobs_dev, (int)n->jobs.size(), start, arena);
+            un_pack_batched_kernel<<<(int)((start + 255) / 256), 256, 0, s>>>(r.jobs_dev, (int)r.jobs.size(), start, arena);
             D3_LAUNCH_CHECK();
         }
     }
-    for (auto &o : n->ops) {
+    for (size_t i = 0; i < n->ops.size(); i++) {
+        const OpD &o = n->ops[i];
         if (o.type == OP_PADCAST) {
-            if (n->xp_ext && n->xp_tensor >= 0 && &o == &n->ops[(size_t)n->xp_op]) continue;      // (the caller prepared it: input prefetch)
+            if (r.xp_ext && n->xp_tensor >= 0 && (int)i == n->xp_op) continue;      // (the caller prepared it: input prefetch)
             const TensorD &to = n->T[o.out];
             const long long M = n->rows[to.level];
             const int Cs = n->T[o.in].C;
             const long long total = M * (to.C / 2);
             if (to.dtype != 1) {
                 const long long tot32 = M * to.C;
-                if (tot32 > 0) un_padcast_f32_kernel<<<(int)((tot32 + 255) / 256), 256, 0, s>>>((const float *)input, (float *)tptr(n, arena, input, o.out), M, Cs, to.C);
+                if (tot32 > 0) un_padcast_f32_kernel<<<(int)((tot32 + 255) / 256), 256, 0, s>>>((const float *)input, (float *)tp(o.out), M, Cs, to.C);
             } else
-            if (total > 0) un_padcast_kernel<<<(int)((total + 255) / 256), 256, 0, s>>>((const float *)input, (unsigned short *)tptr(n, arena, input, o.out), M, Cs, to.C);
+            if (total > 0) un_padcast_kernel<<<(int)((total + 255) / 256), 256, 0, s>>>((const float *)input, (unsigned short *)tp(o.out), M, Cs, to.C);
         } else if (o.type == OP_STATS) {
             if (!training) continue;
             const TensorD &t = n->T[o.in];
             const int M = n->rows[t.level];
-            if (M > 0) un_stats_parts_kernel<<<o.nparts, UN_T, 0, s>>>((const float *)tptr(n, arena, input, o.in), t.ld, M, t.C, (float *)(arena + o.part_off),
-                                                                       use_p2 ? (double *)(arena + o.part2_off) : nullptr);
+            if (M > 0) un_stats_parts_kernel<<<o.nparts_max, UN_T, 0, s>>>((const float *)tp(o.in), t.ld, M, t.C, (float *)(arena + o.part.off),
+                                                                           use_p2 ? (double *)(arena + o.part2.off) : nullptr);
         } else if (o.type == OP_CONV) {
             const TensorD &ti = n->T[o.in], &to = n->T[o.out];
             int Min, Mout; conv_dims(n, o, Min, Mout);
-            const int *tf, *tb; int flip; conv_tables(o, maps, tf, tb, flip);
+            const int *tf, *tb; conv_tables(o, maps, tf, tb);
             const float *res = nullptr; int ldr = 0;
-            if (o.res >= 0) { res = (const float *)tptr(n, arena, input, o.res); ldr = n->T[o.res].ld; }
-            float *part = (o.stats && training) ? (float *)(arena + o.part_off) : nullptr;
-            ConvExtras ex;
-            if (o.map == MAP_K3 && (size_t)o.mlevel < n->k3_16.size()) {
-                ex.tbl16 = n->k3_16[(size_t)o.mlevel];
-                if (use_p2 || !part) ex.tblq = n->k3_q[(size_t)o.mlevel];
-            }
-            if (part && use_p2) ex.part2 = (double *)(arena + o.part2_off);
+            if (o.res >= 0) { res = (const float *)tp(o.res); ldr = n->T[o.res].ld; }
+            float *part = (o.stats && training) ? (float *)(arena + o.part.off) : nullptr;
+            const ConvExtras ex = conv_extras(r, o, part != nullptr, use_p2, arena + o.part2.off);
             int np = 0;
-            const int rc = d3_conv2_run(tptr(n, arena, input, o.in), ti.ld, tf, arena + o.wp_fwd, (float *)tptr(n, arena, input, o.out), to.ld,
-                                        res, ldr, part, Min, Mout, o.K, o.Cin, o.Cout, (ti.dtype == 1 ? D3_CONV_XBF16 : 0) | (n->f32 ? D3_CONV_F32 : 0) | (to.dtype == 1 ? D3_CONV_OUTBF16 : 0),
-                                        nullptr, ex, &np, stream);
+            const int rc = d3_conv2_run(tp(o.in), ti.ld, tf, arena + o.wp_fwd.off, (float *)tp(o.out), to.ld,
+                                        res, ldr, part, Min, Mout, o.K, o.Cin, o.Cout, o.fwd_flags, nullptr, ex, &np, stream);
             if (rc) return rc;
-            if (part) o.nparts = np;      // (rows actually written: the kernel depends on the tables at hand)
+            if (part) nparts[i] = np;
         } else if (o.type == OP_BNACT) {
             const TensorD &ti = n->T[o.in], &to = n->T[o.out];
             const int M = n->rows[ti.level], C = ti.C;
-            float *mean = (float *)(arena + o.state_off), *var = mean + C;
+            float *mean = (float *)(arena + o.state.off), *var = mean + C;
             const float *gamma = (const float *)params[o.gamma], *beta = (const float *)params[o.beta];
             const float *use_mean = mean, *use_var = var;
             if (training) {
                 if (o.srcs.empty() || o.srcs.size() > 2) return D3_ERR_ARG;
                 StatSrc ss[2];
                 for (size_t q = 0; q < 2; q++) {
-                    const SrcRef &r = o.srcs[q < o.srcs.size() ? q : 0];
-                    const OpD &p = n->ops[r.op];
-                    ss[q] = StatSrc{(const float *)(arena + p.part_off), p.nparts, p.partw, r.c0, r.cn, use_p2 ? (const double *)(arena + p.part2_off) : nullptr};
+                    const SrcRef &sr = o.srcs[q < o.srcs.size() ? q : 0];
+                    const OpD &p = n->ops[sr.op];
+                    ss[q] = StatSrc{(const float *)(arena + p.part.off), nparts[sr.op], p.partw, sr.c0, sr.cn, use_p2 ? (const double *)(arena + p.part2.off) : nullptr};
                 }
                 const int fs_rows = d3_tune(D3T_BN_FUSED_ROWS);
                 // (with the second-level tables the reduction is 16 rows whatever the producer's grid was: no size limit)
@@ -1255,8 +1294,8 @@ static int net_forward_impl(void *h, const void *const *params, const int *const
                     int G, rows_pb; un_fs_grid(M, C, G, rows_pb, M <= fs_rows ? 32 : 512);
                     float *rm = o.rmean >= 0 ? (float *)params[o.rmean] : nullptr, *rv = o.rvar >= 0 ? (float *)params[o.rvar] : nullptr;
 #define UN_FSF(OBFV, XBFV)                                                                                                             \
-                    un_bn_fused_small_kernel<OBFV, XBFV><<<G, UN_FS_T, 0, s>>>(ss[0], ss[1], (const float *)tptr(n, arena, input, o.in), ti.ld, gamma, beta, \
-                                                                              tptr(n, arena, input, o.out), to.ld, M, C, o.eps, o.relu, mean, var, rm, rv, o.momentum, rows_pb)
+                    un_bn_fused_small_kernel<OBFV, XBFV><<<G, UN_FS_T, 0, s>>>(ss[0], ss[1], (const float *)tp(o.in), ti.ld, gamma, beta, \
+                                                                              tp(o.out), to.ld, M, C, o.eps, o.relu, mean, var, rm, rv, o.momentum, rows_pb)
                     if (to.dtype == 1) { if (ti.dtype == 1) UN_FSF(true, true); else UN_FSF(true, false); }
                     else { if (ti.dtype == 1) UN_FSF(false, true); else UN_FSF(false, false); }
 #undef UN_FSF
@@ -1273,71 +1312,49 @@ static int net_forward_impl(void *h, const void *const *params, const int *const
             const long long total = (long long)M * (C / 4);
             if (total > 0) {
                 if (to.dtype == 1)
-                    un_bn_apply_kernel<true><<<un_ap_grid(M, C, 8), 256, 0, s>>>((const float *)tptr(n, arena, input, o.in), ti.ld, use_mean, use_var, gamma, beta,
-                                                                                     tptr(n, arena, input, o.out), to.ld, M, C, o.eps, o.relu, ti.dtype == 1 ? 1 : 0);
+                    un_bn_apply_kernel<true><<<un_ap_grid(M, C, 8), 256, 0, s>>>((const float *)tp(o.in), ti.ld, use_mean, use_var, gamma, beta,
+                                                                                     tp(o.out), to.ld, M, C, o.eps, o.relu, ti.dtype == 1 ? 1 : 0);
                 else
-                    un_bn_apply_kernel<false><<<un_ap_grid(M, C, 8), 256, 0, s>>>((const float *)tptr(n, arena, input, o.in), ti.ld, use_mean, use_var, gamma, beta,
-                                                                                      tptr(n, arena, input, o.out), to.ld, M, C, o.eps, o.relu, ti.dtype == 1 ? 1 : 0);
+                    un_bn_apply_kernel<false><<<un_ap_grid(M, C, 8), 256, 0, s>>>((const float *)tp(o.in), ti.ld, use_mean, use_var, gamma, beta,
+                                                                                      tp(o.out), to.ld, M, C, o.eps, o.relu, ti.dtype == 1 ? 1 : 0);
             }
         }
     }
     D3_LAUNCH_CHECK();
     return 0;
 }
-
-// gradient view of a tensor: (pointer, row stride); residual aliases are followed to their root
-static float *gptr(const Net *n, char *garena, const float *gout, float *gin, int tensor, int &ld, int &root, int *bf16 = nullptr) {
-    const TensorD *t = &n->T[tensor];
-    if (bf16) *bf16 = 0;
-    int coff = t->coff;
-    for (int guard = 0; guard < 1000; guard++) {
-        if (t->buf < 0) { ld = t->ld; root = -1; return gin; }
-        if (tensor == n->out_tensor) { ld = t->ld; root = -2; return (float *)gout; }
-        if (n->galias[t->buf] < 0) break;
-        tensor = n->galias[t->buf];
-        t = &n->T[tensor];
-        coff = t->coff;     // the aliased buffer is a whole-buffer view of the target tensor
-    }
-    ld = n->B[t->buf].width;
-    root = t->buf;
-    if (n->gbf[t->buf] || n->gabf[t->buf]) {          // (whole-buffer views only: coff == 0)
-        if (bf16) *bf16 = 1;
-        return (float *)(garena + n->B[t->buf].goff);
-    }
-    return (float *)(garena + n->B[t->buf].goff) + coff;
+extern "C" int d3_net_forward(void *h, const void *const *params, const int *const *k3, const int *const *child,
+                              const int *const *up, const void *input, void *arena_, int training, void *stream) {
+    Net *n = (Net *)h;
+    if (!n) return D3_ERR_ARG;
+    const int rc = net_forward_impl(n, n->run, params, k3, child, up, input, arena_, training, stream);
+    net_drop_k3_16(n->run);
+    return rc;
 }
 
 // gout: gradient of the output tensor (rows x C fp32, dense); pgrads[param]: where to write / accumulate the
 // parameter gradient (NULL = frozen); paccum[param] != 0 -> accumulate.  gin: gradient of the external input
 // (only when the network was created with input_needs_grad).
-static int net_backward_impl(void *h, const void *const *params, const int *const *k3, const int *const *child,
-                             const int *const *up, const void *input, void *arena_, void *garena_, const float *gout,
-                             float *const *pgrads, const int *paccum, float *gin, void *stream);
-extern "C" int d3_net_backward(void *h, const void *const *params, const int *const *k3, const int *const *child,
-                               const int *const *up, const void *input, void *arena_, void *garena_, const float *gout,
-                               float *const *pgrads, const int *paccum, float *gin, void *stream) {
-    if (!h) return D3_ERR_ARG;
-    const int rc = net_backward_impl(h, params, k3, child, up, input, arena_, garena_, gout, pgrads, paccum, gin, stream);
-    net_drop_k3_16((Net *)h);
-    return rc;
-}
-static int net_backward_impl(void *h, const void *const *params, const int *const *k3, const int *const *child,
+static int net_backward_impl(const Net *n, NetRun &r, const void *const *params, const int *const *k3, const int *const *child,
                              const int *const *up, const void *input, void *arena_, void *garena_, const float *gout,
                              float *const *pgrads, const int *paccum, float *gin, void *stream) {
     D3_CLEAR();
-    Net *n = (Net *)h;
     if (!n->planned) return D3_ERR_ARG;
     hipStream_t s = d3_stream(stream);
     char *arena = (char *)arena_, *garena = (char *)garena_;
     Maps maps{k3, child, up};
-    n->ev_used = 0;
+    auto tp = [&](int tensor) { return tptr(n, r, arena, input, tensor); };
+    auto gp = [&](const GradView &v) { return gptr(v, garena, gout, gin); };
+    std::vector<int> bparts(n->ops.size());      // per BNACT: partial rows the fusing convolution's data gradient wrote in THIS call
+    for (size_t i = 0; i < n->ops.size(); i++) bparts[i] = n->ops[i].bparts_max;
+    r.ev_used = 0;
     // Small networks (ScoreNet: a few thousand rows, every kernel ~5 us) are bound by host API calls: their weight
     // gradients stay on the caller's stream (no events).  Big ones use the side stream; the "a side-stream kernel still
     // reads this gradient buffer" hazard gets an event only for the convolutions whose output gradient is later
     // accumulated into in place (residual aliases: known from the program, OpD::wg_hazard).
     constexpr int kSideMinRows = 32768;      // level-0 rows from which the weight gradients run on the side streams
     const bool use_side = n->rows[0] >= kSideMinRows;
-    hipStream_t ws_stream = use_side ? n->side : s;
+    hipStream_t ws_stream = use_side ? r.side : s;
     std::map<int, hipEvent_t> pending;   // gradient buffer root -> event after its last side-stream reader
     bool side_used = false;
     bool main_wgrads = false;                               // ... and the batched reduction (side stream) is ordered behind them by one event
@@ -1348,7 +1365,7 @@ static int net_backward_impl(void *h, const void *const *params, const int *cons
     };
     if (n->bcnt_bytes) D3_CHECK(hipMemsetAsync(garena + n->bcnt_off0, 0, n->bcnt_bytes, s));
     const bool use_p2 = d3_tune(D3T_BN_PART2) != 0;
-    float *bnscr = (float *)(garena + n->bnscr_off);
+    float *bnscr = (float *)(garena + n->bnscr.off);
     std::vector<RedJob> red;
     long long red_blocks = 0;
     // row-split partials -> dW in batched launches on the weight-gradient stream: one when only the last few convolutions of
@@ -1356,14 +1373,14 @@ static int net_backward_impl(void *h, const void *const *params, const int *cons
     // end left its 137 us exposed behind the stem's weight gradient, after the caller's stream had nothing left to do
     // All weight gradients alternate between TWO side streams (speaker step 17.71 -> 17.49 ms in-process against one stream; only the
     // gradients whose dy buffer is later accumulated into in place on the second stream: 17.57; detector step inside the noise).
-    const bool use_side2 = use_side && n->side2;
+    const bool use_side2 = use_side && r.side2;
     bool side2_dirty = false;                               // side2 holds weight gradients the batched reduction / the join has not been ordered behind yet
     int side2_flip = 0;
     auto join_side2 = [&]() -> int {                        // ws_stream waits for everything enqueued on side2
         if (!side2_dirty) return 0;
-        hipEvent_t e = n->next_event();
+        hipEvent_t e = r.next_event();
         if (!e) return D3_ERR_OVERFLOW;
-        D3_CHECK(hipEventRecord(e, n->side2));
+        D3_CHECK(hipEventRecord(e, r.side2));
         D3_CHECK(hipStreamWaitEvent(ws_stream, e, 0));
         side2_dirty = false;
         return 0;
@@ -1372,22 +1389,22 @@ static int net_backward_impl(void *h, const void *const *params, const int *cons
         if (red.empty()) return 0;
         { int jrc = join_side2(); if (jrc) return jrc; }
         if (main_wgrads && use_side) {
-            hipEvent_t e = n->next_event();
+            hipEvent_t e = r.next_event();
             if (!e) return D3_ERR_OVERFLOW;
             D3_CHECK(hipEventRecord(e, s));
             D3_CHECK(hipStreamWaitEvent(ws_stream, e, 0));
             main_wgrads = false;
         }
-        if (red.size() > n->red_cap) {
+        if (red.size() > r.red_cap) {
             D3_CHECK(hipStreamSynchronize(ws_stream));   // (growing: nothing may still read the old tables -- BEFORE they are freed)
-            if (n->red_host) hipHostFree(n->red_host);
-            if (n->red_dev) hipFree(n->red_dev);
-            n->red_cap = red.size() + 16;
-            D3_CHECK(hipHostMalloc((void **)&n->red_host, RED_RING * n->red_cap * sizeof(RedJob)));
-            D3_CHECK(hipMalloc((void **)&n->red_dev, RED_RING * n->red_cap * sizeof(RedJob)));
+            if (r.red_host) hipHostFree(r.red_host);
+            if (r.red_dev) hipFree(r.red_dev);
+            r.red_cap = red.size() + 16;
+            D3_CHECK(hipHostMalloc((void **)&r.red_host, RED_RING * r.red_cap * sizeof(RedJob)));
+            D3_CHECK(hipMalloc((void **)&r.red_dev, RED_RING * r.red_cap * sizeof(RedJob)));
         }
-        n->red_flip = (n->red_flip + 1) % RED_RING;   // <= nchunks + 2 flushes per backward (d3_net_set_chunks bounds nchunks): a slot comes round again >= 2 backward calls later
-        RedJob *hj = n->red_host + (size_t)n->red_flip * n->red_cap, *dj = n->red_dev + (size_t)n->red_flip * n->red_cap;
+        r.red_flip = (r.red_flip + 1) % RED_RING;   // <= nchunks + 2 flushes per backward (d3_net_set_chunks bounds nchunks): a slot comes round again >= 2 backward calls later
+        RedJob *hj = r.red_host + (size_t)r.red_flip * r.red_cap, *dj = r.red_dev + (size_t)r.red_flip * r.red_cap;
         memcpy(hj, red.data(), red.size() * sizeof(RedJob));
         D3_CHECK(hipMemcpyAsync(dj, hj, red.size() * sizeof(RedJob), hipMemcpyHostToDevice, ws_stream));
         un_wgrad_reduce_batched_kernel<<<(int)red_blocks, 256, 0, ws_stream>>>(dj, (int)red.size());
@@ -1401,65 +1418,59 @@ static int net_backward_impl(void *h, const void *const *params, const int *cons
         if (n->ops[i].type == OP_CONV && pgrads[n->ops[i].w] != nullptr && ++c == kRedTail) { tail_idx = i; break; }
     size_t next_chunk = 0;
     auto chunk_done = [&](int i) -> int {      // op i has been processed: close every chunk that ends here
-        while (next_chunk < n->chunk_op.size() && n->chunk_op[next_chunk] >= i) {
+        while (next_chunk < r.chunk_op.size() && r.chunk_op[next_chunk] >= i) {
             int frc = flush_red(); if (frc) return frc;
             frc = join_side2(); if (frc) return frc;       // (weight gradients written straight to dW on the second side stream)
-            D3_CHECK(hipEventRecord(n->chunk_ev_side[next_chunk], ws_stream));
-            D3_CHECK(hipEventRecord(n->chunk_ev_main[next_chunk], s));
+            D3_CHECK(hipEventRecord(r.chunk_ev_side[next_chunk], ws_stream));
+            D3_CHECK(hipEventRecord(r.chunk_ev_main[next_chunk], s));
             next_chunk++;
         }
         return 0;
     };
     for (int i = (int)n->ops.size() - 1; i >= 0; i--) {
-        OpD &o = n->ops[i];
+        const OpD &o = n->ops[i];
         if (i < (int)n->ops.size() - 1) { int crc = chunk_done(i + 1); if (crc) return crc; }
         if (i == tail_idx) { int frc = flush_red(); if (frc) return frc; }
         if (o.type == OP_CONV) {
             const TensorD &ti = n->T[o.in];
             int Min, Mout; conv_dims(n, o, Min, Mout);
-            const int *tf, *tb; int flip; conv_tables(o, maps, tf, tb, flip);
-            int ldgo, root_o, gobf; float *go = gptr(n, garena, gout, gin, o.out, ldgo, root_o, &gobf);
-            float *go32 = go;                      // (the residual add below reads the fp32 buffer)
-            const int ldgo32 = ldgo;
-            if (o.use_shadow && root_o >= 0 && n->gshadow[root_o]) { go = (float *)(garena + n->gshadow_off[root_o]); gobf = 1; ldgo = n->gshadow[root_o]; }   // dense (M, C) bf16
+            const int *tf, *tb; conv_tables(o, maps, tf, tb);
+            const GradView &vo = n->gv[o.out], &vdy = n->gv[o.dy_view];      // (vdy: the bf16 shadow of vo where the op reads that)
+            const int root_o = vo.root, ldgo = vdy.ld;
+            float *go = gp(vdy);
             const bool op_side = use_side;
             hipEvent_t e1 = nullptr;
             if (pgrads[o.w] != nullptr && op_side) {      // dy is complete here
-                e1 = n->next_event();
+                e1 = r.next_event();
                 if (!e1) return D3_ERR_OVERFLOW;
                 D3_CHECK(hipEventRecord(e1, s));
             }
             // data gradient
             if (o.in_grad_mode) {
-                int ldgi, root_i, gibf; float *gi = gptr(n, garena, gout, gin, o.in, ldgi, root_i, &gibf);
-                const int obf = gibf ? D3_CONV_OUTBF16 : 0;
-                if (root_i >= 0) wait_pending(root_i);
-                ConvExtras ex;
-                if (o.map == MAP_K3 && (size_t)o.mlevel < n->k3_16.size()) {
-                    ex.tbl16 = n->k3_16[(size_t)o.mlevel];
-                    if (use_p2 || o.bn_of_in < 0) ex.tblq = n->k3_q[(size_t)o.mlevel];
-                }
+                const GradView &vi = n->gv[o.in];
+                float *gi = gp(vi);
+                if (vi.root >= 0) wait_pending(vi.root);
                 int rc, np = 0;
                 if (o.bn_of_in >= 0) {
                     const OpD &b = n->ops[o.bn_of_in];
                     const TensorD &tx = n->T[b.in];
-                    float *mean = (float *)(arena + b.state_off), *var = mean + tx.C;
-                    if (use_p2) ex.part2 = (double *)(garena + b.bpart2_off);
-                    const ConvBn bn{tptr(n, arena, input, b.in), mean, var, (const float *)params[b.gamma], (const float *)params[b.beta], tx.ld, b.relu, tx.dtype == 1 ? 1 : 0, b.eps};
-                    rc = d3_conv2_run(go, ldgo, tb, arena + o.wp_bwd, gi, ldgi, nullptr, 0, (float *)(garena + b.bpart_off), Mout, Min, o.K, o.Cout, o.CinW,
-                                      (gobf ? D3_CONV_XBF16 : 0) | (n->f32 ? D3_CONV_F32 : 0) | obf, &bn, ex, &np, stream);
-                    if (!rc) n->ops[o.bn_of_in].bparts = np;
+                    float *mean = (float *)(arena + b.state.off), *var = mean + tx.C;
+                    const ConvExtras ex = conv_extras(r, o, true, use_p2, garena + b.bpart2.off);
+                    const ConvBn bn{tp(b.in), mean, var, (const float *)params[b.gamma], (const float *)params[b.beta], tx.ld, b.relu, tx.dtype == 1 ? 1 : 0, b.eps};
+                    rc = d3_conv2_run(go, ldgo, tb, arena + o.wp_bwd.off, gi, vi.ld, nullptr, 0, (float *)(garena + b.bpart.off), Mout, Min, o.K, o.Cout, o.CinW,
+                                      o.dgrad_flags, &bn, ex, &np, stream);
+                    if (!rc) bparts[o.bn_of_in] = np;
                 } else {
-                    rc = d3_conv2_run(go, ldgo, tb, arena + o.wp_bwd, gi, ldgi, nullptr, 0, nullptr, Mout, Min, o.K, o.Cout, o.CinW,
-                                      (o.in_grad_mode == 2 ? D3_CONV_ACCUM : 0) | (gobf ? D3_CONV_XBF16 : 0) | (n->f32 ? D3_CONV_F32 : 0) | obf, nullptr, ex, &np, stream);
+                    rc = d3_conv2_run(go, ldgo, tb, arena + o.wp_bwd.off, gi, vi.ld, nullptr, 0, nullptr, Mout, Min, o.K, o.Cout, o.CinW,
+                                      o.dgrad_flags | (o.in_grad_mode == 2 ? D3_CONV_ACCUM : 0), nullptr, conv_extras(r, o, false, use_p2, nullptr), &np, stream);
                 }
                 if (rc) return rc;
             }
             if (o.res_mode >= 2) {
-                int ldr, root_r; float *gr = gptr(n, garena, gout, gin, o.res, ldr, root_r);
-                if (root_r >= 0) wait_pending(root_r);
-                const long long total = (long long)Mout * (o.Cout / 4);
-                if (total > 0) un_add_kernel<<<(int)((total + 255) / 256), 256, 0, s>>>(gr, ldr, go32, ldgo32, Mout, o.Cout, o.res_mode == 3 ? 1 : 0);
+                const GradView &vr = n->gv[o.res];
+                if (vr.root >= 0) wait_pending(vr.root);
+                const long long total = (long long)Mout * (o.Cout / 4);      // (reads the fp32 buffer, not its shadow)
+                if (total > 0) un_add_kernel<<<(int)((total + 255) / 256), 256, 0, s>>>(gp(vr), vr.ld, gp(vo), vo.ld, Mout, o.Cout, o.res_mode == 3 ? 1 : 0);
             }
             // weight gradient on the side stream -- enqueued AFTER the data gradient: at the deep levels the caller's stream runs ~10 us
             // kernels and the host is the bottleneck (event pair + plan + launches of the weight gradient took ~20 us of host time in
@@ -1469,20 +1480,18 @@ static int net_backward_impl(void *h, const void *const *params, const int *cons
                 if (!op_side) main_wgrads = true;
                 hipStream_t wst = ws_stream;                 // the stream of THIS weight gradient
                 if (op_side) {
-                    if (use_side2 && (side2_flip++ & 1)) { wst = n->side2; side2_dirty = true; }
+                    if (use_side2 && (side2_flip++ & 1)) { wst = r.side2; side2_dirty = true; }
                     D3_CHECK(hipStreamWaitEvent(wst, e1, 0));
                     side_used = true;
                 }
-                const bool xstat = o.Cin > o.Cout;
-                int flags = (ti.dtype == 1 ? D3_CONV_XBF16 : 0) | (paccum[o.w] ? D3_CONV_ACCUM : 0) | (gobf ? D3_CONV_DYBF16 : 0) | (n->f32 ? D3_CONV_F32 : 0);
-                const int *tw = tf;
-                if (xstat) { flags |= D3_CONV_XSTAT | (flip ? D3_CONV_FLIPK : 0); tw = tb; }
+                // the word d3_net_plan sized wsplits / wpart from, plus the per-call bits
+                const int flags = o.wgrad_flags | (paccum[o.w] ? D3_CONV_ACCUM : 0) | D3_CONV_NOREDUCE;
+                const int *tw = (o.wgrad_flags & D3_CONV_XSTAT) ? tb : tf;
                 float *dW = pgrads[o.w];
                 // (the stem's x carries zero-padded channels: dW has CinW rows per offset)
-                char *wpart = garena + o.wpart_off;
-                const void *tw16 = (o.map == MAP_K3 && (size_t)o.mlevel < n->k3_16.size()) ? n->k3_16[(size_t)o.mlevel] : nullptr;
-                int rc = d3_conv2_wgrad(tptr(n, arena, input, o.in), ti.ld, tw, tw16, go, ldgo, dW, Min, Mout, o.K, o.Cin, o.Cout, o.CinW,
-                                        flags | D3_CONV_NOREDUCE, wpart, o.wpart_bytes, (void *)(op_side ? wst : s));
+                char *wpart = garena + o.wpart.off;
+                int rc = d3_conv2_wgrad(tp(o.in), ti.ld, tw, conv_extras(r, o, false, false, nullptr).tbl16, go, ldgo, dW, Min, Mout, o.K, o.Cin, o.Cout, o.CinW,
+                                        flags, wpart, o.wpart.bytes, (void *)(op_side ? wst : s));
                 if (o.wsplits > 1 || paccum[o.w] || n->f32) {   // (a single bf16-path split without accumulation was written to dW directly)
                     RedJob j;
                     memset(&j, 0, sizeof(j));
@@ -1497,7 +1506,7 @@ static int net_backward_impl(void *h, const void *const *params, const int *cons
                     // pending, this stream waits for it first, so that the recorded event covers both readers
                     auto prev = pending.find(root_o);
                     if (prev != pending.end()) D3_CHECK(hipStreamWaitEvent(wst, prev->second, 0));
-                    hipEvent_t e2 = n->next_event();
+                    hipEvent_t e2 = r.next_event();
                     if (!e2) return D3_ERR_OVERFLOW;
                     D3_CHECK(hipEventRecord(e2, wst));
                     pending[root_o] = e2;
@@ -1508,28 +1517,32 @@ static int net_backward_impl(void *h, const void *const *params, const int *cons
             const TensorD &ti = n->T[o.in];
             const int M = n->rows[ti.level], C = ti.C;
             if (M <= 0) continue;
-            float *mean = (float *)(arena + o.state_off), *var = mean + C, *sums = var + C;
+            float *mean = (float *)(arena + o.state.off), *var = mean + C, *sums = var + C;
             const float *gamma = (const float *)params[o.gamma], *beta = (const float *)params[o.beta];
-            int ldgo, root_o, gobf; float *go = gptr(n, garena, gout, gin, o.out, ldgo, root_o, &gobf);
-            const float *x = (const float *)tptr(n, arena, input, o.in);
+            const GradView &vo = n->gv[o.out], &vi = n->gv[o.in];
+            const int ldgo = vo.ld, gobf = vo.bf16, root_i = vi.root, gibf = o.in_grad_mode ? vi.bf16 : 0;
+            float *go = gp(vo);
+            // its apply also writes the bf16 shadow of the buffer it finalises (the view behind the tensors' in Net::gv)
+            const GradView *vs = (o.in_grad_mode && o.write_shadow && root_i >= 0) ? &n->gv[n->T.size() + (size_t)root_i] : nullptr;
+            unsigned short *sh = (vs && vs->ld == C) ? (unsigned short *)gp(*vs) : nullptr;
+            const float *x = (const float *)tp(o.in);
             int relu = o.relu;
             const int fs_rows_b = d3_tune(D3T_BN_FUSED_ROWS);
             if (o.fused_by >= 0 && fs_rows_b > 0 && C <= UN_FS_MAXC &&
-                (use_p2 || 2ll * o.bparts * C <= UN_FS_MAX_PART_FLOATS)) {
+                (use_p2 || 2ll * bparts[i] * C <= UN_FS_MAX_PART_FLOATS)) {
                 // the epilogue partials -> sums / dgamma / dbeta and the input gradient in one launch
                 int G, rows_pb; un_fs_grid(M, C, G, rows_pb, M <= fs_rows_b ? 32 : 512);
-                float *gi = nullptr; int ldgi = 0, root_i = -1, gibf = 0;
+                float *gi = nullptr; int ldgi = 0;
                 if (o.in_grad_mode) {
-                    gi = gptr(n, garena, gout, gin, o.in, ldgi, root_i, &gibf);
+                    gi = gp(vi); ldgi = vi.ld;
                     if (root_i >= 0) wait_pending(root_i);
                 }
-                unsigned short *sh = (o.in_grad_mode && o.write_shadow && root_i >= 0 && n->gshadow[root_i] == C) ? (unsigned short *)(garena + n->gshadow_off[root_i]) : nullptr;
                 if (!o.in_grad_mode) G = 1;
 #define UN_FSB2(OBFV, GBFV, XBFV, RELU_, ACC_, SH_)                                                                                   \
-                un_bn_bwd_fused_small_kernel<OBFV, GBFV, XBFV><<<G, UN_FS_T, 0, s>>>((const float *)(garena + o.bpart_off), o.bparts, x, ti.ld, go, ldgo, mean, \
+                un_bn_bwd_fused_small_kernel<OBFV, GBFV, XBFV><<<G, UN_FS_T, 0, s>>>((const float *)(garena + o.bpart.off), bparts[i], x, ti.ld, go, ldgo, mean, \
                                                                               var, gamma, beta, sums, pgrads[o.gamma], pgrads[o.beta], paccum[o.gamma], gi, \
                                                                               ldgi, M, C, o.eps, RELU_, ACC_, SH_, rows_pb, \
-                                                                              use_p2 ? (const double *)(garena + o.bpart2_off) : nullptr)
+                                                                              use_p2 ? (const double *)(garena + o.bpart2.off) : nullptr)
 #define UN_FSB(OBFV, GBFV, RELU_, ACC_, SH_) do { if (ti.dtype == 1) UN_FSB2(OBFV, GBFV, true, RELU_, ACC_, SH_); else UN_FSB2(OBFV, GBFV, false, RELU_, ACC_, SH_); } while (0)
                 if (gibf) { if (gobf) UN_FSB(true, true, 0, 0, nullptr); else UN_FSB(true, false, 0, 0, nullptr); }
                 else if (gobf) UN_FSB(false, true, 0, o.in_grad_mode == 2 ? 1 : 0, sh);
@@ -1539,7 +1552,7 @@ static int net_backward_impl(void *h, const void *const *params, const int *cons
                 continue;
             }
             if (o.fused_by >= 0) {   // reductions (and the ReLU mask) done by the consumer conv's data gradient
-                un_bn_bwd_final_kernel<<<(C + 3) / 4, 256, 0, s>>>((const float *)(garena + o.bpart_off), o.bparts, C, sums,
+                un_bn_bwd_final_kernel<<<(C + 3) / 4, 256, 0, s>>>((const float *)(garena + o.bpart.off), bparts[i], C, sums,
                                                                pgrads[o.gamma], pgrads[o.beta], paccum[o.gamma]);
                 relu = 0;
             } else {
@@ -1548,10 +1561,9 @@ static int net_backward_impl(void *h, const void *const *params, const int *cons
                 un_bn_bwd_final_kernel<<<(C + 3) / 4, 256, 0, s>>>(bnscr, nb, C, sums, pgrads[o.gamma], pgrads[o.beta], paccum[o.gamma]);
             }
             if (o.in_grad_mode) {
-                int ldgi, root_i, gibf; float *gi = gptr(n, garena, gout, gin, o.in, ldgi, root_i, &gibf);
+                float *gi = gp(vi); const int ldgi = vi.ld;
                 if (root_i >= 0) wait_pending(root_i);
                 const long long total = (long long)M * (C / 4);
-                unsigned short *sh = (o.write_shadow && root_i >= 0 && n->gshadow[root_i] == C) ? (unsigned short *)(garena + n->gshadow_off[root_i]) : nullptr;
 #define UN_APB(OBFV, GBFV, ACC_, SH_)                                                                                                     \
                 un_bn_bwd_apply_kernel<OBFV, GBFV><<<un_ap_grid(M, C, UN_AP_U * 2), 256, 0, s>>>(x, ti.ld, go, ldgo, mean, var, gamma, beta, sums, gi, ldgi, M, C, \
                                                                                               o.eps, relu, ACC_, SH_, ti.dtype == 1 ? 1 : 0)
@@ -1567,11 +1579,20 @@ static int net_backward_impl(void *h, const void *const *params, const int *cons
     { int jrc = join_side2(); if (jrc) return jrc; }
     // join: the caller's stream waits for the last weight gradient
     if (side_used) {
-        hipEvent_t e = n->next_event();
+        hipEvent_t e = r.next_event();
         if (!e) return D3_ERR_OVERFLOW;
-        D3_CHECK(hipEventRecord(e, n->side));
+        D3_CHECK(hipEventRecord(e, r.side));
         D3_CHECK(hipStreamWaitEvent(s, e, 0));
     }
     D3_LAUNCH_CHECK();
     return 0;
+}
+extern "C" int d3_net_backward(void *h, const void *const *params, const int *const *k3, const int *const *child,
+                               const int *const *up, const void *input, void *arena_, void *garena_, const float *gout,
+                               float *const *pgrads, const int *paccum, float *gin, void *stream) {
+    Net *n = (Net *)h;
+    if (!n) return D3_ERR_ARG;
+    const int rc = net_backward_impl(n, n->run, params, k3, child, up, input, arena_, garena_, gout, pgrads, paccum, gin, stream);
+    net_drop_k3_16(n->run);
+    return rc;
 }

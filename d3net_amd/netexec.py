@@ -22,6 +22,18 @@ from .pointgroup_ops import _on, _stream
 OP_CONV, OP_BNACT, OP_PADCAST, OP_STATS = 1, 2, 3, 4
 MAP_K1, MAP_K3, MAP_DOWN, MAP_UP = 0, 1, 2, 3
 F32, BF16 = 0, 1
+# d3_net_describe's records (include/d3hip.h): the header, then one record per op, per tensor (its gradient view) and per buffer
+DESCRIBE_HEADER = ("version", "nops", "ntensors", "nbufs", "nlevels", "planned", "op_words", "tensor_words", "buf_words", "f32",
+                   "arena_bytes", "grad_bytes", "cnt_off0", "cnt_bytes", "bcnt_off0", "bcnt_bytes", "bnscr_off", "bnscr_bytes",
+                   "wgws_off", "wgws_bytes")
+DESCRIBE_OP = ("type", "in_grad_mode", "res_mode", "needs_dgrad_pack", "bn_of_in", "fused_by", "wg_hazard", "use_shadow",
+               "write_shadow", "nsrcs", "src0_op", "src0_c0", "src0_cn", "src1_op", "src1_c0", "src1_cn", "fwd_flags", "dgrad_flags",
+               "wgrad_flags", "wgrad_map", "wgrad_flip", "k3_tables", "Cin", "Cout", "dy_view", "wsplits", "nparts_max", "bparts_max",
+               "partw", "wp_fwd_off", "wp_fwd_bytes", "wp_bwd_off", "wp_bwd_bytes", "part_off", "part_bytes", "part2_off",
+               "part2_bytes", "state_off", "state_bytes", "bpart_off", "bpart_bytes", "bpart2_off", "bpart2_bytes", "wpart_off",
+               "wpart_bytes")
+DESCRIBE_TENSOR = ("kind", "root", "ld", "coff", "bf16", "goff")
+DESCRIBE_BUF = ("galias", "gbf", "gabf", "gshadow", "need_grad", "off", "bytes", "goff", "gbytes", "gshadow_off", "gshadow_bytes")
 import os as _os
 SINGLE_READER_BF16 = _os.environ.get("D3X_T_F32", "") == ""     # (A/B, tools/jobs: D3X_T_F32=1 keeps every convolution output in fp32, rounds 1-5)
 
@@ -209,6 +221,25 @@ class NativeUNet:
             self._plan_key = key
             self._plan = (a.value, g.value, _lib.lib().d3_net_tensor_offset(self._net(), self.out_tensor))
         return self._plan
+
+    def describe(self, rows=None):
+        """the executor's plan as named fields (d3_net_describe; pure host code): {"header": {...}, "ops": [...], "tensors": [...],
+        "bufs": [...]}; rows: plan for these level sizes first (the offsets and sizes are zero before a plan)"""
+        if rows is not None:
+            self._plan_for(rows)
+        L = _lib.lib()
+        nw = L.d3_net_describe(self._net(), None, 0)
+        raw = (C.c_int64 * nw)()
+        assert L.d3_net_describe(self._net(), raw, nw) == nw
+        w = list(raw)
+        hdr = dict(zip(DESCRIBE_HEADER, w))
+        assert hdr["version"] == 1 and (hdr["op_words"], hdr["tensor_words"], hdr["buf_words"]) == (len(DESCRIBE_OP), len(DESCRIBE_TENSOR), len(DESCRIBE_BUF))
+        d, at = {"header": hdr}, len(DESCRIBE_HEADER)
+        for key, count, names in (("ops", hdr["nops"], DESCRIBE_OP), ("tensors", hdr["ntensors"], DESCRIBE_TENSOR), ("bufs", hdr["nbufs"], DESCRIBE_BUF)):
+            d[key] = [dict(zip(names, w[at + i * len(names):at + (i + 1) * len(names)])) for i in range(count)]
+            at += count * len(names)
+        assert at == nw
+        return d
 
     def _grads(self, device):
         """flat gradient buffer + one view per trainable parameter"""

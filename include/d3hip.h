@@ -396,6 +396,22 @@ void *d3_net_create(const int64_t *prog, int nops, const int64_t *tensors, int n
 void d3_net_destroy(void *net);
 int d3_net_plan(void *net, const int *rows, size_t *arena_bytes, size_t *grad_bytes);
 long long d3_net_tensor_offset(void *net, int tensor);
+/* The executor's plan as numbers (pure host code, no GPU call): what d3_net_create decided per op, tensor and buffer, and, after a
+ * d3_net_plan, where every region of the two arenas lies.  Returns the number of int64 words; fills `out` when cap suffices.
+ * Layout: header[20] = version (1), nops, ntensors, nbufs, nlevels, planned, op_words, tensor_words, buf_words, f32, arena_bytes,
+ * grad_bytes, cnt_off0, cnt_bytes, bcnt_off0, bcnt_bytes (the two zeroed-per-call areas), bnscr_off, bnscr_bytes, wgws_off,
+ * wgws_bytes; then nops records of op_words, ntensors of tensor_words, nbufs of buf_words.
+ * op record: type, in_grad_mode, res_mode, needs_dgrad_pack, bn_of_in, fused_by, wg_hazard, use_shadow, write_shadow, nsrcs,
+ * 2 x (src op, c0, cn), fwd_flags, dgrad_flags (without D3_CONV_ACCUM: in_grad_mode == 2 adds it), wgrad_flags (without the per-call
+ * D3_CONV_ACCUM), wgrad_map (0: the forward table, 1: the transposed one), wgrad_flip, k3_tables (may take the 16-bit / lane
+ * table), Cin, Cout, dy_view (gradient view its backward reads dy from: a tensor, or ntensors + buffer = that buffer's bf16 shadow);
+ * after a plan: wsplits, nparts_max, bparts_max, partw, then (offset, bytes) of wp_fwd, wp_bwd, part, part2, state (arena), bpart,
+ * bpart2, wpart (gradient arena).
+ * tensor record (its gradient view): kind (0: the caller's gin, 1: the caller's gout, 2: gradient arena), root buffer (-1 / -2 for
+ * kinds 0 / 1), row stride, column offset, bf16, byte offset in the gradient arena (-1 before a plan and for kinds 0 / 1).
+ * buffer record: galias, gbf, gabf, gshadow, need_grad; after a plan: off, bytes (arena), goff, gbytes, gshadow_off, gshadow_bytes
+ * (gradient arena).  The field names live in d3net_amd/netexec.py (DESCRIBE_*), NativeUNet.describe() returns them named. */
+long long d3_net_describe(void *net, int64_t *out, long long cap);
 int d3_net_forward(void *net, const void *const *params, const int *const *k3, const int *const *child,
                    const int *const *up, const void *input, void *arena, int training, void *stream);
 int d3_net_backward(void *net, const void *const *params, const int *const *k3, const int *const *child,
