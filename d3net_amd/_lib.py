@@ -129,6 +129,10 @@ SIGNATURES = {
     "d3_cross_entropy": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, sz, vp]),
     "d3_attn_fwd": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
     "d3_attn_bwd": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
+    "d3_scanrefer_match_groups": (i32, [i32, i32]),
+    "d3_scanrefer_match_fwd": (i32, [vp, i32, vp]),
+    "d3_scanrefer_match_bwd_ws_bytes": (sz, []),
+    "d3_scanrefer_match_bwd": (i32, [vp, vp, i32, vp]),
     "d3_hgemm": (i32, [vp, i32, vp]),
     "d3_colsum_ws_bytes": (sz, [i32]),
     "d3_colsum": (i32, [vp, i64, i32, i32, vp, i32, vp, sz, vp]),
@@ -228,6 +232,25 @@ class GemmProb(C.Structure):
                 ("gru", i32), ("gru_H", i32), ("g_d0", vp), ("g_ld0", i64), ("g_d1", vp), ("g_ld1", i64),
                 ("g_r", vp), ("g_z", vp), ("g_n", vp), ("g_ghn", vp), ("g_hp", vp), ("g_ldh", i64),
                 ("g_dgi", vp), ("g_lddgi", i64), ("g_dgh", vp), ("g_dhp", vp)]
+
+
+SRM_PARAMS = ("W0", "b0", "g1", "be1", "rm1", "rv1", "alpha", "W3", "b3", "W4", "b4", "g2", "be2", "rm2", "rv2", "W5", "b5", "g3", "be3",
+              "rm3", "rv3", "w6", "b6")
+SRM_GRADS = ("dW0", "db0", "dg1", "dbe1", "dalpha", "dW3", "db3", "dW4", "db4", "dg2", "dbe2", "dW5", "db5", "dg3", "dbe3", "dw6", "db6")
+
+
+class SrmArgs(C.Structure):
+    """d3_srm_args (include/d3hip.h)"""
+    _fields_ = ([(k, i32) for k in ("B", "K", "N", "div", "m", "L")] + [(k, vp) for k in ("feats", "lang", "mask")] +
+                [(k, vp) for k in SRM_PARAMS] + [("eps", f32 * 3), ("momentum", f32 * 3), ("nbt", vp * 3)] +
+                [(k, vp) for k in ("PQ", "part", "x1", "f", "y2", "z2", "y3", "bnstat", "conf")])
+
+
+class SrmGrads(C.Structure):
+    """d3_srm_grads (include/d3hip.h)"""
+    _fields_ = ([("dconf", vp)] + [(k, vp) for k in SRM_GRADS] + [(k, vp) for k in ("dfeats", "dlang")] +
+                [(k, vp) for k in ("dpre3", "dz2", "dpre2", "df", "dbn1", "dP", "dQ", "db0part", "part")] +
+                [("ws", vp), ("ws_bytes", sz)])
 
 
 TOPDOWN_PARAMS = ("W_td", "b_td", "Wih1", "Whh1", "bih1", "bhh1", "W_feat", "W_hidd", "w_att", "W_lang", "b_lang",

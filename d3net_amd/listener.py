@@ -1,6 +1,6 @@
-"""Listener (grounding) head on MI355X: `LangModule`, `MultiHeadAttention`, `TransformerMatchModule`, `ListenerNet`
-with the reference's constructors, `data_dict` keys and state-dict layout
-(reference: model/lang_module.py:8-178, model/transformer/attention.py:7-77,134-176, model/match_module.py:143-336,
+"""Listener (grounding) head on MI355X: `LangModule`, `MultiHeadAttention`, `TransformerMatchModule`, `ScanReferMatchModule`,
+`ListenerNet` with the reference's constructors, `data_dict` keys and state-dict layout
+(reference: model/lang_module.py:8-178, model/transformer/attention.py:7-77,134-176, model/match_module.py:11-336,
 model/listener.py:10-54).
 
 What runs where: projections / 1x1 convs / LayerNorm / BatchNorm1d are plain library GEMMs and elementwise ops
@@ -8,7 +8,8 @@ What runs where: projections / 1x1 convs / LayerNorm / BatchNorm1d are plain lib
 backward) is the hand-written kernel `d3_attn_fwd/bwd` (csrc/attention.hip), which consumes the UN-replicated distance
 weights and (B,T) masks instead of the (B*C,4,128,128) copies the reference builds with `.repeat`
 (model/match_module.py:191-197,324-326), on fp32 MFMA tiles.  The packed-sequence GRU of `LangModule` is the native
-`d3_gru_seq_forward/backward` (csrc/topdown.hip; `LangModule.native`).
+`d3_gru_seq_forward/backward` (csrc/topdown.hip; `LangModule.native`).  The ScanRefer matcher (`match_type: ScanRefer`) is
+csrc/scanrefer_match.hip from its inputs to `cluster_ref`, forward and backward.
 """
 import ctypes as C
 import math
@@ -353,6 +354,184 @@ class TransformerMatchModule(nn.Module):
         return data_dict
 
 
+# ----------------------------------------------------------------------------------- ScanRefer match
+_SRM_ACTS = ("x1", "f", "y2", "z2", "y3")
+_SRM_WEIGHTS = ("W0", "b0", "g1", "be1", "alpha", "W3", "b3", "W4", "b4", "g2", "be2", "W5", "b5", "g3", "be3", "w6", "b6")
+
+
+def _srm_args(feats, lang, mask, div, params, stats, hyper):
+    """d3_srm_args without its scratch pointers: shapes, inputs, the 17 parameters in module order, the six running buffers"""
+    a = _lib.SrmArgs()
+    (a.B, a.K, a.m), (a.N, a.L), a.div = feats.shape, lang.shape, div
+    a.feats, a.lang, a.mask = feats.data_ptr(), lang.data_ptr(), (mask.data_ptr() if mask is not None else None)
+    for k, t in zip(_SRM_WEIGHTS + ("rm1", "rv1", "rm2", "rv2", "rm3", "rv3"), tuple(params) + tuple(stats[:6])):
+        setattr(a, k, t.data_ptr())
+    for j, (eps, mom) in enumerate(hyper):
+        a.eps[j], a.momentum[j] = eps, mom
+    for j, t in enumerate(stats[6:]):          # num_batches_tracked x 3 (the forward only)
+        a.nbt[j] = t.data_ptr()
+    return a
+
+
+class ScanReferMatchFunction(Function):
+    """conf (N, K) of `fuse` + `match` (model/match_module.py:24-39) on feats (B,K,m), lang (N,L), mask (B,K) | None, row n
+    reading the proposals of scene n // div -- csrc/scanrefer_match.hip, forward and backward.  `stats`: the six running
+    buffers and then the three `num_batches_tracked` (all updated in place when `train`); `hyper`: ((eps, momentum) x 3); `keep`: save what the backward needs."""
+
+    @staticmethod
+    def forward(ctx, feats, lang, mask, div, train, keep, stats, hyper, *params):
+        L = _lib.lib()
+        dev = feats.device
+        B, K, m = feats.shape
+        N, Ls = lang.shape
+        R = N * K
+        G = L.d3_scanrefer_match_groups(N, K)
+        f32 = dict(dtype=torch.float32, device=dev)
+        a = _srm_args(feats, lang, mask, div, params, stats, hyper)
+        bufs = {"PQ": torch.empty((B * K + N, 128), **f32), "part": torch.empty((3, G, 2, 128), dtype=torch.float64, device=dev),
+                "conf": torch.empty((N, K), **f32)}
+        for k in (_SRM_ACTS if keep else (("y2", "y3") if train else ())):
+            bufs[k] = torch.empty((R, 128), **f32)
+        if keep:
+            bufs["bnstat"] = torch.empty((3, 2, 128), **f32)
+        for k, t in bufs.items():
+            setattr(a, k, t.data_ptr())
+        with _on(dev):
+            check(L.d3_scanrefer_match_fwd(C.byref(a), int(train), _stream()), "scanrefer_match_fwd")
+        if keep:
+            ctx.save_for_backward(feats, lang, *([mask] if mask is not None else []), *params, bufs["PQ"], bufs["bnstat"],
+                                  *[bufs[k] for k in _SRM_ACTS])
+            ctx.cfg = (div, train, mask is not None, stats, hyper)
+        return bufs["conf"]
+
+    @staticmethod
+    def backward(ctx, dconf):
+        L = _lib.lib()
+        div, train, has_mask, stats, hyper = ctx.cfg
+        saved = list(ctx.saved_tensors)
+        feats, lang = saved[0], saved[1]
+        mask = saved[2] if has_mask else None
+        o = 3 if has_mask else 2
+        params, (PQ, bnstat, x1, f, y2, z2, y3) = saved[o:o + 17], saved[o + 17:]
+        dev = feats.device
+        B, K, m = feats.shape
+        N, Ls = lang.shape
+        R = N * K
+        G = L.d3_scanrefer_match_groups(N, K)
+        f32 = dict(dtype=torch.float32, device=dev)
+        a = _srm_args(feats, lang, mask, div, params, stats[:6], hyper)
+        part_f = torch.empty((3, G, 2, 128), dtype=torch.float64, device=dev)    # (the forward's partial sums are not read again)
+        conf = torch.empty(1, **f32)
+        for k, t in (("PQ", PQ), ("part", part_f), ("x1", x1), ("f", f), ("y2", y2), ("z2", z2), ("y3", y3), ("bnstat", bnstat), ("conf", conf)):
+            setattr(a, k, t.data_ptr())
+        g = _lib.SrmGrads()
+        dconf = dconf.contiguous()
+        g.dconf = dconf.data_ptr()
+        grads = [torch.empty_like(p) for p in params]
+        for k, t in zip(_lib.SRM_GRADS, grads):
+            setattr(g, k, t.data_ptr())
+        dfeats = torch.empty_like(feats) if ctx.needs_input_grad[0] else None
+        dlang = torch.empty_like(lang) if ctx.needs_input_grad[1] else None
+        g.dfeats = dfeats.data_ptr() if dfeats is not None else None
+        g.dlang = dlang.data_ptr() if dlang is not None else None
+        scratch = {k: torch.empty((R, 128), **f32) for k in ("dpre3", "dz2", "dpre2", "df", "dbn1")}
+        scratch["dP"] = torch.empty((B * K, 128), **f32)
+        scratch["dQ"] = torch.empty((N, 128), **f32)
+        scratch["db0part"] = torch.empty((N, 128), **f32)
+        scratch["part"] = torch.empty((3, G, 3, 128), dtype=torch.float64, device=dev)
+        for k, t in scratch.items():
+            setattr(g, k, t.data_ptr())
+        ws = torch.empty(L.d3_scanrefer_match_bwd_ws_bytes(), dtype=torch.uint8, device=dev)
+        g.ws, g.ws_bytes = ws.data_ptr(), ws.numel()
+        with _on(dev):
+            check(L.d3_scanrefer_match_bwd(C.byref(a), C.byref(g), int(train), _stream()), "scanrefer_match_bwd")
+        return (dfeats, dlang, None, None, None, None, None, None) + tuple(grads)
+
+
+class ScanReferMatchModule(nn.Module):
+    """The ScanRefer baseline matcher (reference: model/match_module.py:11-141 `MatchModule`): same constructor, attributes
+    and state-dict keys (`fuse.{0,1,2,3}`, `match.{0,2,3,5,6}` with nn.Conv1d-shaped weights); the arithmetic is
+    csrc/scanrefer_match.hip -- the (N, K, m + lang_size) concatenation and the per-description copies of the proposal rows
+    the reference builds (:116-127) are never materialised.  No CPU path."""
+
+    def __init__(self, cfg, lang_size=256, hidden_size=128):
+        super().__init__()
+        self.num_proposals = cfg.model.max_num_proposal
+        self.lang_size = lang_size
+        self.hidden_size = hidden_size
+        self.det_channel = cfg.model.m
+        self.chunk_size = cfg.data.num_des_per_scene
+        self.fuse = nn.Sequential(
+            nn.Conv1d(lang_size + self.det_channel, hidden_size, 1), nn.BatchNorm1d(hidden_size), nn.PReLU(hidden_size),
+            nn.Conv1d(hidden_size, hidden_size, 1))
+        self.match = nn.Sequential(
+            nn.Conv1d(hidden_size, hidden_size, 1), nn.ReLU(), nn.BatchNorm1d(hidden_size),
+            nn.Conv1d(hidden_size, hidden_size, 1), nn.ReLU(), nn.BatchNorm1d(hidden_size),
+            nn.Conv1d(hidden_size, 1, 1))
+
+    def _check(self, feats, lang, mask, div):
+        """everything the kernels do not cover raises here, before any copy or launch"""
+        if self.hidden_size != 128:
+            raise NotImplementedError("ScanReferMatchModule: the kernels are written for hidden_size 128, not %d" % self.hidden_size)
+        for name, t in (("proposal_feats_batched", feats), ("lang_emb", lang)):
+            if not t.is_cuda:
+                raise RuntimeError("ScanReferMatchModule: %s is on %s; the module runs on the GPU only (no CPU fallback)" % (name, t.device))
+            if t.dtype != torch.float32:
+                raise TypeError("ScanReferMatchModule: %s must be float32, got %s" % (name, t.dtype))
+            if not t.is_contiguous():
+                raise ValueError("ScanReferMatchModule: %s must be contiguous" % name)
+        if feats.dim() != 3 or feats.shape[2] != self.det_channel or self.det_channel % 4 != 0:
+            raise ValueError("ScanReferMatchModule: proposal features (B, K, m) with m == cfg.model.m and m %% 4 == 0 expected, got %s"
+                             % (tuple(feats.shape),))
+        if lang.dim() != 2 or lang.shape[1] != self.lang_size or lang.shape[0] != feats.shape[0] * div:
+            raise ValueError("ScanReferMatchModule: language embedding (%d, %d) expected, got %s"
+                             % (feats.shape[0] * div, self.lang_size, tuple(lang.shape)))
+        if mask is not None and (mask.device != feats.device or tuple(mask.shape) != tuple(feats.shape[:2])):
+            raise ValueError("ScanReferMatchModule: proposal_batch_mask (B, K) on the features' device expected")
+        bns = (self.fuse[1], self.match[2], self.match[5])
+        if any(bn.momentum is None or not bn.track_running_stats or not bn.affine for bn in bns):
+            raise NotImplementedError("ScanReferMatchModule: BatchNorm1d with affine parameters, running statistics and a fixed momentum only")
+        if self.fuse[0].weight.device != feats.device:
+            raise RuntimeError("ScanReferMatchModule: parameters on %s, inputs on %s" % (self.fuse[0].weight.device, feats.device))
+        if self.training and feats.shape[1] * lang.shape[0] < 2:
+            raise ValueError("ScanReferMatchModule: training-mode BatchNorm needs more than one position")
+
+    def _run(self, feats, lang, mask, div):
+        fu, ma = self.fuse, self.match
+        bns = (fu[1], ma[2], ma[5])
+        params = (fu[0].weight, fu[0].bias, fu[1].weight, fu[1].bias, fu[2].weight, fu[3].weight, fu[3].bias, ma[0].weight, ma[0].bias,
+                  ma[2].weight, ma[2].bias, ma[3].weight, ma[3].bias, ma[5].weight, ma[5].bias, ma[6].weight, ma[6].bias)
+        stats = tuple(t for bn in bns for t in (bn.running_mean, bn.running_var)) + tuple(bn.num_batches_tracked for bn in bns)
+        hyper = tuple((float(bn.eps), float(bn.momentum)) for bn in bns)
+        keep = torch.is_grad_enabled() and any(t.requires_grad for t in (feats, lang) + params)
+        return ScanReferMatchFunction.apply(feats, lang, mask, div, self.training, keep, stats, hyper, *params)
+
+    def forward(self, data_dict, use_rl=False):
+        feats = data_dict["proposal_feats_batched"]
+        if use_rl:
+            # (:50-108) no mask; row n reads the proposals of scene n // sampled_topn; the reference's assert (:69) holds for one
+            # description per scene only
+            sampled, baseline = data_dict["lang_emb"]["sampled"], data_dict["lang_emb"]["baseline"]
+            topn = int(data_dict["sampled_topn"])
+            if feats.shape[0] * topn != sampled.shape[0] or sampled.shape != baseline.shape:
+                raise ValueError("ScanReferMatchModule (use_rl): %d scenes x sampled_topn %d != %d sampled descriptions (the reference's "
+                                 "branch holds for num_des_per_scene == 1 only, model/match_module.py:69)"
+                                 % (feats.shape[0], topn, sampled.shape[0]))
+            self._check(feats, sampled, None, topn)
+            self._check(feats, baseline, None, topn)
+            s = self._run(feats, sampled, None, topn)
+            with torch.no_grad():
+                b = self._run(feats, baseline, None, topn)
+            data_dict["cluster_ref"] = {"sampled": s, "baseline": b}
+            return data_dict
+        lang = data_dict["lang_emb"]
+        mask = data_dict["proposal_batch_mask"]
+        self._check(feats, lang, mask, self.chunk_size)
+        # (:130) the mask multiplies both halves of the concatenation; the confidences are NOT masked (:136-137 is commented out)
+        data_dict["cluster_ref"] = self._run(feats, lang, mask.float().contiguous(), self.chunk_size)
+        return data_dict
+
+
 class ListenerNet(nn.Module):
     """(reference: model/listener.py:10-54)"""
 
@@ -361,9 +540,13 @@ class ListenerNet(nn.Module):
         self.cfg = cfg
         self.match_type = cfg.model.match_type
         self.lang = LangModule(cfg)
-        if self.match_type != "Transformer":
-            raise NotImplementedError("only match_type: Transformer (the shipped default, conf/pointgroup.yaml:79)")
-        self.match = TransformerMatchModule(cfg)
+        if self.match_type == "ScanRefer":
+            self.match = ScanReferMatchModule(cfg)
+        elif self.match_type == "Transformer":
+            self.match = TransformerMatchModule(cfg)
+        else:
+            raise NotImplementedError("match_type %r: only Transformer (the shipped default, conf/pointgroup.yaml:79) and ScanRefer"
+                                      % (self.match_type,))
 
     def forward(self, data_dict, use_rl=False):
         data_dict = self.lang(data_dict, use_rl)

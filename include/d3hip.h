@@ -551,6 +551,47 @@ int d3_layernorm_bwd(const float *a, const float *b, const float *gamma, const f
                      const float *dy, float *dx, float *dgamma, float *dbeta, int R, int D, void *ws, size_t ws_bytes,
                      void *stream);
 
+/* ---- ScanRefer match module of the listener (csrc/scanrefer_match.hip) ---------------------------------
+ * MatchModule.forward (model/match_module.py:24-39 the layers, :110-139 the supervised branch, :50-108 the RL branch):
+ *     conf (N,K) = match(fuse(mask . cat[feats[n / div], lang[n]]))   with training- or eval-mode BatchNorm1d,
+ * without the (N, K, m+L) concatenation or the per-description copies of the proposal rows: the first convolution is split into
+ * P = feats W0[:, :m]^T and Q = lang W0[:, m:]^T, h1 = mask (P + Q) + b0 is recomputed where needed, and the chain is cut only
+ * where a training-mode BatchNorm needs statistics over all N K positions (per-workgroup partial sums in double, added in
+ * workgroup order by the consumer: deterministic, no atomics).  Hidden width 128 only; m % 4 == 0; N == B * div.
+ *   feats (B,K,m), lang (N,L), mask (B,K) or NULL (RL branch: no mask, :76-83); W0 (128, m+L) = fuse.0, g1/be1/rm1/rv1 = fuse.1
+ *   (running statistics and the nbt counters updated in place when train != 0: momentum, unbiased variance), alpha (128) = fuse.2, W3/b3 = fuse.3,
+ *   W4/b4 = match.0, g2.. = match.2, W5/b5 = match.3, g3.. = match.5, w6 (128) / b6 (1) = match.6.
+ *   Scratch the caller provides: PQ ((B K + N), 128); part (3, G, 2, 128) doubles with G = d3_scanrefer_match_groups(N, K);
+ *   y2, y3 (N K, 128) (required when train != 0); x1, f, z2 (N K, 128) and bnstat (3, 2, 128: mean, rstd) are kept for the
+ *   backward -- all of x1 / f / y2 / z2 / y3 / bnstat, or x1 == NULL for a forward without one.
+ * fwd launches: 1-2 (hgemm P, Q) + 4 (train) or + 1 (eval).  bwd: 4 kernels + column sums + weight-gradient hgemm calls; dfeats
+ * (B,K,m) / dlang (N,L) may be NULL; dW0 .. db6 are written (not accumulated); the rest of d3_srm_grads is scratch:
+ * dpre3, dz2, dpre2, df, dbn1 (N K, 128), dP (B K, 128), dQ, db0part (N, 128), part (3, G, 3, 128) doubles,
+ * ws >= d3_scanrefer_match_bwd_ws_bytes(). */
+typedef struct {
+    int B, K, N, div, m, L;
+    const float *feats, *lang, *mask;
+    const float *W0, *b0, *g1, *be1; float *rm1, *rv1; const float *alpha;
+    const float *W3, *b3, *W4, *b4, *g2, *be2; float *rm2, *rv2;
+    const float *W5, *b5, *g3, *be3; float *rm3, *rv3; const float *w6, *b6;
+    float eps[3], momentum[3];
+    long long *nbt[3];          /* num_batches_tracked of fuse.1, match.2, match.5 (or NULL): += 1 by the forward when train != 0 */
+    float *PQ; double *part;
+    float *x1, *f, *y2, *z2, *y3, *bnstat;
+    float *conf;
+} d3_srm_args;
+typedef struct {
+    const float *dconf;
+    float *dW0, *db0, *dg1, *dbe1, *dalpha, *dW3, *db3, *dW4, *db4, *dg2, *dbe2, *dW5, *db5, *dg3, *dbe3, *dw6, *db6;
+    float *dfeats, *dlang;
+    float *dpre3, *dz2, *dpre2, *df, *dbn1, *dP, *dQ, *db0part; double *part;
+    void *ws; size_t ws_bytes;
+} d3_srm_grads;
+int d3_scanrefer_match_groups(int N, int K);
+int d3_scanrefer_match_fwd(const d3_srm_args *a, int train, void *stream);
+size_t d3_scanrefer_match_bwd_ws_bytes(void);
+int d3_scanrefer_match_bwd(const d3_srm_args *a, const d3_srm_grads *g, int train, void *stream);
+
 /* ---- small-batch fp32 GEMMs of the proposal-level heads (csrc/hgemm.hip) ---------------------------
  * Every nn.Linear / nn.GRUCell product of the speaker and listener heads (model/caption_module.py:72-133,
  * model/graph_module.py:101-108, model/lang_module.py:51-55):
