@@ -159,6 +159,8 @@ SIGNATURES = {
     "d3_seg_eval_max_inst": (i32, []),
     "d3_seg_eval_ws_bytes": (sz, [i32, i32]),
     "d3_seg_eval": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp, i32, vp, vp, i32, i64, C.c_ulonglong, vp, vp, vp, vp, vp, vp, sz, vp]),
+    "d3_lsap_batched": (i32, [vp, vp, i32, i32, i32, vp, vp, vp]),
+    "d3_dense_caption_assign": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]),
     "d3_scene_limits": (i32, [pi, pi, pi]),
     "d3_scene_transform": (i32, [vp, i32, vp, f64, i32, vp, vp, vp]),
     "d3_scene_reduce": (i32, [vp, vp, i32, vp, vp]),

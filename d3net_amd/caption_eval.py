@@ -3,9 +3,13 @@ CIDEr@kIoU corpus scoring -- the reference's `lib/captioning/eval_helper.py:102-
 `eval_caption_step`, the candidate filtering of `eval_caption_epoch`) and `lib/utils/bbox.py:571-757`
 (`generalized_box3d_iou` for axis-aligned boxes, `box3d_iou_batch_tensor`).
 
-The (B, K1, K2) generalised-IoU cost matrix is computed batched on whatever device the boxes live on (the reference loops
-over the batch in python to mask the padded GT columns); the Hungarian assignment stays scipy on the host, as in the
-reference; CIDEr is d3net_amd.cider (bit-identical to lib/capeval/cider).  BLEU / ROUGE / METEOR are not restated (METEOR
+The assignment has two forms that give the same pairs.  On the device (`assign_boxes_device`, csrc/assign.hip): one launch, one
+workgroup per scene, computes the -GIoU cost from the boxes and solves the assignment with scipy's algorithm and tie order; the
+cost matrix is never stored and nothing is read back.  On the host (the reference's form, `device_assign=False`): the
+(B, K1, K2) generalised-IoU cost matrix is computed batched on whatever device the boxes live on (the reference loops over the
+batch in python to mask the padded GT columns), copied to the host and handed to scipy scene by scene.  `device_assign=None`
+takes the device form when the boxes are on a GPU and K, G <= 256 (DESIGN.md section 3.6 has the measurement behind that
+default).  CIDEr is d3net_amd.cider (bit-identical to lib/capeval/cider).  BLEU / ROUGE / METEOR are not restated (METEOR
 needs a Java runtime).  Pinned to golden vectors produced by the reference's own functions
 (tests/golden/gen_caption_eval_golden.py).
 
@@ -75,29 +79,95 @@ def decode_caption(tokens, idx2word, special_tokens):
     return " ".join(out)
 
 
+DEVICE_ASSIGN_MAX = 256          # rows / columns per scene of csrc/assign.hip
+_ASSIGN_ERRORS = {1: "matrix contains invalid numeric entries", 2: "cost matrix is infeasible"}   # scipy's messages
+
+
+def _center_cost(pred_boxes, gt_boxes):
+    return torch.cdist(pred_boxes.mean(2).float(), gt_boxes.mean(2).float())
+
+
+def _assign_launch(pred_boxes, gt_boxes, nactual, strategy, return_cost):
+    """-> per_gt (B, G) int32, status (B) int32, cost (B, K, G) or None; stream-ordered, nothing read back"""
+    import ctypes as C
+    from . import _lib
+    if strategy not in ("giou", "center"):
+        raise ValueError("invalid strategy.")
+    if not pred_boxes.is_cuda:
+        raise ValueError("assign_boxes_device needs the boxes on a GPU (device_assign=False is the host path)")
+    B, K, G = pred_boxes.shape[0], pred_boxes.shape[1], gt_boxes.shape[1]
+    if K > DEVICE_ASSIGN_MAX or G > DEVICE_ASSIGN_MAX:
+        raise ValueError("assign_boxes_device: K = %d, G = %d exceed the kernel's %d" % (K, G, DEVICE_ASSIGN_MAX))
+    dev = pred_boxes.device
+    per_gt = torch.empty((B, G), dtype=torch.int32, device=dev)
+    status = torch.empty((B,), dtype=torch.int32, device=dev)
+    if B == 0 or K == 0 or G == 0:
+        return per_gt.zero_(), status.zero_(), (torch.zeros((B, K, G), device=dev) if return_cost else None)
+    na = nactual.to(device=dev, dtype=torch.int32).contiguous()
+    p = lambda t: C.c_void_p(t.data_ptr())
+    with torch.cuda.device(dev):
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        if strategy == "giou":
+            pb, gb = pred_boxes.detach().float().contiguous(), gt_boxes.detach().float().contiguous()
+            cost = torch.empty((B, K, G), dtype=torch.float32, device=dev) if return_cost else None
+            _lib.check(_lib.lib().d3_dense_caption_assign(p(pb), p(gb), p(na), B, K, G, p(per_gt), p(status),
+                                                          p(cost) if cost is not None else None, stream), "dense_caption_assign")
+        else:
+            cost = _center_cost(pred_boxes.detach(), gt_boxes.detach()).contiguous()
+            _lib.check(_lib.lib().d3_lsap_batched(p(cost), p(na), B, K, G, p(per_gt), p(status), stream), "lsap_batched")
+    return per_gt, status, (cost if return_cost else None)
+
+
+def _raise_on_status(status_host):
+    for st in status_host.tolist():
+        if st != 0:
+            raise ValueError(_ASSIGN_ERRORS.get(st, "assignment failed (status %d)" % st))
+
+
+def assign_boxes_device(pred_boxes, gt_boxes, nactual, strategy="giou", return_cost=False):
+    """Hungarian assignment of proposals (B,K,8,3) to the first nactual[b] GT boxes (B,G,8,3) in one launch (csrc/assign.hip)
+    -> per_gt (B,G) int64 on the device: per_gt[b, g] = the proposal assigned to GT box g, 0 where none (with return_cost:
+    also the (B,K,G) cost the kernel solved).  "giou": the cost is computed inside the kernel; "center": torch.cdist, the host
+    path's own bits, handed to the solver.  Raises scipy's ValueError for a non-finite cost in a valid column."""
+    per_gt, status, cost = _assign_launch(pred_boxes, gt_boxes, nactual, strategy, return_cost)
+    _raise_on_status(status.cpu())
+    return (per_gt.long(), cost) if return_cost else per_gt.long()
+
+
 def assign_dense_caption(pred_captions, pred_boxes, gt_boxes, gt_box_ids, gt_box_masks, gt_scene_list, idx2word,
-                         special_tokens, strategy="giou"):
-    """eval_helper.py:102-246: Hungarian assignment of proposals to GT boxes, the matched proposal's caption per GT box"""
+                         special_tokens, strategy="giou", device_assign=None):
+    """eval_helper.py:102-246: Hungarian assignment of proposals to GT boxes, the matched proposal's caption per GT box.
+    device_assign (default: when the boxes live on the GPU and K, G <= 256): cost and assignment run as one kernel and stay on
+    the device; False: the reference's form, cost matrix to the host and scipy scene by scene."""
     B, ngt = gt_box_ids.shape
     nactual = gt_box_masks.sum(1).long()
-    if strategy == "giou":
-        cost = -generalized_box3d_iou(pred_boxes, gt_boxes, nactual)
-    elif strategy == "center":
-        cost = torch.cdist(pred_boxes.mean(2).float(), gt_boxes.mean(2).float())
-    else:
+    if strategy not in ("giou", "center"):
         raise ValueError("invalid strategy.")
-    cost = cost.detach().cpu().numpy()
-    per_gt = torch.zeros((B, ngt), dtype=torch.int64)
-    for b in range(B):
-        n = int(nactual[b])
-        if n > 0:
-            rows, cols = linear_sum_assignment(cost[b, :, :n])
-            per_gt[b, torch.from_numpy(cols)] = torch.from_numpy(rows)
-    per_gt = per_gt.to(pred_boxes.device)
+    if device_assign is None:
+        device_assign = bool(pred_boxes.is_cuda) and max(pred_boxes.shape[1], ngt) <= DEVICE_ASSIGN_MAX
+    status = None
+    if device_assign:
+        per_gt, status, _ = _assign_launch(pred_boxes, gt_boxes, nactual, strategy, False)
+        per_gt = per_gt.long()
+    else:
+        if strategy == "giou":
+            cost = -generalized_box3d_iou(pred_boxes, gt_boxes, nactual)
+        else:
+            cost = _center_cost(pred_boxes, gt_boxes)
+        cost = cost.detach().cpu().numpy()
+        per_gt = torch.zeros((B, ngt), dtype=torch.int64)
+        for b in range(B):
+            n = int(nactual[b])
+            if n > 0:
+                rows, cols = linear_sum_assignment(cost[b, :, :n])
+                per_gt[b, torch.from_numpy(cols)] = torch.from_numpy(rows)
+        per_gt = per_gt.to(pred_boxes.device)
     matched = torch.gather(pred_boxes, 1, per_gt[:, :, None, None].expand(B, ngt, 8, 3))
     ious = box3d_iou(matched.reshape(-1, 8, 3), gt_boxes.reshape(-1, 8, 3)).reshape(B, ngt).cpu()
     caps = torch.gather(pred_captions, 1, per_gt[:, :, None].expand(B, ngt, pred_captions.shape[2])).cpu()
     matched_h, gt_h, masks, ids = matched.cpu(), gt_boxes.cpu(), gt_box_masks.cpu(), gt_box_ids.cpu()
+    if status is not None:
+        _raise_on_status(status.cpu())      # after the copies above: the device path adds no synchronisation of its own
     candidates = {}
     for b in range(B):
         for g in range(ngt):

@@ -792,6 +792,23 @@ int d3_seg_eval(const int *gt_sem, const int *gt_inst, const int *pred_sem, cons
                 unsigned long long inst_class_mask, int *confusion, int *gt_stats, int *pred_stats, int *inter, int *status, void *ws,
                 size_t ws_bytes, void *stream);
 
+/* ---- dense-caption assignment (csrc/assign.hip) ------------------------------------------------------------------------------
+ * The Hungarian step of the captioning evaluation, one workgroup per scene, no host round trip.
+ * d3_lsap_batched: scipy.optimize.linear_sum_assignment(cost[b, :, :ncols[b]]) for every scene b, as the loop of
+ *   lib/captioning/eval_helper.py:120-182 (box_assignment) calls it.  cost (B,R,C) float32; ncols (B) int32, clamped to [0, C];
+ *   per_col (B,C) int32: per_col[b, col] = row for the assigned pairs, every other element 0 (what `per_gt[b, cols] = rows`
+ *   leaves on the host; the kernel writes all B * C elements); status (B) int32: 0 solved, 1 a non-finite cost in a valid
+ *   column (scipy raises ValueError), 2 infeasible; per_col[b] is all 0 unless status[b] == 0.  float64 solver state, scipy's
+ *   tie order.  R > 256 or C > 256: D3_ERR_RANGE before any launch.
+ * d3_dense_caption_assign: the same solve with cost = -GIoU(proposal, GT) computed inside the kernel in float32, in the
+ *   operation order of lib/utils/bbox.py generalized_box3d_iou (axis-aligned path, rotated_boxes=False) as
+ *   d3net_amd.caption_eval restates it.  pred_boxes (B,K,8,3), gt_boxes (B,G,8,3) float32 corners; nactual (B) int32 valid GT
+ *   boxes; per_gt (B,G) int32 and status (B) as above; cost_out: NULL, or (B,K,G) float32 that receives the cost (0 in the
+ *   padded columns).  K > 256 or G > 256: D3_ERR_RANGE before any launch. */
+int d3_lsap_batched(const float *cost, const int *ncols, int B, int R, int C, int *per_col, int *status, void *stream);
+int d3_dense_caption_assign(const float *pred_boxes, const float *gt_boxes, const int *nactual, int B, int K, int G, int *per_gt,
+                            int *status, float *cost_out, void *stream);
+
 /* ---- PointGroup scene preparation (csrc/scene_prep.hip, driven by d3net_amd/scene_prep.py) ----------------------------------
  * One scene of n points: xyz (n,3) float32, ids / sem (n) int32 (ids -1 = none).  Coordinates are fp64 (numpy's float32 @ float64
  * promotion) unless fp32 != 0 (the validation path, float32 throughout like the reference's `points.copy() * scale`).
