@@ -161,6 +161,8 @@ SIGNATURES = {
     "d3_seg_eval": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp, i32, vp, vp, i32, i64, C.c_ulonglong, vp, vp, vp, vp, vp, vp, sz, vp]),
     "d3_lsap_batched": (i32, [vp, vp, i32, i32, i32, vp, vp, vp]),
     "d3_dense_caption_assign": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]),
+    "d3_det_match": (i32, [vp, vp, vp, vp, f64, vp, vp, vp, i32, i32, i32, i32, C.POINTER(f64), i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "d3_det_ap": (i32, [vp, vp, vp, i32, i64, i32, i32, vp, vp]),
     "d3_scene_limits": (i32, [pi, pi, pi]),
     "d3_scene_transform": (i32, [vp, i32, vp, f64, i32, vp, vp, vp]),
     "d3_scene_reduce": (i32, [vp, vp, i32, vp, vp]),

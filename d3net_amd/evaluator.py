@@ -1,9 +1,11 @@
 """Detection evaluator: class-aware 3D NMS -> per-class precision/recall -> VOC AP -> mAP, as in the reference
 (lib/det/ap_helper.py:24-150 parse_predictions, :152-193 parse_groundtruths, :195-249 APCalculator;
 lib/det/nms.py:110-150 nms_3d_faster_samecls; lib/det/eval_det.py:21-52 voc_ap, :74-158 eval_det_cls, :165-204 eval_det;
-lib/det/box_util.py:97-121 box3d_iou).  Host-side numpy like the reference (it is an epoch-end metric, not a per-step
-kernel), vectorised over boxes instead of the reference's per-box python loops; float64 arithmetic as numpy does there.
-Used for the mAP@0.5 parity report (HIP detector vs CPU oracle on identical weights and scenes)."""
+lib/det/box_util.py:97-121 box3d_iou).  The functions down to APCalculator are host-side numpy like the reference, vectorised
+over boxes instead of the reference's per-box python loops, float64 arithmetic as numpy does there; they are the form pinned to
+the reference's own numbers and the one the mAP@0.5 parity report uses (HIP detector vs CPU oracle on identical weights and
+scenes).  DetectionEvaluator below them is the same metric on the device (csrc/nms.hip + csrc/det_eval.hip): nothing is read
+back per batch, one small table at the end."""
 import numpy as np
 
 POST_DICT = {"remove_empty_box": False, "use_3d_nms": True, "nms_iou": 0.25, "use_old_type_nms": False, "cls_nms": True,
@@ -209,3 +211,159 @@ class APCalculator:
 
     def reset(self):
         self.gt_map_cls, self.pred_map_cls, self.scan_cnt = {}, {}, 0
+
+
+# ------------------------------------------------------------------------------------------------- device path (csrc/det_eval.hip)
+DET_MAX_BOXES, DET_MAX_THRESHOLDS = 256, 4
+_DET_KEYS = ("proposal_bbox_batched", "proposal_sem_cls_batched", "proposal_batch_mask", "proposal_scores_batched",
+             "gt_bbox", "gt_bbox_label", "sem_cls_label")
+
+
+def map_pred_classes(sem):
+    """proposal_sem_cls_batched -> int32 evaluation classes as parse_predictions maps them (sem - 2, negative -> 17); a value that
+    is no integer matches no class there and becomes -1"""
+    import torch
+    cls = sem.detach().float() - 2
+    cls = torch.where(cls < 0, torch.full_like(cls, 17.0), cls)
+    ci = cls.to(torch.int32)
+    return torch.where(ci.float() == cls, ci, torch.full_like(ci, -1)).contiguous()
+
+
+def det_match_device(boxes, cls, scores, pick, conf_thresh, gt_boxes, gt_mask, gt_cls, thresholds, num_class=18, status=None):
+    """one d3_det_match launch: boxes (B,K,8,3) f32, cls (B,K) i32 mapped classes, scores (B,K) f32, pick (B,K) f32, gt_boxes
+    (B,G,8,3) f32, gt_mask (B,G) f32, gt_cls (B,G) i32, all contiguous on one GPU -> dict of device tensors: kept, cls, score,
+    ovmax (f64), jmax, tp (bit q: true positive at thresholds[q]) (B,K); gt_count (B,num_class); status (1,) int32, OR-ed into
+    when given.  Nothing is read back."""
+    import ctypes as C
+    import torch
+    from . import _lib
+    B, K = scores.shape
+    G = gt_mask.shape[1]
+    dev = scores.device
+    i32 = lambda *s: torch.empty(s, dtype=torch.int32, device=dev)
+    out = dict(kept=i32(B, K), cls=i32(B, K), score=torch.empty((B, K), dtype=torch.float32, device=dev),
+               ovmax=torch.empty((B, K), dtype=torch.float64, device=dev), jmax=i32(B, K), tp=i32(B, K), gt_count=i32(B, num_class),
+               status=status if status is not None else torch.zeros(1, dtype=torch.int32, device=dev))
+    thr = (C.c_double * len(thresholds))(*[float(t) for t in thresholds])
+    p = lambda t: C.c_void_p(t.data_ptr())
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().d3_det_match(p(boxes), p(cls), p(scores), p(pick), float(conf_thresh), p(gt_boxes), p(gt_mask), p(gt_cls),
+                                           B, K, G, num_class, thr, len(thresholds), p(out["kept"]), p(out["cls"]), p(out["score"]),
+                                           p(out["ovmax"]), p(out["jmax"]), p(out["tp"]), p(out["gt_count"]), p(out["status"]),
+                                           C.c_void_p(torch.cuda.current_stream().cuda_stream)), "det_match")
+    return out
+
+
+def det_ap_device(kept, cls, score, tp, gt_count, num_thresholds, num_class=18):
+    """flat record tensors (n,) in record order (scene sequence number, then proposal index) and gt_count (S,num_class) -> table
+    (T,num_class,4) float64 on the device = [AP, last recall, detections, present].  One stable sort on the key (class, descending
+    score) -- equal scores keep their record order -- and one d3_det_ap launch; nothing is read back."""
+    import ctypes as C
+    import torch
+    from . import _lib
+    dev = gt_count.device
+    b = score.view(torch.int32).to(torch.int64)
+    asc = torch.where(b >= 0, b + (1 << 31), -1 - b)                     # float32 order as an unsigned 32-bit key
+    key = torch.where(kept == 1, cls.to(torch.int64) * (1 << 32) + ((1 << 32) - 1 - asc), torch.full_like(b, num_class << 32))
+    skey, order = torch.sort(key, stable=True)
+    tp_sorted = tp[order].contiguous()
+    bounds = torch.searchsorted(skey, torch.arange(num_class + 1, device=dev, dtype=torch.int64) * (1 << 32)).to(torch.int32).contiguous()
+    table = torch.empty((num_thresholds, num_class, 4), dtype=torch.float64, device=dev)
+    p = lambda t: C.c_void_p(t.data_ptr()) if t.numel() else None
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().d3_det_ap(p(tp_sorted), p(bounds), p(gt_count), gt_count.shape[0], tp_sorted.numel(), num_class,
+                                        num_thresholds, p(table), C.c_void_p(torch.cuda.current_stream().cuda_stream)), "det_ap")
+    return table
+
+
+class DetectionEvaluator:
+    """parse_predictions + parse_groundtruths + one APCalculator per threshold, on the device: `add_batch` runs the class-aware NMS
+    and the match kernel and keeps the per-slot records on the GPU (no read-back), `compute_metrics` sorts them once, runs the AP
+    kernel and reads one small table back -> a list, in threshold order, of the dicts APCalculator(thr).compute_metrics() returns.
+    Exactly tied scores: descending score, then scene sequence number, then proposal index (numpy's argsort, which the host
+    path and the reference use, leaves that order to its sort implementation)."""
+
+    def __init__(self, thresholds=(0.25, 0.5), post_dict=POST_DICT, num_class=18, class2type_map=None):
+        cfg = dict(POST_DICT); cfg.update(post_dict or {})
+        if not (cfg["use_3d_nms"] and cfg["cls_nms"] and not cfg["remove_empty_box"] and cfg["per_class_proposal"]):
+            raise ValueError("DetectionEvaluator: only the configuration the reference uses (3D class-aware NMS, per-class proposals)")
+        self.thresholds = tuple(float(t) for t in thresholds)
+        if not 1 <= len(self.thresholds) <= DET_MAX_THRESHOLDS:
+            raise ValueError("DetectionEvaluator: 1 to %d thresholds" % DET_MAX_THRESHOLDS)
+        if not 1 <= num_class <= 256:
+            raise ValueError("DetectionEvaluator: num_class in [1, 256]")
+        self.cfg, self.num_class, self.class2type_map = cfg, int(num_class), class2type_map
+        self.reset()
+
+    def reset(self):
+        self._records, self._status, self.table = [], None, None
+
+    def _checked(self, data_dict):
+        import torch
+        missing = [k for k in _DET_KEYS if k not in data_dict]
+        if missing:
+            raise ValueError("DetectionEvaluator.add_batch: missing %s" % missing)
+        boxes, sem, mask, scores, gtb, gtm, gtc = (data_dict[k] for k in _DET_KEYS)
+        for k in _DET_KEYS:
+            if not torch.is_tensor(data_dict[k]) or not data_dict[k].is_cuda or data_dict[k].device != boxes.device:
+                raise ValueError("DetectionEvaluator.add_batch: %s must be a tensor on the GPU of the proposals" % k)
+        if self._status is not None and self._status.device != boxes.device:
+            raise ValueError("DetectionEvaluator.add_batch: the batches of one evaluation live on one device")
+        if boxes.dim() != 4 or tuple(boxes.shape[2:]) != (8, 3) or gtb.dim() != 4 or tuple(gtb.shape[2:]) != (8, 3) or gtb.shape[0] != boxes.shape[0]:
+            raise ValueError("DetectionEvaluator.add_batch: corners (B,K,8,3) and (B,G,8,3) expected")
+        B, K, G = boxes.shape[0], boxes.shape[1], gtb.shape[1]
+        if B < 1 or K > DET_MAX_BOXES or G > DET_MAX_BOXES:
+            raise ValueError("DetectionEvaluator.add_batch: B >= 1, K <= %d and G <= %d (got B %d, K %d, G %d)" % (DET_MAX_BOXES, DET_MAX_BOXES, B, K, G))
+        for k, t, n in ((_DET_KEYS[1], sem, K), (_DET_KEYS[2], mask, K), (_DET_KEYS[3], scores, K), (_DET_KEYS[5], gtm, G), (_DET_KEYS[6], gtc, G)):
+            if tuple(t.shape) != (B, n):
+                raise ValueError("DetectionEvaluator.add_batch: %s must be (%d, %d)" % (k, B, n))
+        ints = (torch.int32, torch.int64)
+        for k, t, ok in ((_DET_KEYS[0], boxes, (torch.float32,)), (_DET_KEYS[3], scores, (torch.float32,)), (_DET_KEYS[4], gtb, (torch.float32,)),
+                         (_DET_KEYS[1], sem, (torch.float32,) + ints), (_DET_KEYS[2], mask, (torch.float32, torch.bool, torch.uint8) + ints),
+                         (_DET_KEYS[5], gtm, (torch.float32, torch.bool, torch.uint8) + ints), (_DET_KEYS[6], gtc, ints)):
+            if t.dtype not in ok:
+                raise ValueError("DetectionEvaluator.add_batch: %s has dtype %s, expected one of %s" % (k, t.dtype, ok))
+        return boxes, sem, scores, gtb, gtm, gtc, B, K
+
+    def add_batch(self, data_dict):
+        """the seven keys parse_predictions and parse_groundtruths read, as GPU tensors"""
+        import torch
+        boxes, sem, scores, gtb, gtm, gtc, B, K = self._checked(data_dict)
+        dev = boxes.device
+        if self._status is None:
+            self._status = torch.zeros(1, dtype=torch.int32, device=dev)
+        if K > 0:
+            pick = nms_pred_mask_device(data_dict, self.cfg["nms_iou"], self.cfg["use_old_type_nms"])
+        else:
+            pick = torch.empty((B, 0), dtype=torch.float32, device=dev)
+        r = det_match_device(boxes.detach().contiguous(), map_pred_classes(sem), scores.detach().contiguous(), pick, self.cfg["conf_thresh"],
+                             gtb.detach().contiguous(), (gtm.detach() == 1).float().contiguous(), gtc.detach().to(torch.int32).contiguous(),
+                             self.thresholds, self.num_class, self._status)
+        self._records.append(tuple(r[k].view(-1) for k in ("kept", "cls", "score", "tp")) + (r["gt_count"],))
+
+    def compute_metrics(self):
+        import torch
+        from . import _lib
+        if not self._records:
+            raise ValueError("DetectionEvaluator.compute_metrics: no batch was added")
+        kept, cls, score, tp, gt_count = (torch.cat([r[i] for r in self._records]) for i in range(5))
+        table = det_ap_device(kept, cls, score, tp, gt_count, len(self.thresholds), self.num_class)
+        host = torch.cat([table.view(-1), self._status.to(torch.float64)]).cpu().numpy()          # the one read-back
+        status = int(host[-1])
+        if status & 1:
+            raise _lib.D3Error("DetectionEvaluator: a kept detection or a valid GT box holds a non-finite coordinate")
+        if status & 2:
+            raise _lib.D3Error("DetectionEvaluator: a valid GT box has a class outside [0, %d)" % self.num_class)
+        self.table = host[:-1].reshape(len(self.thresholds), self.num_class, 4)
+        name = lambda k: self.class2type_map[k] if self.class2type_map else str(k)
+        out = []
+        for q in range(len(self.thresholds)):
+            t = self.table[q]
+            present = [c for c in range(self.num_class) if t[c, 3] == 1]
+            ret = {"%s Average Precision" % name(c): t[c, 0] for c in present}
+            ret["mAP"] = np.mean([t[c, 0] for c in present])
+            for c in present:
+                ret["%s Recall" % name(c)] = t[c, 1]
+            ret["AR"] = np.mean([t[c, 1] for c in present])
+            out.append(ret)
+        return out

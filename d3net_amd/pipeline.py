@@ -266,6 +266,12 @@ class PipelineNet(nn.Module):
             self.log("val_score/{}".format(k), v)
         return log
 
+    def evaluate_detection(self, batches, evaluator=None):
+        """detection mAP of the detector over `batches` (scripts/eval.py:128-166): PointGroup.evaluate_detection"""
+        if self.no_detection:
+            raise NotImplementedError("evaluate_detection needs the detector (model.no_detection is set)")
+        return self.detector.evaluate_detection(batches, evaluator)
+
     def forward(self, data_dict):
         """inference entry point (model/pipeline.py:894-925): detector -> speaker -> listener, whichever exist"""
         if not self.no_detection:

@@ -931,6 +931,23 @@ class PointGroup(nn.Module):
             self.train(was_training)
         return ev.instance_results()[0], ev.semantic_results()[0]
 
+    def evaluate_detection(self, batches, evaluator=None):
+        """Detection AP / recall per class, mAP and AR of the predictions over `batches` (collated batches that carry gt_bbox,
+        gt_bbox_label and sem_cls_label on the GPU), the library's form of scripts/eval.py:128-166 (eval_detection): feed in
+        eval() mode, NMS + matching of each batch on the device (evaluator.DetectionEvaluator, no read-back per batch)
+        -> one APCalculator-shaped dict per IoU threshold (0.25 and 0.5 by default)"""
+        from .evaluator import DetectionEvaluator
+        ev = evaluator if evaluator is not None else DetectionEvaluator()
+        was_training = self.training
+        self.eval()
+        try:
+            with torch.no_grad():
+                for batch in batches:
+                    ev.add_batch(self.feed(batch, self.current_epoch))
+        finally:
+            self.train(was_training)
+        return ev.compute_metrics()
+
     def training_step(self, data_dict, idx=0):
         """(reference :513-528) minus the Lightning logging."""
         _mark("begin")

@@ -809,6 +809,31 @@ int d3_lsap_batched(const float *cost, const int *ncols, int B, int R, int C, in
 int d3_dense_caption_assign(const float *pred_boxes, const float *gt_boxes, const int *nactual, int B, int K, int G, int *per_gt,
                             int *status, float *cost_out, void *stream);
 
+/* ---- detection mAP (csrc/det_eval.hip, driven by d3net_amd.evaluator.DetectionEvaluator) --------------------------------------
+ * d3_det_match: per validation batch, one workgroup per scene, in place of the list building of lib/det/ap_helper.py:80-150
+ *   (parse_predictions after its NMS), :152-193 (parse_groundtruths) and the IoU walk of lib/det/eval_det.py:113-136.
+ *   pred_corners (B,K,8,3) float32; pred_cls (B,K) int32 already mapped (sem - 2, negative -> 17); scores (B,K) float32; pick (B,K)
+ *   float32, the NMS mask; gt_corners (B,G,8,3) float32, gt_mask (B,G) float32 (== 1: valid), gt_cls (B,G) int32; thresholds:
+ *   T doubles in HOST memory.  A detection is kept when pick == 1 && score > (float)conf_thresh && 0 <= class < num_class
+ *   (float32, as numpy compares a float32 score with a Python float).  Per slot (B,K): kept 0/1, cls_out (-1 when not kept), score_out, ovmax float64 (box_util.py:97-121 box3d_iou in float64, -inf when no
+ *   valid GT box of the class), jmax (lowest j on equal IoU, -1), tp_bits (bit q: true positive at thresholds[q]; see the order-free
+ *   rule in det_eval.hip: exactly eval_det_cls's result with the detections of a class taken in descending score, exact ties
+ *   by scene then proposal index).  gt_count (B,num_class) int32 valid GT boxes per class.  *status (device int32) is OR-ed with
+ *   1 when a kept detection or a valid GT box holds a non-finite coordinate, 2 when a valid GT box's class is outside
+ *   [0, num_class) (that box is skipped); the caller zeroes it.
+ *   K > 256, G > 256, T outside [1, 4], B < 1 or num_class > 256: D3_ERR_RANGE before any launch.
+ * d3_det_ap: the epoch-end pass of eval_det.py:148-156 and voc_ap :21-52 (use_07_metric=False), one workgroup per (class,
+ *   threshold).  tp_sorted (N) int32: the tp_bits of the kept records ordered by class, then descending score, then record order;
+ *   seg_offsets (num_class + 1) int32: class c owns [seg_offsets[c], seg_offsets[c+1]); gt_count (S,num_class) int32 of all S scenes.
+ *   table (T,num_class,4) float64 = [AP, last recall (0 without detections), detections, present (any GT or any detection)].
+ *   T outside [1, 4] or num_class > 256: D3_ERR_RANGE before any launch. */
+int d3_det_match(const float *pred_corners, const int *pred_cls, const float *scores, const float *pick, double conf_thresh,
+                 const float *gt_corners, const float *gt_mask, const int *gt_cls, int B, int K, int G, int num_class,
+                 const double *thresholds, int T, int *kept, int *cls_out, float *score_out, double *ovmax, int *jmax, int *tp_bits,
+                 int *gt_count, int *status, void *stream);
+int d3_det_ap(const int *tp_sorted, const int *seg_offsets, const int *gt_count, int S, long long N, int num_class, int T,
+              double *table, void *stream);
+
 /* ---- PointGroup scene preparation (csrc/scene_prep.hip, driven by d3net_amd/scene_prep.py) ----------------------------------
  * One scene of n points: xyz (n,3) float32, ids / sem (n) int32 (ids -1 = none).  Coordinates are fp64 (numpy's float32 @ float64
  * promotion) unless fp32 != 0 (the validation path, float32 throughout like the reference's `points.copy() * scale`).
