@@ -27,6 +27,20 @@
 #define BQ_SUPER 64
 #define BQ_CAP 1000  // reference: int idx_temp[1000] (bfs_cluster.cu:20,38-44)
 
+// hash slot of the cell grid: (key, first sorted position of the cell, points in the cell) -- ONE 16-byte load answers a probe
+struct __attribute__((aligned(16))) BqSlot { unsigned long long key; int start, count; };
+
+// the cell grid of the padded form (d3_ballquery_padded)
+struct BqGrid {
+    unsigned long long *key;
+    int *slot32, *skey;               // a point's cell slot (the sort key) / the sorted slots
+    BqSlot *tbl;
+    int *pid, *sidx, *head, *rid, *cstart, *cslot, *tlead, *leader_of, *scal, *dense;
+    float *sxyz, *cbox;
+    void *temp; size_t temp_bytes;
+    size_t cap;
+};
+
 struct BqWs {
     float *clo, *chi;  // chunk boxes   (nchunks,3) each
     float *slo, *shi;  // super boxes   (nsuper,3) each
@@ -35,14 +49,14 @@ struct BqWs {
     int *total;        // 1
     void *temp; size_t temp_bytes;
     int nchunks, nsuper;
+    BqGrid grid;       // sits behind the scan's tables
+    size_t bytes;      // what d3_ballquery_ws_bytes reports: all of the above + 256
 };
 
-struct BqGrid;
-static void bqg_carve(D3Carver &c, int n, BqGrid &g);
-static bool bq_carve(void *ws, size_t ws_bytes, int n, BqWs &w, BqGrid *g = nullptr);
-static bool bq_carve(void *ws, size_t ws_bytes, int n, BqWs &w, BqGrid *g) {
-    D3Carver c(ws, ws_bytes);
-    size_t nn = (size_t)(n > 0 ? n : 1);
+static size_t bqg_cap(int n) { size_t c = 1024; while (c < (size_t)n * 2) c <<= 1; return c; }
+
+static void bq_layout(D3Carver &c, int n, BqWs &w) {
+    const size_t nn = (size_t)(n > 0 ? n : 1);
     w.nchunks = (int)((nn + BQ_CHUNK - 1) / BQ_CHUNK);
     w.nsuper = (w.nchunks + BQ_SUPER - 1) / BQ_SUPER;
     w.clo = c.take<float>((size_t)w.nchunks * 3);
@@ -54,42 +68,41 @@ static bool bq_carve(void *ws, size_t ws_bytes, int n, BqWs &w, BqGrid *g) {
     w.total = c.take<int>(64);
     w.temp_bytes = d3_scan_temp_bytes(n);
     w.temp = c.take<char>(w.temp_bytes);
-    if (g) bqg_carve(c, n, *g);        // the cell grid of the padded form sits behind the scan's tables
-    return ws != nullptr && c.ok();
+    BqGrid &g = w.grid;
+    g.cap = bqg_cap(n);
+    g.key = c.take<unsigned long long>(nn); g.slot32 = c.take<int>(nn); g.skey = c.take<int>(nn); g.tbl = c.take<BqSlot>(g.cap);
+    g.pid = c.take<int>(nn); g.sidx = c.take<int>(nn); g.head = c.take<int>(nn); g.rid = c.take<int>(nn);
+    g.cstart = c.take<int>(nn + 1); g.cslot = c.take<int>(nn); g.tlead = c.take<int>(g.cap); g.leader_of = c.take<int>(nn);
+    g.scal = c.take<int>(64); g.dense = c.take<int>(nn);
+    g.sxyz = c.take<float>(nn * 3); g.cbox = c.take<float>(nn * 6);
+    g.temp_bytes = d3_sort_pairs_temp_bytes(n);
+    if (w.temp_bytes > g.temp_bytes) g.temp_bytes = w.temp_bytes;      // (the grid scans n ints too)
+    g.temp = c.take<char>(g.temp_bytes);
+    w.bytes = c.off + 256;
+}
+static bool bq_carve(void *ws, size_t ws_bytes, int n, BqWs &w) {
+    D3Carver c(ws, ws_bytes);
+    bq_layout(c, n, w);
+    return c.ok();
+}
+extern "C" size_t d3_ballquery_ws_bytes(int n) {
+    D3Carver c(nullptr, 0);
+    BqWs w;
+    bq_layout(c, n, w);
+    return w.bytes;
 }
 
 // the optional hit stash (n * BQ_CAP ints, 400 MB at n = 100k: HBM is 288 GB) sits behind the base workspace; both phases
 // use it iff the caller's workspace is big enough (d3_ballquery_ws_bytes_single_pass)
-extern "C" size_t d3_ballquery_ws_bytes(int n);
-static int *bq_stash(void *ws, size_t ws_bytes, int n) {
-    const size_t base = d3_align(d3_ballquery_ws_bytes(n), 4096);
-    const size_t need = base + (size_t)(n > 0 ? n : 1) * BQ_CAP * sizeof(int);
-    return (ws != nullptr && ws_bytes >= need) ? (int *)((char *)ws + base) : nullptr;
-}
 extern "C" size_t d3_ballquery_ws_bytes_single_pass(int n) {
     return d3_align(d3_ballquery_ws_bytes(n), 4096) + (size_t)(n > 0 ? n : 1) * BQ_CAP * sizeof(int);
 }
-
-static size_t bqg_cap_host(int n) { size_t c = 1024; while (c < (size_t)n * 2) c <<= 1; return c; }
-extern "C" size_t d3_ballquery_ws_bytes(int n) {
-    BqWs w;
-    D3Carver c(nullptr, 0);
-    size_t nn = (size_t)(n > 0 ? n : 1);
-    int nchunks = (int)((nn + BQ_CHUNK - 1) / BQ_CHUNK), nsuper = (nchunks + BQ_SUPER - 1) / BQ_SUPER;
-    c.take<float>((size_t)nchunks * 3); c.take<float>((size_t)nchunks * 3);
-    c.take<float>((size_t)nsuper * 3); c.take<float>((size_t)nsuper * 3);
-    c.take<int>(nn); c.take<int>(nn); c.take<int>(64);
-    c.take<char>(d3_scan_temp_bytes(n));
-    (void)w;
-    // + the cell grid (d3_ballquery_padded)
-    const size_t cap = bqg_cap_host(n);
-    c.take<unsigned long long>(nn); c.take<unsigned long long>(nn); c.take<char>(cap * 16);
-    c.take<int>(nn); c.take<int>(nn); c.take<int>(nn); c.take<int>(nn); c.take<int>(nn + 1); c.take<int>(nn); c.take<int>(cap); c.take<int>(nn);
-    c.take<int>(64); c.take<int>(nn); c.take<float>(nn * 3); c.take<float>(nn * 6);
-    size_t tb = d3_sort_pairs_u64_temp_bytes(n);
-    if (d3_scan_temp_bytes(n) > tb) tb = d3_scan_temp_bytes(n);
-    c.take<char>(tb);
-    return c.off + 256;
+static int *bq_stash(void *ws, size_t ws_bytes, int n, const BqWs &w) {
+    const size_t base = d3_align(w.bytes, 4096), hits = (size_t)(n > 0 ? n : 1) * BQ_CAP;
+    if (ws_bytes < base + hits * sizeof(int)) return nullptr;      // (= d3_ballquery_ws_bytes_single_pass; the last region needs no padding)
+    D3Carver c(ws, ws_bytes);
+    c.take<char>(base);
+    return c.take<int>(hits);
 }
 
 __device__ __forceinline__ float wave_min(float v) {
@@ -283,7 +296,7 @@ extern "C" int d3_ballquery_count(const float *xyz, const int *batch_idxs, const
     hipStream_t s = d3_stream(stream);
     int rc = bq_boxes(xyz, n, w, s);
     if (rc) return rc;
-    int *stash = bq_stash(ws, ws_bytes, n);
+    int *stash = bq_stash(ws, ws_bytes, n, w);
     if (stash)
         bq_scan_kernel<2><<<(n + 3) / 4, 256, 0, s>>>(xyz, batch_idxs, batch_offsets, n, radius, w.clo, w.chi, w.slo,
                                                      w.shi, w.nchunks, w.len, nullptr, stash, 0);
@@ -321,7 +334,7 @@ extern "C" int d3_ballquery_fill(const float *xyz, const int *batch_idxs, const 
     if (!bq_carve((void *)ws, ws_bytes, n, w)) return D3_ERR_WORKSPACE;
     hipStream_t s = d3_stream(stream);
     // boxes and starts are still in the workspace from the count phase; with the big workspace so are the hits
-    int *stash = bq_stash((void *)ws, ws_bytes, n);
+    int *stash = bq_stash((void *)ws, ws_bytes, n, w);
     if (stash) {
         bq_compact_kernel<<<(n + 3) / 4, 256, 0, s>>>(stash, w.len, w.start, n, idx, idx_capacity);
         D3_LAUNCH_CHECK();
@@ -357,33 +370,6 @@ extern "C" int d3_ballquery_fill(const float *xyz, const int *batch_idxs, const 
 #define BQG_EMPTY 0xFFFFFFFFFFFFFFFFull
 #define BQG_BUF 2048            // per-wave LDS hit buffer (ints) of the dense kernel
 #define BQG_BIAS 16384
-
-// hash slot: (key, first sorted position of the cell, points in the cell) -- ONE 16-byte load answers a probe
-struct __attribute__((aligned(16))) BqSlot { unsigned long long key; int start, count; };
-
-struct BqGrid {
-    unsigned long long *key;
-    int *slot32, *skey;               // a point's cell slot (the sort key) / the sorted slots
-    BqSlot *tbl;
-    int *pid, *sidx, *head, *rid, *cstart, *cslot, *tlead, *leader_of, *scal, *dense;
-    float *sxyz, *cbox;
-    void *temp; size_t temp_bytes;
-    size_t cap;
-};
-static size_t bqg_cap(int n) { size_t c = 1024; while (c < (size_t)n * 2) c <<= 1; return c; }
-static void bqg_carve(D3Carver &c, int n, BqGrid &g) {
-    const size_t nn = (size_t)(n > 0 ? n : 1);
-    g.cap = bqg_cap(n);
-    g.key = c.take<unsigned long long>(nn); g.slot32 = c.take<int>(nn); g.skey = c.take<int>(nn); g.tbl = c.take<BqSlot>(g.cap);
-    g.pid = c.take<int>(nn); g.sidx = c.take<int>(nn); g.head = c.take<int>(nn); g.rid = c.take<int>(nn);
-    g.cstart = c.take<int>(nn + 1); g.cslot = c.take<int>(nn); g.tlead = c.take<int>(g.cap); g.leader_of = c.take<int>(nn);
-    g.scal = c.take<int>(64); g.dense = c.take<int>(nn);
-    g.sxyz = c.take<float>(nn * 3); g.cbox = c.take<float>(nn * 6);
-    g.temp_bytes = d3_sort_pairs_temp_bytes(n);
-    const size_t sb = d3_scan_temp_bytes(n);
-    if (sb > g.temp_bytes) g.temp_bytes = sb;
-    g.temp = c.take<char>(g.temp_bytes);
-}
 
 __device__ __forceinline__ unsigned long long bqg_hash(unsigned long long k) {
     k ^= k >> 33; k *= 0xff51afd7ed558ccdull; k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ull; k ^= k >> 33;
@@ -840,8 +826,8 @@ extern "C" int d3_ballquery_padded(const float *xyz, const int *batch_idxs, cons
     if (n <= 0) return 0;
     if ((long long)n * BQ_CAP > 0x7FFFFFFFLL) return D3_ERR_ARG;
     BqWs w;
-    BqGrid g;
-    if (!bq_carve(ws, ws_bytes, n, w, &g)) return D3_ERR_WORKSPACE;
+    if (!bq_carve(ws, ws_bytes, n, w)) return D3_ERR_WORKSPACE;
+    BqGrid &g = w.grid;
     hipStream_t s = d3_stream(stream);
     if (d3_tune(D3T_BQ_GRID) != 0 && radius > 0.f) return bqg_padded(xyz, batch_idxs, n, radius, start_len, w, g, idx_padded, s);
     int rc = bq_boxes(xyz, n, w, s);

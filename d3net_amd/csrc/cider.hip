@@ -187,8 +187,18 @@ __global__ __launch_bounds__(64) void cd_sim_kernel(const CdVec *__restrict__ ve
     }
 }
 
+struct CdWs { unsigned long long *hkeys; int *hcnt; CdVec *vecs; };
+static void cd_layout(D3Carver &c, int SR, int E, int hash_slots, CdWs &w) {
+    w.hkeys = c.take<unsigned long long>(hash_slots);
+    w.hcnt = c.take<int>(hash_slots);
+    c.take<int>(64);
+    w.vecs = c.take<CdVec>((size_t)SR + E);
+}
 extern "C" size_t d3_cider_ws_bytes(int SR, int E, int hash_slots) {
-    return d3_align((size_t)hash_slots * 8) + d3_align((size_t)hash_slots * 4) + d3_align(256) + d3_align((size_t)(SR + E) * sizeof(CdVec));
+    D3Carver c(nullptr, 0);
+    CdWs w;
+    cd_layout(c, SR, E, hash_slots, w);
+    return c.off;
 }
 
 // tokens (R, ldt) / lens (R): the reference corpus on the device.  Batch description (small int32 device arrays):
@@ -201,13 +211,14 @@ extern "C" int d3_cider_scores(const int *tokens, int ldt, const int *lens, cons
                                int hash_slots, double *scores, int *overflow_dev, void *ws, size_t ws_bytes, void *stream) {
     D3_CLEAR();
     if (U < 1 || SR < 1 || E < 1 || hash_slots < 1024 || (hash_slots & (hash_slots - 1))) return D3_ERR_ARG;
-    if (ws_bytes < d3_cider_ws_bytes(SR, E, hash_slots)) return D3_ERR_WORKSPACE;
-    hipStream_t s = d3_stream(stream);
     D3Carver c(ws, ws_bytes);
-    unsigned long long *hkeys = c.take<unsigned long long>(hash_slots);
-    int *hcnt = c.take<int>(hash_slots);
-    c.take<int>(64);
-    CdVec *vecs = c.take<CdVec>((size_t)SR + E);
+    CdWs w;
+    cd_layout(c, SR, E, hash_slots, w);
+    if (!c.ok()) return D3_ERR_WORKSPACE;
+    hipStream_t s = d3_stream(stream);
+    unsigned long long *hkeys = w.hkeys;
+    int *hcnt = w.hcnt;
+    CdVec *vecs = w.vecs;
     D3_CHECK(hipMemsetAsync(hkeys, 0, (size_t)hash_slots * 8, s));
     D3_CHECK(hipMemsetAsync(hcnt, 0, (size_t)hash_slots * 4, s));
     D3_CHECK(hipMemsetAsync(overflow_dev, 0, sizeof(int), s));

@@ -60,8 +60,7 @@ struct ClWs {
     void *temp; size_t temp_bytes;
 };
 
-static bool cl_carve(void *ws, size_t ws_bytes, int n, ClWs &w) {
-    D3Carver c(ws, ws_bytes);
+static void cl_layout(D3Carver &c, int n, ClWs &w) {
     size_t nn = (size_t)(n > 0 ? n : 1);
     w.parent = c.take<int>(nn); w.lab = c.take<int>(nn); w.own = c.take<int>(nn); w.sizes = c.take<int>(nn);
     w.flag = c.take<int>(nn); w.cid = c.take<int>(nn); w.ksz = c.take<int>(nn); w.koff = c.take<int>(nn);
@@ -73,15 +72,16 @@ static bool cl_carve(void *ws, size_t ws_bytes, int n, ClWs &w) {
     w.ninfo = c.take<int4>(nn);
     w.temp_bytes = d3_scan_temp_bytes(n);
     w.temp = c.take<char>(w.temp_bytes);
-    return ws != nullptr && c.ok();
+}
+static bool cl_carve(void *ws, size_t ws_bytes, int n, ClWs &w) {
+    D3Carver c(ws, ws_bytes);
+    cl_layout(c, n, w);
+    return c.ok();
 }
 extern "C" size_t d3_bfs_cluster_ws_bytes(int n) {
     D3Carver c(nullptr, 0);
-    size_t nn = (size_t)(n > 0 ? n : 1);
-    for (int i = 0; i < 18; i++) c.take<int>(nn);
-    c.take<int>(64);
-    c.take<int4>(nn);
-    c.take<char>(d3_scan_temp_bytes(n));
+    ClWs w;
+    cl_layout(c, n, w);
     return c.off + 256;
 }
 

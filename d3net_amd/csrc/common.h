@@ -26,13 +26,15 @@ static inline hipStream_t d3_stream(void *s) { return (hipStream_t)s; }
 
 static inline size_t d3_align(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
 
-// carve a typed region out of a workspace; returns nullptr when it does not fit
+// carve typed, 256-byte aligned regions out of a workspace.  A layout function lists the regions once; the run carves
+// with it and checks ok() before its first launch, the *_ws_bytes query runs it on a null base (take() then returns
+// nullptr and only advances off) and reads off.
 struct D3Carver {
     char *base; size_t cap; size_t off;
     D3Carver(void *ws, size_t bytes) : base((char *)ws), cap(bytes), off(0) {}
     template <typename T> T *take(size_t count) {
         size_t bytes = d3_align(count * sizeof(T));
-        T *p = (T *)(base + off);
+        T *p = base ? (T *)(base + off) : nullptr;
         off += bytes;
         return p;
     }
@@ -60,3 +62,10 @@ int d3_sort_pairs_i32(const int *kin, int *kout, const int *vin, int *vout, int 
 size_t d3_sort_pairs_u64_temp_bytes(int n);
 int d3_sort_pairs_u64(const unsigned long long *kin, unsigned long long *kout, const int *vin, int *vout, int n, void *temp,
                       size_t temp_bytes, hipStream_t s);
+
+// batched fp32-MFMA GEMMs and column sums (implemented in hgemm.hip)
+int hg_launch(const d3_gemm_prob *probs, int nprobs, hipStream_t s);
+size_t hg_colsum_ws_bytes(int njobs, int cmax);
+// n column sums in two launches; ws >= hg_colsum_ws_bytes(n, max C)
+int hg_colsum_multi(const float *const *x, const long long *ld, const int *R, const int *C, float *const *out, const int *accum, int n,
+                    void *ws, size_t ws_bytes, hipStream_t s);

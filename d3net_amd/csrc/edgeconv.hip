@@ -18,11 +18,6 @@
 #include "common.h"
 #include <string.h>
 
-int hg_launch(const d3_gemm_prob *probs, int nprobs, hipStream_t s);
-size_t hg_colsum_ws_bytes(int njobs, int cmax);
-int hg_colsum_multi(const float *const *x, const long long *ld, const int *R, const int *C, float *const *out, const int *accum, int n,
-                    void *ws, size_t ws_bytes, hipStream_t s);
-
 #define GM_MAXK 256
 
 // adj (B,K,K) 0/1, mask (B,K) -> see d3_graph_edges in include/d3hip.h
@@ -203,13 +198,33 @@ static d3_gemm_prob ec_prob(int M, int N, float *C, long long ldc) {
     return p;
 }
 
-extern "C" size_t d3_edgeconv_ws_bytes(int Emax, int Cin, int Cout) {
-    return d3_align((size_t)Emax * 2 * Cin * 4) + d3_align((size_t)Emax * Cout * 4);
-}
 #define EC_KSPLIT 4
+// the forward's workspace, kept for the backward: gathered edge inputs and the hidden layer
+struct EcFwdWs { float *Ein, *hid; };
+static void ec_fwd_layout(D3Carver &c, long long Emax, int Cin, int Cout, EcFwdWs &w) {
+    w.Ein = c.take<float>((size_t)Emax * 2 * Cin);
+    w.hid = c.take<float>((size_t)Emax * Cout);
+}
+struct EcBwdWs { float *dm, *dh, *dE, *wpart; void *cs; size_t cs_bytes; };
+static void ec_bwd_layout(D3Carver &c, long long Emax, int Cin, int Cout, EcBwdWs &w) {
+    w.dm = c.take<float>((size_t)Emax * Cout);
+    w.dh = c.take<float>((size_t)Emax * Cout);
+    w.dE = c.take<float>((size_t)Emax * 2 * Cin);
+    w.cs_bytes = hg_colsum_ws_bytes(2, Cout);
+    w.cs = c.take<char>(w.cs_bytes);
+    w.wpart = c.take<float>((size_t)EC_KSPLIT * Cout * 2 * Cin);
+}
+extern "C" size_t d3_edgeconv_ws_bytes(int Emax, int Cin, int Cout) {
+    D3Carver c(nullptr, 0);
+    EcFwdWs w;
+    ec_fwd_layout(c, Emax, Cin, Cout, w);
+    return c.off;
+}
 extern "C" size_t d3_edgeconv_bwd_ws_bytes(int Emax, int Cin, int Cout) {
-    return d3_align((size_t)Emax * Cout * 4) * 2 + d3_align((size_t)Emax * 2 * Cin * 4) + d3_align(hg_colsum_ws_bytes(2, Cout)) +
-           d3_align((size_t)EC_KSPLIT * Cout * 2 * Cin * 4);
+    D3Carver c(nullptr, 0);
+    EcBwdWs w;
+    ec_bwd_layout(c, Emax, Cin, Cout, w);
+    return c.off;
 }
 // out = part[0] + part[1] + part[2] + part[3] (fixed order)
 __global__ void ec_sum_parts_kernel(const float *__restrict__ part, long long n, float *__restrict__ out) {
@@ -249,9 +264,12 @@ extern "C" int d3_edgeconv_fwd(const float *x, const float *W0, const float *b0,
     D3_CLEAR();
     if ((Cin & 3) || Cout > 1024 || B < 1) return D3_ERR_ARG;
     const long long Emax = (long long)B * K * L;
-    if (ws_bytes < d3_edgeconv_ws_bytes((int)Emax, Cin, Cout)) return D3_ERR_WORKSPACE;
+    D3Carver cv(ws, ws_bytes);
+    EcFwdWs f;
+    ec_fwd_layout(cv, Emax, Cin, Cout, f);
+    if (!cv.ok()) return D3_ERR_WORKSPACE;
     hipStream_t s = d3_stream(stream);
-    float *Ein = (float *)ws, *hid = (float *)((char *)ws + d3_align((size_t)Emax * 2 * Cin * 4));
+    float *Ein = f.Ein, *hid = f.hid;
     const long long tot = Emax * (Cin / 4);
     ec_gather_kernel<<<(int)((tot + 255) / 256), 256, 0, s>>>(x, src, dst, Ein, Emax, Cin);
     int rc;
@@ -305,13 +323,15 @@ extern "C" int d3_edgeconv_bwd(const float *W0, const float *W2, const int *src,
     D3_CLEAR();
     if ((Cin & 3) || Cin > 1024 || B < 1) return D3_ERR_ARG;
     const long long Emax = (long long)B * K * L;
-    if (ws2_bytes < d3_edgeconv_bwd_ws_bytes((int)Emax, Cin, Cout)) return D3_ERR_WORKSPACE;
+    D3Carver cv(ws2, ws2_bytes), cf(const_cast<void *>(ws), SIZE_MAX);      // (the forward checked its own size)
+    EcBwdWs w;
+    EcFwdWs f;
+    ec_bwd_layout(cv, Emax, Cin, Cout, w);
+    ec_fwd_layout(cf, Emax, Cin, Cout, f);
+    if (!cv.ok() || !cf.ok()) return D3_ERR_WORKSPACE;
     hipStream_t s = d3_stream(stream);
-    const float *Ein = (const float *)ws, *hid = (const float *)((const char *)ws + d3_align((size_t)Emax * 2 * Cin * 4));
-    float *dm = (float *)ws2, *dh = (float *)((char *)ws2 + d3_align((size_t)Emax * Cout * 4));
-    float *dE = (float *)((char *)ws2 + 2 * d3_align((size_t)Emax * Cout * 4));
-    float *wpart = (float *)((char *)ws2 + 2 * d3_align((size_t)Emax * Cout * 4) + d3_align((size_t)Emax * 2 * Cin * 4) +
-                             d3_align(hg_colsum_ws_bytes(2, Cout)));
+    const float *Ein = f.Ein, *hid = f.hid;
+    float *dm = w.dm, *dh = w.dh, *dE = w.dE, *wpart = w.wpart;
     (void)src;
     const long long tot = Emax * Cout;
     ec_bwd_dm_kernel<<<(int)((tot + 255) / 256), 256, 0, s>>>(d_msg, d_node, dst, dm, Emax, Cout);
@@ -331,8 +351,7 @@ extern "C" int d3_edgeconv_bwd(const float *W0, const float *W2, const int *src,
         // both bias gradients in one two-stage column sum (dm is not modified after the first block)
         const float *cx[2] = {dm, dh}; const long long cl[2] = {Cout, Cout}; const int cr[2] = {(int)Emax, (int)Emax}, cc[2] = {Cout, Cout};
         float *co[2] = {db2, db0};
-        char *cs = (char *)ws2 + 2 * d3_align((size_t)Emax * Cout * 4) + d3_align((size_t)Emax * 2 * Cin * 4);
-        if ((rc = hg_colsum_multi(cx, cl, cr, cc, co, nullptr, 2, cs, hg_colsum_ws_bytes(2, Cout), s))) return rc;
+        if ((rc = hg_colsum_multi(cx, cl, cr, cc, co, nullptr, 2, w.cs, w.cs_bytes, s))) return rc;
     }
     ec_bwd_dx_kernel<<<B * K, ((Cin + 63) / 64) * 64, 0, s>>>(dE, in_ptr, in_list, out_start, out_cnt, dx, K, K * L, Cin);
     D3_LAUNCH_CHECK();

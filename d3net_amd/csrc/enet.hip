@@ -297,11 +297,21 @@ static int en_conv(const EnConv &c, int Cout, int epi, int F, hipStream_t s) {
     return D3_ERR_ARG;
 }
 
+// two block-I/O buffers of H*W*4 floats per frame (16 ch at H/2, 64 at H/4, 128 at H/8 all fit) + two inner buffers of H*W
+// (H and W are multiples of 8, so every region is a multiple of 256 bytes and the four lie back to back)
+struct EnWs { float *bufA, *bufB, *in1, *in2; };
+static void en_layout(D3Carver &c, int F, int H, int W, EnWs &w) {
+    const size_t per = (size_t)H * W;
+    w.bufA = c.take<float>(F * per * 4); w.bufB = c.take<float>(F * per * 4);
+    w.in1 = c.take<float>(F * per); w.in2 = c.take<float>(F * per);
+}
+
 size_t d3_enet_ws_bytes(int F, int H, int W) {
     if (F <= 0 || H <= 0 || W <= 0 || (H % 8) || (W % 8)) return 0;
-    // two block-I/O buffers of H*W*4 floats per frame (16 ch at H/2, 64 at H/4, 128 at H/8 all fit) + two inner buffers of H*W
-    size_t per = (size_t)H * W;
-    return d3_align(2 * F * per * 4 * sizeof(float)) + d3_align(2 * F * per * sizeof(float));
+    D3Carver c(nullptr, 0);
+    EnWs w;
+    en_layout(c, F, H, W, w);
+    return c.off;
 }
 
 int d3_enet_forward(const float *x, int F, int H, int W, const float *params, long long n_params, const int *table, int n_table,
@@ -317,15 +327,14 @@ int d3_enet_forward(const float *x, int F, int H, int W, const float *params, lo
     if (F > EN_MAX_FRAMES || (long long)H * W * 4 >= (1ll << 31)) return D3_ERR_RANGE;
     if (F == 0) return 0;
     if (!x || !params || !out || !ws) return D3_ERR_ARG;
-    size_t need = d3_enet_ws_bytes(F, H, W);
-    if (ws_bytes < need) return D3_ERR_WORKSPACE;
+    D3Carver cv(ws, ws_bytes);
+    EnWs lw;
+    en_layout(cv, F, H, W, lw);
+    if (!cv.ok()) return D3_ERR_WORKSPACE;
     hipStream_t s = d3_stream(stream);
     D3_CLEAR();
 
-    size_t per = (size_t)H * W;
-    float *bufA = (float *)ws, *bufB = (float *)((char *)ws + d3_align(F * per * 4 * sizeof(float)));
-    float *in1 = (float *)((char *)ws + d3_align(2 * F * per * 4 * sizeof(float)));
-    float *in2 = in1 + F * per;
+    float *bufA = lw.bufA, *bufB = lw.bufB, *in1 = lw.in1, *in2 = lw.in2;
 
     int H2 = H / 2, W2 = W / 2;
     dim3 g0((H2 * W2 + EN_BLOCK - 1) / EN_BLOCK, F);

@@ -36,11 +36,17 @@ lp_features_kernel(const int *__restrict__ tokens, const int *__restrict__ lens,
     }
 }
 
-static size_t lp_features_ws(int S, int E) { return 2 * d3_align((size_t)(S + 1) * sizeof(int)) + d3_align((size_t)(E > 0 ? E : 1) * sizeof(int)); }
+struct LpFeatWs { int *rows, *eptr, *epos; };
+static void lp_features_layout(D3Carver &c, int S, int E, LpFeatWs &w) {
+    w.rows = c.take<int>(S + 1); w.eptr = c.take<int>(S + 1); w.epos = c.take<int>(E > 0 ? E : 1);
+}
 
 size_t d3_lang_features_ws_bytes(int S, int E) {
     if (S < 0 || S > LP_MAX_SLOTS || E < 0 || (long long)E > (long long)LP_MAX_SLOTS * 64) return 0;
-    return lp_features_ws(S, E);
+    D3Carver c(nullptr, 0);
+    LpFeatWs w;
+    lp_features_layout(c, S, E, w);
+    return c.off;
 }
 
 int d3_lang_features(const int *tokens, const int *lens, int Nd, const float *glove, int V, int D, int L, int unk,
@@ -62,9 +68,11 @@ int d3_lang_features(const int *tokens, const int *lens, int Nd, const float *gl
     for (int e = 0; e < E; ++e)
         if (erase_pos_host[e] < 0 || erase_pos_host[e] >= L) return D3_ERR_ARG;
     if (!tokens || !lens || !glove || !lang_feat || !lang_ids || !lang_len) return D3_ERR_ARG;
-    if (!ws || ws_bytes < lp_features_ws(S, E)) return D3_ERR_WORKSPACE;
     D3Carver cv(ws, ws_bytes);
-    int *rows = cv.take<int>(S + 1), *eptr = cv.take<int>(S + 1), *epos = cv.take<int>(E > 0 ? E : 1);
+    LpFeatWs w;
+    lp_features_layout(cv, S, E, w);
+    if (!cv.ok()) return D3_ERR_WORKSPACE;
+    int *rows = w.rows, *eptr = w.eptr, *epos = w.epos;
     hipStream_t st = d3_stream(stream);
     D3_CLEAR();
     // pageable host memory is staged before hipMemcpyAsync returns; lang_prep.py keeps its arrays referenced all the same
@@ -114,9 +122,13 @@ lp_rot_kernel(const long long *__restrict__ gt_ids, const long long *__restrict_
     if (lane == 0) rot_masks[row] = best >= 0 ? 1 : 0;
 }
 
+static int *lp_ref_layout(D3Carver &c, int B) { return c.take<int>(B + 1); }      // the scene index of every batch row
+
 size_t d3_ref_targets_ws_bytes(int B) {
     if (B < 0 || B > LP_MAX_SLOTS) return 0;
-    return d3_align((size_t)(B + 1) * sizeof(int));
+    D3Carver c(nullptr, 0);
+    lp_ref_layout(c, B);
+    return c.off;
 }
 
 int d3_ref_targets(const long long *gt_ids, const long long *gt_label, const float *gt_bbox, const long long *object_id, int B, int C,
@@ -130,8 +142,9 @@ int d3_ref_targets(const long long *gt_ids, const long long *gt_label, const flo
     if (Ns > 0 && (!rot_off || !rot_ids || !rot_mats)) return D3_ERR_ARG;
     for (int b = 0; b < B; ++b)
         if (scene_host[b] < -1 || scene_host[b] >= Ns) return D3_ERR_RANGE;
-    if (!ws || ws_bytes < d3_align((size_t)(B + 1) * sizeof(int))) return D3_ERR_WORKSPACE;
-    int *scene = (int *)ws;
+    D3Carver cv(ws, ws_bytes);
+    int *scene = lp_ref_layout(cv, B);
+    if (!cv.ok()) return D3_ERR_WORKSPACE;
     hipStream_t st = d3_stream(stream);
     D3_CLEAR();
     D3_CHECK(hipMemcpyAsync(scene, scene_host, (size_t)B * sizeof(int), hipMemcpyHostToDevice, st));

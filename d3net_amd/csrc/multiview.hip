@@ -187,10 +187,21 @@ __global__ __launch_bounds__(MV_BLOCK) void mv_scatter_kernel(int N, const int *
     }
 }
 
+struct MvProjWs { float *par; int *pix, *flag, *pos; void *temp; size_t temp_bytes; };
+static void mv_project_layout(D3Carver &c, int N, int F, MvProjWs &w) {
+    const size_t nf = (size_t)N * F;
+    w.par = c.take<float>((size_t)F * MV_NPAR);
+    w.pix = c.take<int>(nf); w.flag = c.take<int>(nf); w.pos = c.take<int>(nf);
+    w.temp_bytes = d3_scan_temp_bytes((int)nf);
+    w.temp = c.take<char>(w.temp_bytes);
+}
+
 size_t d3_multiview_project_ws_bytes(int N, int F) {
     if (N < 1 || N > MV_MAX_POINTS || F < 1 || F > MV_MAX_FRAMES || (long long)N * F > 0x7fffffffll) return 0;
-    size_t nf = (size_t)N * F;
-    return d3_align((size_t)F * MV_NPAR * 4) + 3 * d3_align(nf * 4) + d3_scan_temp_bytes((int)nf);
+    D3Carver c(nullptr, 0);
+    MvProjWs w;
+    mv_project_layout(c, N, F, w);
+    return c.off;
 }
 
 static int mv_check_sizes(int N, int F, int W, int H) {
@@ -210,14 +221,13 @@ int d3_multiview_project(const float *points, int N, const float *depths, const 
     rc = mv_cam(intr_host, W, H, &cam);
     if (rc) return rc;
     if (N == 0 || F == 0) return 0;
-    size_t need = d3_multiview_project_ws_bytes(N, F);
-    if (ws_bytes < need) return D3_ERR_WORKSPACE;
-    size_t nf = (size_t)N * F;
     D3Carver cv(ws, ws_bytes);
-    float *par = cv.take<float>((size_t)F * MV_NPAR);
-    int *pix = cv.take<int>(nf), *flag = cv.take<int>(nf), *pos = cv.take<int>(nf);
-    size_t tbytes = ws_bytes - cv.off;
-    void *temp = cv.base + cv.off;
+    MvProjWs w;
+    mv_project_layout(cv, N, F, w);
+    if (!cv.ok()) return D3_ERR_WORKSPACE;
+    const size_t nf = (size_t)N * F;
+    float *par = w.par;
+    int *pix = w.pix, *flag = w.flag, *pos = w.pos;
     hipStream_t st = d3_stream(stream);
     D3_CHECK(hipMemsetAsync(idx3d, 0, (size_t)F * (N + 1) * sizeof(long long), st));
     D3_CHECK(hipMemsetAsync(idx2d, 0, (size_t)F * (N + 1) * sizeof(long long), st));
@@ -226,7 +236,7 @@ int d3_multiview_project(const float *points, int N, const float *depths, const 
     dim3 g(mv_blocks(N, MV_BLOCK), F);
     hipLaunchKernelGGL(mv_map_kernel, g, dim3(MV_BLOCK), 0, st, points, N, depths, par, cam, pix, flag);
     D3_LAUNCH_CHECK();
-    rc = d3_exclusive_scan_i32(flag, pos, (int)nf, temp, tbytes, st);
+    rc = d3_exclusive_scan_i32(flag, pos, (int)nf, w.temp, w.temp_bytes, st);
     if (rc) return rc;
     hipLaunchKernelGGL(mv_scatter_kernel, g, dim3(MV_BLOCK), 0, st, N, pix, pos, idx3d, idx2d);
     D3_LAUNCH_CHECK();
@@ -359,9 +369,19 @@ __global__ __launch_bounds__(MV_BLOCK) void mv_fuse_kernel(const float *__restri
     }
 }
 
+struct MvFuseWs { float *par; int *counts; float *hwc; };
+static void mv_fuse_layout(D3Carver &c, int F, int W, int H, MvFuseWs &w) {
+    w.par = c.take<float>((size_t)F * MV_NPAR);
+    w.counts = c.take<int>(F);
+    w.hwc = c.take<float>((size_t)F * W * H * MV_C);
+}
+
 size_t d3_multiview_fuse_ws_bytes(int F, int W, int H) {
     if (F < 1 || F > MV_MAX_FRAMES || W < 1 || H < 1 || (long long)W * H > MV_MAX_PIXELS) return 0;
-    return d3_align((size_t)F * MV_NPAR * 4) + d3_align((size_t)F * 4) + d3_align((size_t)F * W * H * MV_C * 4);
+    D3Carver c(nullptr, 0);
+    MvFuseWs w;
+    mv_fuse_layout(c, F, W, H, w);
+    return c.off;
 }
 
 int d3_multiview_fuse(const float *points, int N, const float *depths, const float *c2w, const float *w2c, int F,
@@ -380,11 +400,13 @@ int d3_multiview_fuse(const float *points, int N, const float *depths, const flo
         D3_CHECK(hipMemsetAsync(out, 0, (size_t)N * MV_C * sizeof(float), st));
         return 0;
     }
-    if (ws_bytes < d3_multiview_fuse_ws_bytes(F, W, H)) return D3_ERR_WORKSPACE;
     D3Carver cv(ws, ws_bytes);
-    float *par = cv.take<float>((size_t)F * MV_NPAR);
-    int *counts = cv.take<int>(F);
-    float *hwc = cv.take<float>((size_t)F * W * H * MV_C);
+    MvFuseWs w;
+    mv_fuse_layout(cv, F, W, H, w);
+    if (!cv.ok()) return D3_ERR_WORKSPACE;
+    float *par = w.par;
+    int *counts = w.counts;
+    float *hwc = w.hwc;
     const int HW = W * H;
     D3_CHECK(hipMemsetAsync(counts, 0, (size_t)F * sizeof(int), st));
     hipLaunchKernelGGL(mv_params_kernel, dim3(mv_blocks(F, 64)), dim3(64), 0, st, c2w, w2c, F, cam, par);

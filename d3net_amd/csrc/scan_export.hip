@@ -161,9 +161,18 @@ __global__ __launch_bounds__(SX_BLOCK) void sx_vertex_mesh_kernel(const unsigned
     a[0] = ax; a[1] = ay; a[2] = az; a[3] = cr; a[4] = cg; a[5] = cb; a[6] = nx; a[7] = ny; a[8] = nz;
 }
 
+struct SxMeshWs { int *last; float *fn; };
+static void sx_mesh_layout(D3Carver &c, int N, int F, SxMeshWs &w) {
+    w.last = c.take<int>((size_t)3 * N);
+    w.fn = c.take<float>((size_t)3 * (F > 0 ? F : 1));
+}
+
 size_t d3_scan_mesh_ws_bytes(int N, int F) {
     if (N < 1 || N > SX_MAX_VERTICES || F < 0 || F > SX_MAX_FACES) return 0;
-    return d3_align((size_t)3 * N * 4) + d3_align((size_t)3 * (F > 0 ? F : 1) * 4);
+    D3Carver c(nullptr, 0);
+    SxMeshWs w;
+    sx_mesh_layout(c, N, F, w);
+    return c.off;
 }
 
 int d3_scan_mesh(const void *vertex_rec, int N, const void *face_rec, int F, const double *align_host, float *mesh, float *aligned_mesh,
@@ -171,11 +180,12 @@ int d3_scan_mesh(const void *vertex_rec, int N, const void *face_rec, int F, con
     if (N < 1 || N > SX_MAX_VERTICES || F < 0 || F > SX_MAX_FACES) return D3_ERR_RANGE;
     if (!vertex_rec || (F > 0 && !face_rec) || !mesh || !aligned_mesh || !flags || !ws) return D3_ERR_ARG;
     if (((uintptr_t)vertex_rec & 3) != 0) return D3_ERR_ARG;
-    if (ws_bytes < d3_scan_mesh_ws_bytes(N, F)) return D3_ERR_WORKSPACE;
     D3Carver cv(ws, ws_bytes);
-    int *last = cv.take<int>((size_t)3 * N);
-    float *fn = cv.take<float>((size_t)3 * (F > 0 ? F : 1));
+    SxMeshWs w;
+    sx_mesh_layout(cv, N, F, w);
     if (!cv.ok()) return D3_ERR_WORKSPACE;
+    int *last = w.last;
+    float *fn = w.fn;
     SxAlign al;
     al.on = align_host != nullptr;
     for (int i = 0; i < 16; i++) al.m[i] = align_host ? align_host[i] : 0.0;
@@ -360,10 +370,21 @@ static bool sx_label_sizes_ok(int N, int S, int P, int K, int R) {
            K <= SX_MAX_OBJECTS && R >= 1 && R <= SX_MAX_ROWS;
 }
 
+struct SxLabelWs { int *seg_first, *seg_owner, *kfirst, *code, *row_claim; unsigned *kmin, *kmax; double *rows; };
+static void sx_label_layout(D3Carver &c, int S, int K, int R, SxLabelWs &w) {
+    w.seg_first = c.take<int>(S); w.seg_owner = c.take<int>(S);
+    w.kfirst = c.take<int>(K); w.code = c.take<int>(K);
+    w.kmin = c.take<unsigned>((size_t)6 * K); w.kmax = c.take<unsigned>((size_t)6 * K);
+    w.rows = c.take<double>((size_t)16 * R);
+    w.row_claim = c.take<int>(R);
+}
+
 size_t d3_scan_labels_ws_bytes(int N, int S, int P, int K, int R) {
     if (!sx_label_sizes_ok(N, S, P, K, R)) return 0;
-    return 2 * d3_align((size_t)S * 4) + 2 * d3_align((size_t)K * 4) + 2 * d3_align((size_t)6 * K * 4) +
-           d3_align((size_t)16 * R * 8) + d3_align((size_t)R * 4);
+    D3Carver c(nullptr, 0);
+    SxLabelWs w;
+    sx_label_layout(c, S, K, R, w);
+    return c.off;
 }
 
 int d3_scan_labels(const unsigned short *raw, const int *seg, int N, int S, const int *pair_seg, const int *pair_obj, int P,
@@ -374,14 +395,13 @@ int d3_scan_labels(const unsigned short *raw, const int *seg, int N, int S, cons
     if (!raw || !seg || (P > 0 && (!pair_seg || !pair_obj)) || !obj_id || !obj_label_seg || !mesh || !aligned_mesh ||
         !instance_ids || !sem_labels || !inst_gt || !boxes || !aligned_boxes || !flags || !ws)
         return D3_ERR_ARG;
-    if (ws_bytes < d3_scan_labels_ws_bytes(N, S, P, K, R)) return D3_ERR_WORKSPACE;
     D3Carver cv(ws, ws_bytes);
-    int *seg_first = cv.take<int>(S), *seg_owner = cv.take<int>(S);
-    int *kfirst = cv.take<int>(K), *code = cv.take<int>(K);
-    unsigned *kmin = cv.take<unsigned>((size_t)6 * K), *kmax = cv.take<unsigned>((size_t)6 * K);
-    double *rows = cv.take<double>((size_t)16 * R);
-    int *row_claim = cv.take<int>(R);
+    SxLabelWs w;
+    sx_label_layout(cv, S, K, R, w);
     if (!cv.ok()) return D3_ERR_WORKSPACE;
+    int *seg_first = w.seg_first, *seg_owner = w.seg_owner, *kfirst = w.kfirst, *code = w.code, *row_claim = w.row_claim;
+    unsigned *kmin = w.kmin, *kmax = w.kmax;
+    double *rows = w.rows;
     hipStream_t st = d3_stream(stream);
     D3_CLEAR();
     D3_CHECK(hipMemsetAsync(seg_first, 0x7f, (size_t)S * 4, st));

@@ -28,11 +28,6 @@
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-int hg_launch(const d3_gemm_prob *probs, int nprobs, hipStream_t s);
-size_t hg_colsum_ws_bytes(int njobs, int cmax);
-int hg_colsum_multi(const float *const *x, const long long *ld, const int *R, const int *C, float *const *out, const int *accum, int n,
-                    void *ws, size_t ws_bytes, hipStream_t s);
-
 #define SM_H 128          // hidden width (the only one the kernels are written for)
 #define SM_TR 64          // rows per workgroup
 #define SM_LP 132         // LDS row pitch in floats: 16-byte aligned rows, the 16 lanes of a k quad on distinct banks

@@ -338,15 +338,40 @@ __global__ void sp_emit_kernel(const double *__restrict__ y, const double *__res
     }
 }
 
+// The three entry points share one workspace, one after the other: d3_scene_ws_bytes is the largest of their layouts.
+struct SpEmitWs { int *pos; void *tmp; size_t tmp_bytes; };
+static void sp_emit_layout(D3Carver &c, int n, SpEmitWs &w) {
+    w.pos = c.take<int>(n);
+    w.tmp_bytes = d3_scan_temp_bytes(n);
+    w.tmp = c.take<char>(w.tmp_bytes);
+}
+struct SpRelabelWs { int *pres, *val_of, *orig_at; };
+static void sp_relabel_layout(D3Carver &c, int V, SpRelabelWs &w) {
+    w.pres = c.take<int>(V); w.val_of = c.take<int>(V); w.orig_at = c.take<int>(V);
+}
+struct SpInstWs {
+    int *hist, *pres, *start, *rank, *keys, *vals, *keys2, *sorted;
+    double *istats;
+    void *scan_t, *sort_t; size_t scan_b, sort_b;
+};
+static void sp_inst_layout(D3Carver &c, int n, int V, SpInstWs &w) {
+    w.hist = c.take<int>(V + 1); w.pres = c.take<int>(V + 1); w.start = c.take<int>(V + 1); w.rank = c.take<int>(V);
+    w.keys = c.take<int>(n); w.vals = c.take<int>(n); w.keys2 = c.take<int>(n); w.sorted = c.take<int>(n);
+    w.istats = c.take<double>(9 * (size_t)V);
+    w.scan_b = d3_scan_temp_bytes(V + 1); w.sort_b = d3_sort_pairs_temp_bytes(n);
+    w.scan_t = c.take<char>(w.scan_b); w.sort_t = c.take<char>(w.sort_b);
+}
+
 size_t d3_scene_ws_bytes(int n, int max_id) {
     if (n < 0 || n > SP_MAX_POINTS || max_id > SP_MAX_ID) return 0;
-    size_t V = (size_t)(max_id < 0 ? 0 : max_id) + 1;
-    size_t emit = d3_align((size_t)n * 4) + d3_scan_temp_bytes(n);
-    size_t relabel = 3 * d3_align(V * 4);
-    size_t inst = 3 * d3_align((V + 1) * 4) + d3_align(V * 4) + 4 * d3_align((size_t)n * 4) + d3_align(9 * V * 8) + d3_align(16) +
-                  d3_scan_temp_bytes((int)V + 1) + d3_sort_pairs_temp_bytes(n);
-    size_t m = emit > relabel ? emit : relabel;
-    return m > inst ? m : inst;
+    const int V = (max_id < 0 ? 0 : max_id) + 1;
+    D3Carver emit(nullptr, 0), relabel(nullptr, 0), inst(nullptr, 0);
+    SpEmitWs we; SpRelabelWs wr; SpInstWs wi;
+    sp_emit_layout(emit, n, we);
+    sp_relabel_layout(relabel, V, wr);
+    sp_inst_layout(inst, n, V, wi);
+    const size_t m = emit.off > relabel.off ? emit.off : relabel.off;
+    return m > inst.off ? m : inst.off;
 }
 
 int d3_scene_emit(const double *y, const double *s, const float *feats, int C, const int *sem, const int *ids, int n,
@@ -362,11 +387,11 @@ int d3_scene_emit(const double *y, const double *s, const float *feats, int C, c
     int *pos = nullptr;
     if (flags) {
         D3Carver cv(ws, ws_bytes);
-        pos = cv.take<int>(n);
-        size_t tb = d3_scan_temp_bytes(n);
-        void *tmp = cv.take<char>(tb);
+        SpEmitWs w;
+        sp_emit_layout(cv, n, w);
         if (!cv.ok()) return D3_ERR_WORKSPACE;
-        int rc = d3_exclusive_scan_i32(flags, pos, n, tmp, tb, st);
+        pos = w.pos;
+        int rc = d3_exclusive_scan_i32(flags, pos, n, w.tmp, w.tmp_bytes, st);
         if (rc) return rc;
     }
     hipLaunchKernelGGL(sp_emit_kernel, dim3(sp_grid(n)), dim3(SP_BLOCK), 0, st, y, s, feats, C, sem, ids, n, flags, pos, p, fp32,
@@ -417,8 +442,10 @@ int d3_scene_relabel(int *ids, int n, int max_id, void *ws, size_t ws_bytes, voi
     int V = max_id + 1;
     hipStream_t st = d3_stream(stream);
     D3Carver cv(ws, ws_bytes);
-    int *pres = cv.take<int>(V), *val_of = cv.take<int>(V), *orig_at = cv.take<int>(V);
+    SpRelabelWs w;
+    sp_relabel_layout(cv, V, w);
     if (!cv.ok()) return D3_ERR_WORKSPACE;
+    int *pres = w.pres, *val_of = w.val_of, *orig_at = w.orig_at;
     D3_CHECK(hipMemsetAsync(pres, 0, (size_t)V * 4, st));
     hipLaunchKernelGGL(sp_presence_kernel, dim3(sp_grid(n)), dim3(SP_BLOCK), 0, st, (const int *)ids, n, V, pres);
     D3_LAUNCH_CHECK();
@@ -581,13 +608,15 @@ int d3_scene_instances(const double *y, const int *ids, const int *sem, int n, i
     hipStream_t st = d3_stream(stream);
     int V = (max_id < 0 ? 0 : max_id) + 1;
     D3Carver cv(ws, ws_bytes);
-    int *hist = cv.take<int>(V + 1), *pres = cv.take<int>(V + 1), *start = cv.take<int>(V + 1), *rank = cv.take<int>(V);
-    int *keys = cv.take<int>(n), *vals = cv.take<int>(n), *keys2 = cv.take<int>(n), *sorted = cv.take<int>(n);
-    double *istats = cv.take<double>(9 * (size_t)V);
-    int *cnt_dev = counts;
-    size_t scan_b = d3_scan_temp_bytes(V + 1), sort_b = d3_sort_pairs_temp_bytes(n);
-    void *scan_t = cv.take<char>(scan_b), *sort_t = cv.take<char>(sort_b);
+    SpInstWs w;
+    sp_inst_layout(cv, n, V, w);
     if (!cv.ok()) return D3_ERR_WORKSPACE;
+    int *hist = w.hist, *pres = w.pres, *start = w.start, *rank = w.rank;
+    int *keys = w.keys, *vals = w.vals, *keys2 = w.keys2, *sorted = w.sorted;
+    double *istats = w.istats;
+    int *cnt_dev = counts;
+    const size_t scan_b = w.scan_b, sort_b = w.sort_b;
+    void *scan_t = w.scan_t, *sort_t = w.sort_t;
     D3_CHECK(hipMemsetAsync(hist, 0, (size_t)(V + 1) * 4, st));
     D3_CHECK(hipMemsetAsync(counts, 0, 4 * sizeof(int), st));
     if (n > 0) {

@@ -31,11 +31,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define GRU_U 2      // k blocks of 16 per wave and batch of loads (812 / 16 = 51 blocks over 8 waves; 4 measured slower: 12.4 -> 13.4 us)
 #endif
 
-int hg_launch(const d3_gemm_prob *probs, int nprobs, hipStream_t s);
-size_t hg_colsum_ws_bytes(int njobs, int cmax);
-int hg_colsum_multi(const float *const *x, const long long *ld, const int *R, const int *C, float *const *out, const int *accum, int n,
-                    void *ws, size_t ws_bytes, hipStream_t s);
-
 // ------------------------------------------------------------------------------ fused GRUCell forward
 // h' = GRUCell(x, h) (torch.nn.GRUCell semantics: r, z, n gate order; n = tanh(W_in x + b_in + r * (W_hn h + b_hn))).
 // A workgroup owns 16 hidden units (the three gate rows j, H+j, 2H+j of both weight matrices) x RT*16 batch rows; its 4
@@ -949,9 +944,18 @@ extern "C" int d3_topdown_xe_backward_ex(const d3_topdown_args *a, const d3_topd
 // on the classifier output and nothing can be batched over time: 8 launches (x1, GRU1, map_hidd, attention, map_lang, GRU2,
 // classifier.0, classifier.2).  fp = map_feat(obj) is computed once per decode by d3_topdown_feat_proj.  obj_div: consecutive
 // samples sharing one (K,F) object block (the evaluation decode runs the K targets of a scene as K samples).
+struct TdStepWs { int *widx, *act, *nact; float *x1, *x2, *q, *c0, *att, *msum; };
+static void td_step_layout(D3Carver &c, int N, int K, int H, int E, int F, TdStepWs &w) {
+    w.widx = c.take<int>(N);
+    w.x1 = c.take<float>((size_t)N * E); w.x2 = c.take<float>((size_t)N * E); w.q = c.take<float>((size_t)N * H);
+    w.c0 = c.take<float>((size_t)N * H); w.att = c.take<float>((size_t)N * F); w.msum = c.take<float>((size_t)N * F);
+    w.act = c.take<int>((size_t)N * K); w.nact = c.take<int>(N);
+}
 extern "C" size_t d3_topdown_step_ws_bytes(int N, int K, int H, int E, int F) {
-    return 2 * d3_align((size_t)N * 4) + 2 * d3_align((size_t)N * E * 4) + 2 * d3_align((size_t)N * H * 4) + 2 * d3_align((size_t)N * F * 4) +
-           d3_align((size_t)N * K * 4) + 256;
+    D3Carver c(nullptr, 0);
+    TdStepWs w;
+    td_step_layout(c, N, K, H, E, F, w);
+    return c.off + 256;
 }
 
 extern "C" int d3_topdown_feat_proj(const float *obj, const float *W_feat, float *fp, int rows, int H, int F, void *stream) {
@@ -972,13 +976,13 @@ extern "C" int d3_topdown_step(const d3_topdown_args *a, const long long *word, 
     D3_CLEAR();
     if (!a || a->N < 1 || (a->H & 15) || (a->E & 3) || (a->F & 3) || a->F > 128 || obj_div < 1) return D3_ERR_ARG;
     const int N = a->N, K = a->K, V = a->V, H = a->H, E = a->E, F = a->F;
-    if (ws_bytes < d3_topdown_step_ws_bytes(N, K, H, E, F)) return D3_ERR_WORKSPACE;
-    hipStream_t s = d3_stream(stream);
     D3Carver cv(ws_, ws_bytes);
-    int *widx = cv.take<int>(N);
-    float *x1 = cv.take<float>((size_t)N * E), *x2 = cv.take<float>((size_t)N * E), *q = cv.take<float>((size_t)N * H);
-    float *c0 = cv.take<float>((size_t)N * H), *att = cv.take<float>((size_t)N * F), *msum = cv.take<float>((size_t)N * F);
-    int *act = cv.take<int>((size_t)N * K), *nact = cv.take<int>(N);
+    TdStepWs w;
+    td_step_layout(cv, N, K, H, E, F, w);
+    if (!cv.ok()) return D3_ERR_WORKSPACE;
+    hipStream_t s = d3_stream(stream);
+    int *widx = w.widx, *act = w.act, *nact = w.nact;
+    float *x1 = w.x1, *x2 = w.x2, *q = w.q, *c0 = w.c0, *att = w.att, *msum = w.msum;
     const long long ldtd = H + F + E, ldlang = F + H;
     int rc;
     if (256 % F) return D3_ERR_ARG;
@@ -1045,10 +1049,16 @@ static GsLayout gs_layout(int N, int T, int H) {
     return L;
 }
 extern "C" size_t d3_gru_seq_ws_bytes(int N, int T, int I, int H) { (void)I; return gs_layout(N, T, H).total; }
-extern "C" size_t d3_gru_seq_bwd_ws_bytes(int N, int T, int I, int H) {
-    (void)I;
-    return d3_align((size_t)N * T * 3 * H * 4) * 2 + d3_align((size_t)N * H * 4) + d3_align(hg_colsum_ws_bytes(2, 3 * H)) + 256;
+struct GsBwdLayout { size_t DGI, DGH, carry, cs, cs_bytes, total; };
+static GsBwdLayout gs_bwd_layout(int N, int T, int H) {
+    GsBwdLayout B; size_t o = 0;
+    auto take = [&](size_t b) { size_t at = o; o += d3_align(b); return at; };
+    B.DGI = take((size_t)N * T * 3 * H * 4); B.DGH = take((size_t)N * T * 3 * H * 4); B.carry = take((size_t)N * H * 4);
+    B.cs_bytes = hg_colsum_ws_bytes(2, 3 * H); B.cs = take(B.cs_bytes);
+    B.total = o;
+    return B;
 }
+extern "C" size_t d3_gru_seq_bwd_ws_bytes(int N, int T, int I, int H) { (void)I; return gs_bwd_layout(N, T, H).total + 256; }
 
 extern "C" int d3_gru_seq_forward(const float *x, const int *lens, const float *Wih, const float *Whh, const float *bih, const float *bhh,
                                   int N, int T, int I, int H, float *hiddens, float *last, void *ws_, size_t ws_bytes, void *stream) {
@@ -1085,15 +1095,14 @@ extern "C" int d3_gru_seq_backward(const float *x, const int *lens, const float 
                                    float *dbhh, float *dx, void *ws2_, size_t ws2_bytes, void *stream) {
     D3_CLEAR();
     if (N < 1 || T < 1 || (H & 15) || (I & 3)) return D3_ERR_ARG;
-    if (ws2_bytes < d3_gru_seq_bwd_ws_bytes(N, T, I, H)) return D3_ERR_WORKSPACE;
+    const GsBwdLayout B = gs_bwd_layout(N, T, H);
+    if (ws2_bytes < B.total) return D3_ERR_WORKSPACE;
     hipStream_t s = d3_stream(stream);
     const GsLayout L = gs_layout(N, T, H);
     const char *ws = (const char *)ws_;
     const float *Hs = (const float *)(ws + L.Hs), *g = (const float *)(ws + L.g);
     char *w2 = (char *)ws2_;
-    const size_t gsz = d3_align((size_t)N * T * 3 * H * 4);
-    float *DGI = (float *)w2, *DGH = (float *)(w2 + gsz), *carry = (float *)(w2 + 2 * gsz);
-    char *cs = w2 + 2 * gsz + d3_align((size_t)N * H * 4);
+    float *DGI = (float *)(w2 + B.DGI), *DGH = (float *)(w2 + B.DGH), *carry = (float *)(w2 + B.carry);
     const size_t NH = (size_t)N * H, TNH = (size_t)T * NH;
     int rc;
     if (d_last) D3_CHECK(hipMemcpyAsync(carry, d_last, NH * 4, hipMemcpyDeviceToDevice, s));
@@ -1116,7 +1125,7 @@ extern "C" int d3_gru_seq_backward(const float *x, const int *lens, const float 
         if ((rc = hg_launch(&p[1], 1, s))) return rc;
         const float *cx[2] = {DGI, DGH}; const long long cl[2] = {3 * H, 3 * H}; const int cr[2] = {N * T, N * T}, cc[2] = {3 * H, 3 * H};
         float *co[2] = {dbih, dbhh};
-        if ((rc = hg_colsum_multi(cx, cl, cr, cc, co, nullptr, 2, cs, hg_colsum_ws_bytes(2, 3 * H), s))) return rc;
+        if ((rc = hg_colsum_multi(cx, cl, cr, cc, co, nullptr, 2, w2 + B.cs, B.cs_bytes, s))) return rc;
         if (dx) {
             d3_gemm_prob q = td_prob(N * T, I, dx, I);
             q.nseg = 1; q.seg[0] = td_seg(DGI, 3 * H, Wih, I, 3 * H, nullptr, 0, 1);

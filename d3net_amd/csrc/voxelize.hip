@@ -246,8 +246,7 @@ struct VoxIdxWs {
 
 static size_t vi_cap(int n) { size_t c = 1024; while (c < (size_t)n * 2) c <<= 1; return c; }
 
-static bool vi_carve(void *ws, size_t ws_bytes, int n, VoxIdxWs &w) {
-    D3Carver c(ws, ws_bytes);
+static void vi_layout(D3Carver &c, int n, VoxIdxWs &w) {
     size_t nn = (size_t)(n > 0 ? n : 1);
     w.cap = vi_cap(n);
     w.keys = c.take<unsigned long long>(w.cap);
@@ -264,20 +263,17 @@ static bool vi_carve(void *ws, size_t ws_bytes, int n, VoxIdxWs &w) {
     size_t t1 = d3_scan_temp_bytes(n), t2 = d3_sort_pairs_temp_bytes(n);
     w.temp_bytes = t1 > t2 ? t1 : t2;
     w.temp = c.take<char>(w.temp_bytes);
-    return ws == nullptr ? false : c.ok();
+}
+static bool vi_carve(void *ws, size_t ws_bytes, int n, VoxIdxWs &w) {
+    D3Carver c(ws, ws_bytes);
+    vi_layout(c, n, w);
+    return c.ok();
 }
 
 extern "C" size_t d3_voxelize_idx_ws_bytes(int n) {
-    VoxIdxWs w;
     D3Carver c(nullptr, 0);
-    size_t nn = (size_t)(n > 0 ? n : 1);
-    size_t cap = vi_cap(n);
-    c.take<unsigned long long>(cap); c.take<int>(cap); c.take<int>(cap);
-    for (int i = 0; i < 7; i++) c.take<int>(nn);
-    c.take<int>(64);
-    size_t t1 = d3_scan_temp_bytes(n), t2 = d3_sort_pairs_temp_bytes(n);
-    c.take<char>(t1 > t2 ? t1 : t2);
-    (void)w;
+    VoxIdxWs w;
+    vi_layout(c, n, w);
     return c.off + 256;
 }
 

@@ -71,6 +71,45 @@ def test_convolutions_hand_nothing_over_through_globals():
         assert "thread_local" not in open(os.path.join(csrc, f)).read(), f
 
 
+def test_workspace_layouts_are_written_once():
+    """a workspace's regions are listed by ONE layout function that the run carves with and the *_ws_bytes query measures
+    (D3Carver, csrc/common.h): no `(char *)ws... +` / `(const char *)ws... +` arithmetic in an expression (the offset-struct
+    layouts of topdown.hip, whose runs add checked offsets to a `char *` alias, are not what this looks for), and the hgemm.hip
+    helpers are declared once"""
+    csrc = os.path.join(ROOT, "d3net_amd", "csrc")
+    hips = [f for f in sorted(os.listdir(csrc)) if f.endswith(".hip")]
+    assert len(hips) >= 20
+    arith = re.compile(r"\(\s*(?:const\s+)?char\s*\*\s*\)\s*ws\w*[^;\n]*\+")
+    decl = re.compile(r"^\s*(?:static\s+|extern\s+)?(?:int|size_t)\s+(hg_launch|hg_colsum_ws_bytes|hg_colsum_multi)\s*\(", re.M)
+    bad = []
+    for f in hips:
+        t = open(os.path.join(csrc, f), errors="ignore").read()
+        bad += [(f, m.group(0)) for m in arith.finditer(t)]
+        if f != "hgemm.hip":
+            bad += [(f, m.group(1)) for m in decl.finditer(t)]
+    assert not bad, bad
+    assert len(decl.findall(open(os.path.join(csrc, "hgemm.hip")).read())) == 3
+    assert len(decl.findall(open(os.path.join(csrc, "common.h")).read())) == 3
+
+
+def test_workspace_sizes_are_pinned(built_lib):
+    """the size queries without rocPRIM scratch are pure arithmetic: the values of the hand-written formulas that the layout
+    functions replaced"""
+    from d3net_amd import _lib
+    l = _lib.lib()
+    assert l.d3_topdown_step_ws_bytes(8, 16, 512, 300, 128) == 61696
+    assert l.d3_gru_seq_bwd_ws_bytes(8, 30, 300, 256) == 1581312
+    assert l.d3_edgeconv_ws_bytes(160, 128, 128) == 245760
+    assert l.d3_edgeconv_bwd_ws_bytes(160, 128, 128) == 868352
+    assert l.d3_enet_ws_bytes(2, 64, 80) == 409600
+    assert l.d3_cider_ws_bytes(40, 8, 4096) == 543744
+    assert l.d3_scan_labels_ws_bytes(1000, 50, 60, 10, 20) == 4352
+    assert l.d3_scan_mesh_ws_bytes(1000, 2000) == 36096
+    assert l.d3_multiview_fuse_ws_bytes(4, 41, 32) == 2688000
+    assert l.d3_lang_features_ws_bytes(8, 5) == 768
+    assert l.d3_ref_targets_ws_bytes(2) == 256
+
+
 def test_switch_table_stays_small(built_lib):
     """the library's measurement / cross-check switches live in ONE table (csrc/tuning.hip): at most 12, every name unique"""
     from d3net_amd import _lib

@@ -19,10 +19,17 @@ def _cfg(**model):
     return default_conf(overrides=base)
 
 
-@pytest.mark.parametrize("mode", [0, 1, 2])
-def test_pipeline_modes_run_and_train(dev, mode):
+@pytest.mark.parametrize("mode,exact_ws", [pytest.param(m, e, id="%d-exact_ws" % m if e else str(m)) for e in (False, True) for m in (0, 1, 2)])
+def test_pipeline_modes_run_and_train(dev, mode, exact_ws, monkeypatch):
+    """exact_ws: every operator workspace is handed to the library with ws_bytes equal to exactly what its *_ws_bytes query
+    returned (the allocation behind it keeps its usual slack, so nothing can be written outside it)"""
     from d3net_amd import synthetic as S
     from d3net_amd.pipeline import PipelineNet
+    if exact_ws:
+        import d3net_amd.heads, d3net_amd.minkowski, d3net_amd.nativelinear, d3net_amd.pointgroup_ops
+        orig = d3net_amd.pointgroup_ops._workspace
+        for m in (d3net_amd.pointgroup_ops, d3net_amd.minkowski, d3net_amd.heads, d3net_amd.nativelinear):
+            monkeypatch.setattr(m, "_workspace", lambda nbytes, device, tag: orig(nbytes, device, tag)[:int(nbytes)])
     flags = {0: dict(no_captioning=True, no_grounding=True), 1: dict(no_captioning=False, no_grounding=True),
              2: dict(no_captioning=True, no_grounding=False)}[mode]
     cfg = _cfg(**flags)
