@@ -29,6 +29,7 @@
 #include "prof.h"
 #include <stdio.h>
 #include <stdlib.h>
+#include <memory>
 #include <mutex>
 #include <vector>
 
@@ -361,83 +362,6 @@ __global__ void cl_totals_kernel(const int *flag, const int *cid, const int *ksz
     }
 }
 
-static int cl_count(const int *semantic_label, const int *ball_query_idxs, const int *start_len, int n, int threshold, void *ws,
-                    size_t ws_bytes, int *sumNPoint_host, int *nCluster_host, int flags, void *stream);
-
-extern "C" int d3_bfs_cluster_count(const int *semantic_label, const int *ball_query_idxs, const int *start_len,
-                                    int n, int threshold, void *ws, size_t ws_bytes, int *sumNPoint_host,
-                                    int *nCluster_host, void *stream) {
-    return cl_count(semantic_label, ball_query_idxs, start_len, n, threshold, ws, ws_bytes, sumNPoint_host, nCluster_host, 0, stream);
-}
-// flags: D3_BFS_ASCENDING -- every list is in ascending index order (what ballquery_batch_p produces): the label push then
-// skips, per node, the prefix of targets that cannot change
-extern "C" int d3_bfs_cluster_count_ex(const int *semantic_label, const int *ball_query_idxs, const int *start_len,
-                                       int n, int threshold, void *ws, size_t ws_bytes, int *sumNPoint_host,
-                                       int *nCluster_host, int flags, void *stream) {
-    return cl_count(semantic_label, ball_query_idxs, start_len, n, threshold, ws, ws_bytes, sumNPoint_host, nCluster_host, flags, stream);
-}
-
-// One iteration of the count phase, enqueued only: a pair of label-push sweeps (it == 0: also the union-find in front of them), owners,
-// sizes, kept flags, cluster ids / offsets, and the copy of the scalars to `h` (6 ints; pinned memory for the asynchronous form).
-static int cl_count_enqueue(const int *semantic_label, const int *ball_query_idxs, const int *start_len, int n, int threshold, ClWs &w,
-                            int asc, int it, int *h, hipStream_t s) {
-    const int T = 256, nb = (n + T - 1) / T, nwb = (n + 3) / 4;
-    if (it == 0) {
-        cl_init_kernel<<<nb, T, 0, s>>>(w.parent, w.lab, w.sizes, w.par, w.klen, w.qln, n, w.scalars);   // (klen, qln: scratch until the fill)
-        // one hook per node under a smaller-index neighbour first (ECL-CC init), then the hooked trees flattened before the unions: most
-        // edges then find parent[i] == parent[j] with two loads and no walk (speaker step 16.59 -> 16.42 ms in-process, round 5)
-        cl_hook_kernel<<<nb, T, 0, s>>>(semantic_label, ball_query_idxs, start_len, n, w.parent);
-        cl_flatten_kernel<<<nb, T, 0, s>>>(w.parent, n);
-        cl_union_kernel<<<(int)(((long long)n * CL_UG + T - 1) / T), T, 0, s>>>(semantic_label, ball_query_idxs, start_len, n, w.parent, w.scalars);
-        cl_flatten_kernel<<<nb, T, 0, s>>>(w.parent, n);
-        D3_LAUNCH_CHECK();
-    }
-    // Label pushes in pairs, and the sizes / ids / offsets computed right behind them, all read back with ONE host round
-    // trip: the usual case is one productive sweep plus the sweep that finds nothing left to do (the second one reports
-    // through its own flag, scalars[4]); only when both sweeps still changed labels is the tail recomputed after more.
-    const int npb = nb < 2048 ? nb : 2048;        // label push: a bounded grid, one thread per node for the filters, a wave per surviving list
-    if (it > 0) {          // (the first pair of sweeps finds both flags zeroed by cl_init_kernel: two 4-byte fill launches less per clustering)
-        D3_CHECK(hipMemsetAsync(w.scalars, 0, sizeof(int), s));
-        D3_CHECK(hipMemsetAsync(w.scalars + 4, 0, sizeof(int), s));
-    }
-    if (it == 0 && asc)
-        cl_push_kernel<<<npb, T, 0, s>>>(semantic_label, ball_query_idxs, start_len, n, w.parent, w.lab, w.klen, w.qln, w.scalars, w.scalars + 3, asc, 1);
-    cl_push_kernel<<<npb, T, 0, s>>>(semantic_label, ball_query_idxs, start_len, n, w.parent, w.lab, w.klen, w.qln, w.scalars, w.scalars + 3, asc, 0);
-    cl_push_kernel<<<npb, T, 0, s>>>(semantic_label, ball_query_idxs, start_len, n, w.parent, w.lab, w.klen, w.qln, w.scalars + 4, w.scalars + 3, asc, 0);
-    if (it > 0) D3_CHECK(hipMemsetAsync(w.sizes, 0, (size_t)n * sizeof(int), s));   // (cl_owner_kernel accumulates)
-    cl_owner_kernel<<<nb, T, 0, s>>>(w.parent, w.lab, w.own, w.sizes, n);
-    cl_keep_kernel<<<nb, T, 0, s>>>(w.sizes, w.flag, w.ksz, n, threshold, start_len, w.scalars);
-    int rc = d3_exclusive_scan_i32(w.flag, w.cid, n, w.temp, w.temp_bytes, s);
-    if (rc) return rc;
-    rc = d3_exclusive_scan_i32(w.ksz, w.koff, n, w.temp, w.temp_bytes, s);
-    if (rc) return rc;
-    cl_totals_kernel<<<1, 64, 0, s>>>(w.flag, w.cid, w.ksz, w.koff, n, w.scalars);
-    D3_LAUNCH_CHECK();
-    D3_CHECK(hipMemcpyAsync(h, w.scalars, 6 * sizeof(int), hipMemcpyDeviceToHost, s));
-    return 0;
-}
-
-static int cl_count(const int *semantic_label, const int *ball_query_idxs, const int *start_len, int n, int threshold, void *ws,
-                    size_t ws_bytes, int *sumNPoint_host, int *nCluster_host, int flags, void *stream) {
-    D3_CLEAR();
-    const int asc = (flags & D3_BFS_ASCENDING) ? 1 : 0;
-    *sumNPoint_host = 0; *nCluster_host = 0;
-    if (n <= 0) return 0;
-    ClWs w;
-    if (!cl_carve(ws, ws_bytes, n, w)) return D3_ERR_WORKSPACE;
-    hipStream_t s = d3_stream(stream);
-    int h[6] = {0, 0, 0, 0, 0, 0};
-    for (int it = 0;; it += 2) {
-        int rc = cl_count_enqueue(semantic_label, ball_query_idxs, start_len, n, threshold, w, asc, it, h, s);
-        if (rc) return rc;
-        D3_CHECK(hipStreamSynchronize(s));
-        if (!h[0] || !h[4] || it >= n + 2) break;
-    }
-    *nCluster_host = h[1];
-    *sumNPoint_host = h[2];
-    return 0;
-}
-
 // z0 / z1 (optional, n ints each): zeroed here instead of by two fill launches in front of the record pass (3 MB each at the bench
 // batch: 13 + 29 us of fill kernels and their launch gaps on the clustering's critical path)
 // cnt (optional): the count phase's device scalars ([1] = nCluster, [2] = sumNPoint) -- the speculative fill of d3_bfs_cluster_run is
@@ -593,23 +517,6 @@ __global__ __launch_bounds__(CL_BFS_THREADS) void cl_bfs_kernel(const int *__res
         cluster_idxs[(size_t)(base + p) * 2 + 0] = c;
         cluster_idxs[(size_t)(base + p) * 2 + 1] = ld_dev(&q[p]);
     }
-}
-
-extern "C" int d3_bfs_cluster_fill(const int *semantic_label, const int *ball_query_idxs, const int *start_len,
-                                   int n, void *ws, size_t ws_bytes, int *cluster_idxs, int *cluster_offsets,
-                                   int sumNPoint, int nCluster, void *stream) {
-    D3_CLEAR();
-    if (n <= 0) return 0;
-    ClWs w;
-    if (!cl_carve(ws, ws_bytes, n, w)) return D3_ERR_WORKSPACE;
-    hipStream_t s = d3_stream(stream);
-    const int T = 256, nb = (n + T - 1) / T;
-    cl_seed_kernel<<<nb, T, 0, s>>>(w.flag, w.cid, w.koff, n, w.seeds, cluster_offsets, nCluster, sumNPoint, nullptr, nullptr, nullptr);
-    if (nCluster > 0)
-        cl_bfs_kernel<<<nCluster, CL_BFS_THREADS, 0, s>>>(semantic_label, ball_query_idxs, start_len, w.own, w.seeds,
-                                                         w.koff, w.sizes, w.par, w.queue, w.fcnt, w.qln, cluster_idxs, 0);
-    D3_LAUNCH_CHECK();
-    return 0;
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -981,122 +888,176 @@ __global__ void cl_prof_total_kernel(const int *estart, const int *klen, int n, 
 
 extern "C" size_t d3_bfs_cluster_erec_bytes(long long nActive) { return (size_t)(nActive > 0 ? nActive : 1) * sizeof(int4); }
 
-// d3_bfs_cluster_fill with the record-form level loop; erec: d3_bfs_cluster_erec_bytes(nActive) bytes of scratch
-// (nActive = length of ball_query_idxs).  Same outputs, bit for bit.
-// dev_counts: the sizes are read on the device (w.scalars, written by the count kernels enqueued in front); sumNPoint / nCluster are
-// then UPPER BOUNDS for the grids (the star pass and the replay walk `nCluster` slots and find the real count on the device), and
-// the generic level loop for clusters beyond the LDS bitmap is left to the caller, who launches it once it knows sumNPoint.
-static int cl_fill2_impl(const int *semantic_label, const int *ball_query_idxs, const int *start_len,
-                         int n, void *ws, size_t ws_bytes, void *erec, size_t erec_bytes, long long nActive,
-                         int *cluster_idxs, int *cluster_offsets, int sumNPoint, int nCluster, bool dev_counts, int c0, void *stream) {
-    if (n <= 0) return 0;
-    ClWs w;
-    if (!cl_carve(ws, ws_bytes, n, w)) return D3_ERR_WORKSPACE;
-    if (erec == nullptr || erec_bytes < d3_bfs_cluster_erec_bytes(nActive)) return D3_ERR_WORKSPACE;
-    hipStream_t s = d3_stream(stream);
-    const int T = 256, nb = (n + T - 1) / T, nwb = (n + 3) / 4;
-    const int *cnt = dev_counts ? w.scalars : nullptr;
-    if (c0 == 0)
-        cl_seed_kernel<<<nb, T, 0, s>>>(w.flag, w.cid, w.koff, n, w.seeds, cluster_offsets, nCluster, sumNPoint, nCluster > 0 ? w.lcnt : nullptr, w.star, cnt);
-    if (nCluster > 0) {
-        static bool attr_done_dev[64] = {false};   // the attribute is per device
-        const size_t lds = (size_t)B2_LDS_INTS * sizeof(int);
-        int dev_id = 0;
-        if (hipGetDevice(&dev_id) != hipSuccess || dev_id < 0 || dev_id >= 64 || !attr_done_dev[dev_id]) {
-            D3_CHECK(hipFuncSetAttribute((const void *)cl_bfs2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            if (dev_id >= 0 && dev_id < 64) attr_done_dev[dev_id] = true;
-        }
-        const bool no_star = d3_tune(D3T_BFS_NO_STAR) != 0;   // (tests: force the level loop for every cluster)
-        if (c0 == 0) {      // (c0 > 0: a second replay launch for the clusters beyond the speculative grid -- the tables are built)
-        if (!no_star)
-            cl_star_kernel<<<(nCluster + 3) / 4, T, 0, s>>>(ball_query_idxs, start_len, w.own, w.seeds, w.koff, w.sizes, nCluster, w.star,
-                                                           cluster_idxs, cnt);
-        cl_lid_kernel<<<nb, T, 0, s>>>(w.own, w.flag, w.star, start_len, w.lcnt, w.lid, w.klen, n);
-        int rc = d3_exclusive_scan_i32(w.klen, w.estart, n, w.temp, w.temp_bytes, s);
-        if (rc) return rc;
-        cl_ninfo_kernel<<<nb, T, 0, s>>>(w.own, w.lid, w.estart, start_len, w.ninfo, n);
-        cl_erec_kernel<<<(int)(((long long)n * CL_EG + T - 1) / T), T, 0, s>>>(ball_query_idxs, start_len, w.own, w.flag, w.star, w.ninfo, w.estart, (int4 *)erec, n);
-        }
-        // launch timing (bench.py): SURVEY 8(d) "BFS/CC" bytes = 4 nActive + 12 n + 8 S, nActive = the list entries of the kept
-        // clusters' nodes (what the replay streams; the padded lists' capacity says nothing) -- known on the device only
-        void *pr = d3_prof_begin(5, 12.0 * (double)n + (dev_counts ? 0.0 : 8.0 * (double)sumNPoint), 0.0, s);
-        cl_bfs2_kernel<<<nCluster - c0, B2_THREADS, lds, s>>>((const int4 *)erec, start_len, w.estart, w.lid, w.seeds, w.koff, w.sizes,
-                                                        w.star, w.fcnt, w.qln, cluster_idxs, 0, cnt, c0);
-        if (pr) {
-            d3_prof_tag(pr, 0, n); d3_prof_tag(pr, 1, nCluster); d3_prof_end(pr, s);
-            if (double *slot = d3_prof_dev_slot(pr, 4.0)) cl_prof_total_kernel<<<1, 1, 0, s>>>(w.estart, w.klen, n, slot, cnt);   // (behind the bracket)
-        }
-        // clusters beyond the LDS bitmap: the generic level loop (none can exist when all kept points together fit)
-        if (!dev_counts && c0 == 0 && sumNPoint > B2_MAXSIZE)
-            cl_bfs_kernel<<<nCluster, CL_BFS_THREADS, 0, s>>>(semantic_label, ball_query_idxs, start_len, w.own, w.seeds,
-                                                         w.koff, w.sizes, w.par, w.queue, w.fcnt, w.qln, cluster_idxs, B2_MAXSIZE);
-    }
-    D3_LAUNCH_CHECK();
-    return 0;
-}
+// ------------------------------------------------------------------------------------------------------------------
+// host side.  One clustering is `begin` + `end` (d3_bfs_cluster_run: both in one call):
+//   count : cl_count_enqueue, repeated by cl_count_loop until the label push has converged -> sizes, kept flags, cluster ids / offsets
+//           in the workspace, nCluster / sumNPoint in scalars[1] / [2];
+//   fill  : cl_fill -- seeds and offsets, the star shortcut, the edge records, the record-form replay (cl_bfs2_kernel); clusters
+//           beyond its LDS bitmap are left to the generic level loop (cl_bfs_oversized).
+// `begin` enqueues the first count iteration, the copy of its scalars, an event, and the WHOLE fill with its sizes read on the device
+// (upper-bound grids: the speculative fill); `end` waits for the event -- not for the stream: while the host reads the counts the
+// record pass and the replay are already running -- and finishes the rare cases: kept clusters beyond the speculative grid, clusters
+// beyond the LDS bitmap, and a label push that had not converged (cl_finish_blocking then overwrites the speculative output).  ONE
+// host thread can so keep two clusterings (PointGroup's shifted and unshifted branch, on two streams) in flight: begin, begin, end,
+// end -- no helper thread whose wake-up sits on the step's critical path (on a slow host the wait for the helper's branch grew from
+// 0.5 to 0.8 ms: profiles r05_d vs r05_e).  When the speculative form is not available (D3_CL_SPEC=0, cap_points < n) `begin` runs
+// cl_finish_blocking itself and `end` only hands the sizes over.
 
-extern "C" int d3_bfs_cluster_fill2(const int *semantic_label, const int *ball_query_idxs, const int *start_len,
-                                    int n, void *ws, size_t ws_bytes, void *erec, size_t erec_bytes, long long nActive,
-                                    int *cluster_idxs, int *cluster_offsets, int sumNPoint, int nCluster, void *stream) {
-    D3_CLEAR();
-    return cl_fill2_impl(semantic_label, ball_query_idxs, start_len, n, ws, ws_bytes, erec, erec_bytes, nActive, cluster_idxs, cluster_offsets,
-                         sumNPoint, nCluster, false, 0, stream);
-}
-
-// count + fill as ONE native call (round 5): the caller hands in outputs at their upper bounds (cluster_idxs: cap_points x 2 ints,
-// cluster_offsets: cap_clusters + 1 ints) and reads back how much of them was written.  Between the two phases the two-call form
-// goes back to its caller for the output allocation; when that caller is a Python thread next to another busy one (the two
-// clustering branches of PointGroup.forward), re-acquiring the interpreter lock there cost 80 - 470 us of idle queue per branch
-// (gpurun_out/r05_j11/cluster_timeline.txt).  Same results as count_ex + fill2: it IS count_ex + fill2.
-// A pinned landing buffer + event per in-flight count (pooled; the clustering branches run on two host threads)
+// A pinned landing buffer + event per in-flight count (pooled; the clustering branches may run on two host threads)
 struct ClTicket { int *pinned; hipEvent_t ev; };
 static std::mutex g_clt_mu;
 static std::vector<ClTicket *> g_clt_free;
 #define CL_SPEC_GRID 2048      // cluster slots of the speculative replay launch (more kept clusters: a second launch once the count is known)
 
-// begin / end (round 5): d3_bfs_cluster_run cut at its one host wait.  `begin` enqueues the count kernels, the copy of their scalars,
-// an event and the whole speculative fill, and returns a ticket; `end` waits for the event and finishes (the rare cases: more label
-// sweeps, kept clusters beyond the speculative grid, clusters beyond the LDS bitmap).  ONE host thread can so keep two clusterings
-// (PointGroup's shifted and unshifted branch, on two streams) in flight: begin, begin, end, end -- no helper thread whose wake-up
-// sits on the step's critical path (on a slow host the wait for the helper's branch grew from 0.5 to 0.8 ms: profiles r05_d vs r05_e).
-// When the speculative form is not available (D3_CL_SPEC=0, cap_points < n) `begin` runs the whole blocking call.
+// one call's arguments (as d3_bfs_cluster_begin takes them), and what `begin` leaves for `end`
 struct ClRun {
     const int *sem, *idx, *start_len; int n, threshold; void *ws; size_t ws_bytes; void *erec; size_t erec_bytes; long long nActive; int flags;
     int *cluster_idxs; long long cap_points; int *cluster_offsets; long long cap_clusters; void *stream;
-    ClTicket *t; int slots; int done; int rc; int sumNPoint, nCluster;
+    ClTicket *t;                // the count in flight; NULL when `begin` finished the clustering itself
+    int slots;                  // cluster slots of the speculative replay launch
+    int sumNPoint, nCluster;    // the sizes when `begin` finished the clustering itself
 };
-extern "C" int d3_bfs_cluster_end(void *ticket, int *sumNPoint_host, int *nCluster_host);
+static void cl_run_free(ClRun *r) {
+    if (r->t) { std::lock_guard<std::mutex> lk(g_clt_mu); g_clt_free.push_back(r->t); }
+    delete r;
+}
+typedef std::unique_ptr<ClRun, void (*)(ClRun *)> ClRunPtr;
+
+// One iteration of the count phase, enqueued only: a pair of label-push sweeps (it == 0: also the union-find in front of them), owners,
+// sizes, kept flags, cluster ids / offsets, and the copy of the scalars to `h` (6 ints; pinned memory for the asynchronous form).
+static int cl_count_enqueue(const ClRun &r, ClWs &w, int it, int *h) {
+    const int n = r.n, asc = (r.flags & D3_BFS_ASCENDING) ? 1 : 0;
+    hipStream_t s = d3_stream(r.stream);
+    const int T = 256, nb = (n + T - 1) / T;
+    if (it == 0) {
+        cl_init_kernel<<<nb, T, 0, s>>>(w.parent, w.lab, w.sizes, w.par, w.klen, w.qln, n, w.scalars);   // (klen, qln: scratch until the fill)
+        // one hook per node under a smaller-index neighbour first (ECL-CC init), then the hooked trees flattened before the unions: most
+        // edges then find parent[i] == parent[j] with two loads and no walk (speaker step 16.59 -> 16.42 ms in-process, round 5)
+        cl_hook_kernel<<<nb, T, 0, s>>>(r.sem, r.idx, r.start_len, n, w.parent);
+        cl_flatten_kernel<<<nb, T, 0, s>>>(w.parent, n);
+        cl_union_kernel<<<(int)(((long long)n * CL_UG + T - 1) / T), T, 0, s>>>(r.sem, r.idx, r.start_len, n, w.parent, w.scalars);
+        cl_flatten_kernel<<<nb, T, 0, s>>>(w.parent, n);
+        D3_LAUNCH_CHECK();
+    }
+    // Label pushes in pairs, and the sizes / ids / offsets computed right behind them, all read back with ONE host round
+    // trip: the usual case is one productive sweep plus the sweep that finds nothing left to do (the second one reports
+    // through its own flag, scalars[4]); only when both sweeps still changed labels is the tail recomputed after more.
+    const int npb = nb < 2048 ? nb : 2048;        // label push: a bounded grid, one thread per node for the filters, a wave per surviving list
+    if (it > 0) {          // (the first pair of sweeps finds both flags zeroed by cl_init_kernel: two 4-byte fill launches less per clustering)
+        D3_CHECK(hipMemsetAsync(w.scalars, 0, sizeof(int), s));
+        D3_CHECK(hipMemsetAsync(w.scalars + 4, 0, sizeof(int), s));
+    }
+    if (it == 0 && asc)
+        cl_push_kernel<<<npb, T, 0, s>>>(r.sem, r.idx, r.start_len, n, w.parent, w.lab, w.klen, w.qln, w.scalars, w.scalars + 3, asc, 1);
+    cl_push_kernel<<<npb, T, 0, s>>>(r.sem, r.idx, r.start_len, n, w.parent, w.lab, w.klen, w.qln, w.scalars, w.scalars + 3, asc, 0);
+    cl_push_kernel<<<npb, T, 0, s>>>(r.sem, r.idx, r.start_len, n, w.parent, w.lab, w.klen, w.qln, w.scalars + 4, w.scalars + 3, asc, 0);
+    if (it > 0) D3_CHECK(hipMemsetAsync(w.sizes, 0, (size_t)n * sizeof(int), s));   // (cl_owner_kernel accumulates)
+    cl_owner_kernel<<<nb, T, 0, s>>>(w.parent, w.lab, w.own, w.sizes, n);
+    cl_keep_kernel<<<nb, T, 0, s>>>(w.sizes, w.flag, w.ksz, n, r.threshold, r.start_len, w.scalars);
+    int rc = d3_exclusive_scan_i32(w.flag, w.cid, n, w.temp, w.temp_bytes, s);
+    if (rc) return rc;
+    rc = d3_exclusive_scan_i32(w.ksz, w.koff, n, w.temp, w.temp_bytes, s);
+    if (rc) return rc;
+    cl_totals_kernel<<<1, 64, 0, s>>>(w.flag, w.cid, w.ksz, w.koff, n, w.scalars);
+    D3_LAUNCH_CHECK();
+    D3_CHECK(hipMemcpyAsync(h, w.scalars, 6 * sizeof(int), hipMemcpyDeviceToHost, s));
+    return 0;
+}
+
+// The count on the host: iterations from it0, each followed by a wait for the stream, while both sweeps of a pair still changed
+// labels (h[0], h[4]) and it < n + 2.  Leaves the six scalars of the last iteration in h.
+static int cl_count_loop(const ClRun &r, ClWs &w, int it0, int *h) {
+    for (int it = it0;; it += 2) {
+        int rc = cl_count_enqueue(r, w, it, h);
+        if (rc) return rc;
+        D3_CHECK(hipStreamSynchronize(d3_stream(r.stream)));
+        if (!h[0] || !h[4] || it >= r.n + 2) return 0;
+    }
+}
+
+// clusters beyond the LDS bitmap of the record-form replay: the generic level loop, which skips every cluster of at most B2_MAXSIZE
+// points (none larger can exist when all kept points together fit: the callers' condition)
+static void cl_bfs_oversized(const ClRun &r, ClWs &w, int nCluster) {
+    cl_bfs_kernel<<<nCluster, CL_BFS_THREADS, 0, d3_stream(r.stream)>>>(r.sem, r.idx, r.start_len, w.own, w.seeds, w.koff, w.sizes, w.par, w.queue,
+                                                                       w.fcnt, w.qln, r.cluster_idxs, B2_MAXSIZE);
+}
+
+// The fill behind a count: cluster_offsets, and cluster_idxs in the reference's visitation order (r.erec: scratch for the edge records).
+// dev_counts: the sizes are read on the device (w.scalars, written by the count kernels enqueued in front); sumNPoint / nCluster are
+// then UPPER BOUNDS for the grids (the star pass and the replay walk `nCluster` slots and find the real count on the device), and
+// the clusters beyond the LDS bitmap are left to the caller, who launches cl_bfs_oversized once it knows sumNPoint.
+// c0 > 0: only the replay of the clusters from c0 on (those beyond the speculative grid), on the tables the c0 == 0 call built.
+static int cl_fill(const ClRun &r, ClWs &w, int sumNPoint, int nCluster, bool dev_counts, int c0) {
+    const int n = r.n;
+    hipStream_t s = d3_stream(r.stream);
+    const int T = 256, nb = (n + T - 1) / T;
+    const int *cnt = dev_counts ? w.scalars : nullptr;
+    if (c0 == 0)
+        cl_seed_kernel<<<nb, T, 0, s>>>(w.flag, w.cid, w.koff, n, w.seeds, r.cluster_offsets, nCluster, sumNPoint, nCluster > 0 ? w.lcnt : nullptr, w.star, cnt);
+    if (nCluster > 0) {
+        static bool attr_done_dev[64] = {false};
+        const size_t lds = (size_t)B2_LDS_INTS * sizeof(int);
+        if (d3_once_per_device(attr_done_dev))
+            D3_CHECK(hipFuncSetAttribute((const void *)cl_bfs2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        if (c0 == 0) {
+            if (d3_tune(D3T_BFS_NO_STAR) == 0)   // (tests: the switch forces the level loop for every cluster)
+                cl_star_kernel<<<(nCluster + 3) / 4, T, 0, s>>>(r.idx, r.start_len, w.own, w.seeds, w.koff, w.sizes, nCluster, w.star, r.cluster_idxs, cnt);
+            cl_lid_kernel<<<nb, T, 0, s>>>(w.own, w.flag, w.star, r.start_len, w.lcnt, w.lid, w.klen, n);
+            int rc = d3_exclusive_scan_i32(w.klen, w.estart, n, w.temp, w.temp_bytes, s);
+            if (rc) return rc;
+            cl_ninfo_kernel<<<nb, T, 0, s>>>(w.own, w.lid, w.estart, r.start_len, w.ninfo, n);
+            cl_erec_kernel<<<(int)(((long long)n * CL_EG + T - 1) / T), T, 0, s>>>(r.idx, r.start_len, w.own, w.flag, w.star, w.ninfo, w.estart, (int4 *)r.erec, n);
+        }
+        // launch timing (bench.py): SURVEY 8(d) "BFS/CC" bytes = 4 nActive + 12 n + 8 S, nActive = the list entries of the kept
+        // clusters' nodes (what the replay streams; the padded lists' capacity says nothing) -- known on the device only
+        void *pr = d3_prof_begin(5, 12.0 * (double)n + (dev_counts ? 0.0 : 8.0 * (double)sumNPoint), 0.0, s);
+        cl_bfs2_kernel<<<nCluster - c0, B2_THREADS, lds, s>>>((const int4 *)r.erec, r.start_len, w.estart, w.lid, w.seeds, w.koff, w.sizes,
+                                                        w.star, w.fcnt, w.qln, r.cluster_idxs, 0, cnt, c0);
+        if (pr) {
+            d3_prof_tag(pr, 0, n); d3_prof_tag(pr, 1, nCluster); d3_prof_end(pr, s);
+            if (double *slot = d3_prof_dev_slot(pr, 4.0)) cl_prof_total_kernel<<<1, 1, 0, s>>>(w.estart, w.klen, n, slot, cnt);   // (behind the bracket)
+        }
+        if (!dev_counts && c0 == 0 && sumNPoint > B2_MAXSIZE) cl_bfs_oversized(r, w, nCluster);
+    }
+    D3_LAUNCH_CHECK();
+    return 0;
+}
+
+// The clustering with its counts read on the host: the count from iteration it0 on (h: the scalars of the iterations before, if any),
+// the sizes checked against the outputs' bounds, the fill with exact grids.
+static int cl_finish_blocking(const ClRun &r, ClWs &w, int it0, int *h, int *sumNPoint, int *nCluster) {
+    int rc = cl_count_loop(r, w, it0, h);
+    if (rc) return rc;
+    *nCluster = h[1]; *sumNPoint = h[2];
+    if ((long long)h[2] > r.cap_points || (long long)h[1] > r.cap_clusters) return D3_ERR_WORKSPACE;
+    return cl_fill(r, w, h[2], h[1], false, 0);
+}
+
+// Returns 0 and a ticket that d3_bfs_cluster_end consumes, or a non-zero status and *ticket == NULL with nothing left allocated.
 extern "C" int d3_bfs_cluster_begin(const int *semantic_label, const int *ball_query_idxs, const int *start_len, int n, int threshold,
                                     void *ws, size_t ws_bytes, void *erec, size_t erec_bytes, long long nActive, int flags,
                                     int *cluster_idxs, long long cap_points, int *cluster_offsets, long long cap_clusters,
                                     void **ticket, void *stream) {
     if (!ticket) return D3_ERR_ARG;
     *ticket = nullptr;
-    ClRun *r = new ClRun{semantic_label, ball_query_idxs, start_len, n, threshold, ws, ws_bytes, erec, erec_bytes, nActive, flags,
-                         cluster_idxs, cap_points, cluster_offsets, cap_clusters, stream, nullptr, 0, 0, 0, 0, 0};
-    if (n <= 0 || d3_tune(D3T_CL_SPEC) == 0 || cap_points < n) {
-        int S = 0, P = 0;
-        int rc = cl_count(semantic_label, ball_query_idxs, start_len, n, threshold, ws, ws_bytes, &S, &P, flags, stream);
-        if (!rc && n > 0) {
-            if ((long long)S > cap_points || (long long)P > cap_clusters) rc = D3_ERR_WORKSPACE;
-            else rc = d3_bfs_cluster_fill2(semantic_label, ball_query_idxs, start_len, n, ws, ws_bytes, erec, erec_bytes, nActive, cluster_idxs,
-                                           cluster_offsets, S, P, stream);
-        }
-        r->done = 1; r->rc = rc; r->sumNPoint = S; r->nCluster = P;
-        *ticket = r;
-        return rc;
-    }
-    // Speculative form: the count kernels, the copy of their scalars and an event are enqueued, then the WHOLE fill with its sizes
-    // read on the device (upper-bound grids); the host waits later (`end`) -- for the event, not for the stream: while it reads the
-    // counts the record pass and the level replay are already running.  Should the label push not have converged in its first pair
-    // of sweeps (both sweeps still changed labels: capped lists in a chain), the speculative fill's output is overwritten by the
-    // regular path in `end`.
     D3_CLEAR();
-    int rc = 0;
+    ClRunPtr r(new ClRun{semantic_label, ball_query_idxs, start_len, n, threshold, ws, ws_bytes, erec, erec_bytes, nActive, flags,
+                         cluster_idxs, cap_points, cluster_offsets, cap_clusters, stream, nullptr, 0, 0, 0}, cl_run_free);
+    if (n <= 0) { *ticket = r.release(); return 0; }
     ClWs w;
-    if (erec == nullptr || erec_bytes < d3_bfs_cluster_erec_bytes(nActive) || !cl_carve(ws, ws_bytes, n, w)) { delete r; return D3_ERR_WORKSPACE; }
-    const int asc = (flags & D3_BFS_ASCENDING) ? 1 : 0;
-    hipStream_t s = d3_stream(stream);
+    // (both buffers at their whole queried sizes: d3_bfs_cluster_ws_bytes is the carve plus its slack)
+    if (erec == nullptr || erec_bytes < d3_bfs_cluster_erec_bytes(nActive) || ws_bytes < d3_bfs_cluster_ws_bytes(n) ||
+        !cl_carve(ws, ws_bytes, n, w))
+        return D3_ERR_WORKSPACE;
+    if (d3_tune(D3T_CL_SPEC) == 0 || cap_points < n) {
+        int h[6] = {0, 0, 0, 0, 0, 0};
+        int rc = cl_finish_blocking(*r, w, 0, h, &r->sumNPoint, &r->nCluster);
+        if (rc) return rc;
+        *ticket = r.release();
+        return 0;
+    }
+    // (should the label push not have converged in its first pair of sweeps -- both still changed labels: capped lists in a chain --
+    // `end` overwrites the speculative fill's output by the blocking path)
     ClTicket *t = nullptr;
     {
         std::lock_guard<std::mutex> lk(g_clt_mu);
@@ -1106,70 +1067,52 @@ extern "C" int d3_bfs_cluster_begin(const int *semantic_label, const int *ball_q
         t = new ClTicket{nullptr, nullptr};
         hipError_t he = hipHostMalloc((void **)&t->pinned, 8 * sizeof(int));
         if (he == hipSuccess) he = hipEventCreateWithFlags(&t->ev, hipEventDisableTiming);
-        if (he != hipSuccess) { delete t; delete r; return (int)he; }
+        if (he != hipSuccess) { delete t; return (int)he; }
     }
     r->t = t;
-    auto fail = [&](int code) { { std::lock_guard<std::mutex> lk(g_clt_mu); g_clt_free.push_back(t); } delete r; return code; };
-    rc = cl_count_enqueue(semantic_label, ball_query_idxs, start_len, n, threshold, w, asc, 0, t->pinned, s);
-    if (rc) return fail(rc);
-    if (hipEventRecord(t->ev, s) != hipSuccess) return fail(D3_ERR_ARG);
+    int rc = cl_count_enqueue(*r, w, 0, t->pinned);
+    if (rc) return rc;
+    if (hipEventRecord(t->ev, d3_stream(stream)) != hipSuccess) return D3_ERR_ARG;
     r->slots = (int)(cap_clusters < CL_SPEC_GRID ? cap_clusters : CL_SPEC_GRID);
     // (cluster_offsets has cap_clusters + 1 entries and cluster_idxs n rows: whatever the device counts turn out to be, they fit)
-    rc = cl_fill2_impl(semantic_label, ball_query_idxs, start_len, n, ws, ws_bytes, erec, erec_bytes, nActive, cluster_idxs, cluster_offsets,
-                       n, r->slots > 0 ? r->slots : 1, true, 0, stream);
-    if (rc) return fail(rc);
-    *ticket = r;
+    rc = cl_fill(*r, w, n, r->slots > 0 ? r->slots : 1, true, 0);
+    if (rc) return rc;
+    *ticket = r.release();
     return 0;
 }
 extern "C" int d3_bfs_cluster_end(void *ticket, int *sumNPoint_host, int *nCluster_host) {
     if (!ticket || !sumNPoint_host || !nCluster_host) return D3_ERR_ARG;
-    ClRun *r = (ClRun *)ticket;
-    struct Free { ClRun *r; ~Free() { if (r->t) { std::lock_guard<std::mutex> lk(g_clt_mu); g_clt_free.push_back(r->t); } delete r; } } fr{r};
-    *sumNPoint_host = 0; *nCluster_host = 0;
-    if (r->done) { *sumNPoint_host = r->sumNPoint; *nCluster_host = r->nCluster; return r->rc; }
+    ClRunPtr r((ClRun *)ticket, cl_run_free);
+    *sumNPoint_host = r->sumNPoint; *nCluster_host = r->nCluster;
+    if (!r->t) return 0;      // `begin` finished the clustering
     D3_CLEAR();
-    const int n = r->n;
-    hipStream_t s = d3_stream(r->stream);
     ClWs w;
-    if (!cl_carve(r->ws, r->ws_bytes, n, w)) return D3_ERR_WORKSPACE;
-    const int asc = (r->flags & D3_BFS_ASCENDING) ? 1 : 0;
+    if (!cl_carve(r->ws, r->ws_bytes, r->n, w)) return D3_ERR_WORKSPACE;
     D3_CHECK(hipEventSynchronize(r->t->ev));
     int h[6];
     for (int k = 0; k < 6; k++) h[k] = r->t->pinned[k];
-    int rc = 0;
-    if (h[0] && h[4]) {      // not converged: more sweeps, then the regular fill over the speculative one
-        for (int it = 2;; it += 2) {
-            rc = cl_count_enqueue(r->sem, r->idx, r->start_len, n, r->threshold, w, asc, it, h, s);
-            if (rc) return rc;
-            D3_CHECK(hipStreamSynchronize(s));
-            if (!h[0] || !h[4] || it >= n + 2) break;
-        }
-        *nCluster_host = h[1]; *sumNPoint_host = h[2];
-        if ((long long)h[2] > r->cap_points || (long long)h[1] > r->cap_clusters) return D3_ERR_WORKSPACE;
-        return d3_bfs_cluster_fill2(r->sem, r->idx, r->start_len, n, r->ws, r->ws_bytes, r->erec, r->erec_bytes, r->nActive, r->cluster_idxs,
-                                    r->cluster_offsets, h[2], h[1], r->stream);
-    }
+    if (h[0] && h[4]) return cl_finish_blocking(*r, w, 2, h, sumNPoint_host, nCluster_host);      // not converged: more sweeps, the fill again
     *nCluster_host = h[1]; *sumNPoint_host = h[2];
     if ((long long)h[1] > r->cap_clusters) return D3_ERR_WORKSPACE;      // (cannot happen for cap_clusters >= n / threshold: kept clusters have >= threshold points)
-    if (h[1] > r->slots)        // kept clusters beyond the speculative grid: their replay now, on the tables the first launch built
-        rc = cl_fill2_impl(r->sem, r->idx, r->start_len, n, r->ws, r->ws_bytes, r->erec, r->erec_bytes, r->nActive, r->cluster_idxs, r->cluster_offsets,
-                           h[2], h[1], false, r->slots, r->stream);
-    if (rc) return rc;
-    if (h[2] > B2_MAXSIZE && h[1] > 0)      // clusters beyond the LDS bitmap: the generic level loop (none can exist when all kept points together fit)
-        cl_bfs_kernel<<<h[1], CL_BFS_THREADS, 0, s>>>(r->sem, r->idx, r->start_len, w.own, w.seeds, w.koff, w.sizes, w.par, w.queue,
-                                                     w.fcnt, w.qln, r->cluster_idxs, B2_MAXSIZE);
+    if (h[1] > r->slots) {      // kept clusters beyond the speculative grid: their replay now, on the tables the first launch built
+        int rc = cl_fill(*r, w, h[2], h[1], false, r->slots);
+        if (rc) return rc;
+    }
+    if (h[2] > B2_MAXSIZE && h[1] > 0) cl_bfs_oversized(*r, w, h[1]);
     D3_LAUNCH_CHECK();
     return 0;
 }
+// begin + end as ONE native call: between the two a Python caller next to another busy thread (the two clustering branches of
+// PointGroup.forward on the helper-thread path) would re-acquire the interpreter lock -- 80 - 470 us of idle queue per branch
+// (measured in round 5)
 extern "C" int d3_bfs_cluster_run(const int *semantic_label, const int *ball_query_idxs, const int *start_len, int n, int threshold,
                                   void *ws, size_t ws_bytes, void *erec, size_t erec_bytes, long long nActive, int flags,
                                   int *cluster_idxs, long long cap_points, int *cluster_offsets, long long cap_clusters,
                                   int *sumNPoint_host, int *nCluster_host, void *stream) {
     if (!sumNPoint_host || !nCluster_host) return D3_ERR_ARG;
+    *sumNPoint_host = 0; *nCluster_host = 0;
     void *ticket = nullptr;
     const int rc = d3_bfs_cluster_begin(semantic_label, ball_query_idxs, start_len, n, threshold, ws, ws_bytes, erec, erec_bytes, nActive, flags,
                                         cluster_idxs, cap_points, cluster_offsets, cap_clusters, &ticket, stream);
-    if (!ticket) { *sumNPoint_host = 0; *nCluster_host = 0; return rc; }
-    const int rc2 = d3_bfs_cluster_end(ticket, sumNPoint_host, nCluster_host);
-    return rc ? rc : rc2;
+    return rc ? rc : d3_bfs_cluster_end(ticket, sumNPoint_host, nCluster_host);
 }

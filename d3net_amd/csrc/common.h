@@ -26,6 +26,16 @@ static inline hipStream_t d3_stream(void *s) { return (hipStream_t)s; }
 
 static inline size_t d3_align(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
 
+// true on the first call per device for a flag array `done[64]` (a dynamic-LDS attribute is set per device), and whenever the device
+// cannot be told
+static inline bool d3_once_per_device(bool *done) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return true;
+    if (done[dev]) return false;
+    done[dev] = true;
+    return true;
+}
+
 // carve typed, 256-byte aligned regions out of a workspace.  A layout function lists the regions once; the run carves
 // with it and checks ok() before its first launch, the *_ws_bytes query runs it on a null base (take() then returns
 // nullptr and only advances off) and reads off.
@@ -58,9 +68,6 @@ int d3_exclusive_scan_i32(const int *in, int *out, int n, void *temp, size_t tem
 size_t d3_sort_pairs_temp_bytes(int n);
 // stable ascending sort of (key,val) int32 pairs on the low `bits` bits of key
 int d3_sort_pairs_i32(const int *kin, int *kout, const int *vin, int *vout, int n, int bits, void *temp,
-                      size_t temp_bytes, hipStream_t s);
-size_t d3_sort_pairs_u64_temp_bytes(int n);
-int d3_sort_pairs_u64(const unsigned long long *kin, unsigned long long *kout, const int *vin, int *vout, int n, void *temp,
                       size_t temp_bytes, hipStream_t s);
 
 // batched fp32-MFMA GEMMs and column sums (implemented in hgemm.hip)

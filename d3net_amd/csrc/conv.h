@@ -23,15 +23,6 @@ __device__ __forceinline__ unsigned int pack2bf2(float lo, float hi) {   // v_cv
 int d3_conv_ncu();
 // one more launch that read a 16-bit kernel map: what d3_spconv_t16_launches() counts (spconv2.hip)
 void d3_conv_count_t16();
-// true on the first call per device for a flag array `done[64]` (a dynamic-LDS attribute is set per device), and whenever the device
-// cannot be told
-static inline bool d3_once_per_device(bool *done) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return true;
-    if (done[dev]) return false;
-    done[dev] = true;
-    return true;
-}
 
 // ------------------------------------------------------------------------------ dispatchers <-> executor
 // fused BatchNorm backward of a data-gradient call (d3_spconv_fwd2_bnbwd): x is the BatchNorm INPUT, fp32, or bf16 with xbf16

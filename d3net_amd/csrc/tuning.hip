@@ -23,7 +23,7 @@ const Entry kTable[D3T_COUNT] = {
     {"D3_KMAP16", 1},               // 0: the executor's K = 27 convolutions read the dense int32 kernel maps only
     {"D3_HG_SPLITK", 256},          // largest number of 16 x 16 output tiles of a deep (K >= 8192) heads GEMM whose reduction is cut over 4 workgroups; 0: never
     {"D3_BN_PART2", 1},             // 0: BatchNorm launches reduce the producer's whole per-workgroup partial table (rounds 1-4) instead of the 16-row fp64 second-level table
-    {"D3_CL_SPEC", 1},              // 0: d3_bfs_cluster_run waits for the cluster counts before it enqueues the fill (count_ex + fill2); 1: the fill is enqueued behind the count kernels with its sizes read on the device, the host waits for the counts while the fill already runs
+    {"D3_CL_SPEC", 1},              // 0: d3_bfs_cluster_run waits for the cluster counts before it enqueues the fill; 1: the fill is enqueued behind the count kernels with its sizes read on the device, the host waits for the counts while the fill already runs
     {"D3_TD_FUSE_GATES", 1},        // 0: the captioner's backward step keeps its two GRU gate kernels (rounds 2-4: 6 dependent launches per step) instead of running them as epilogues of the GEMMs that complete their input (4 launches)
     {"D3_C3", 1},                   // 0: the K = 27 convolutions of the big levels never run spconv_fwd3_kernel (lane table, round 6) -- A/B against spconv_fwd2_kernel
 };

@@ -278,6 +278,29 @@ def ballquery_batch_p_padded(coords, batch_idxs, batch_offsets, radius, max_byte
     return idx, start_len
 
 
+def _cluster_args(sem, idx, sl, threshold, ascending, ws_tag):
+    """what d3_bfs_cluster_run and d3_bfs_cluster_begin share, for device tensors on the current device: their leading arguments (up to
+    cap_clusters), the tensors those point into (to be kept alive until the clustering has ended), and the two outputs at their
+    upper bounds -- N points, N / threshold + 1 clusters -- which the caller slices by the returned sizes"""
+    N = sl.size(0)
+    assert sem.is_contiguous() and sem.dtype == torch.int32
+    assert idx.is_contiguous() and idx.dtype == torch.int32
+    assert sl.is_contiguous() and sl.dtype == torch.int32
+    dev = sem.device
+    if idx.numel() == 0:
+        idx = torch.zeros(1, dtype=torch.int32, device=dev)
+    L = _lib.lib()
+    nact = int(idx.numel())
+    ws = _workspace(L.d3_bfs_cluster_ws_bytes(N), dev, "cl" + ws_tag)
+    rec = _workspace(L.d3_bfs_cluster_erec_bytes(nact), dev, "clrec" + ws_tag)
+    capP, capC = max(N, 1), N // max(int(threshold), 1) + 1
+    cluster_idxs = torch.empty((capP, 2), dtype=torch.int32, device=dev)
+    cluster_offsets = torch.empty(capC + 1, dtype=torch.int32, device=dev)
+    args = (_ptr(sem), _ptr(idx), _ptr(sl), N, int(threshold), _ptr(ws), ws.numel(), _ptr(rec), rec.numel(), nact, 1 if ascending else 0,
+            _ptr(cluster_idxs), capP, _ptr(cluster_offsets), capC)
+    return args, (sem, idx, sl, ws, rec), cluster_idxs, cluster_offsets
+
+
 class BFSCluster(Function):
     @staticmethod
     def forward(ctx, semantic_label, ball_query_idxs, start_len, threshold, ascending=False):
@@ -290,31 +313,17 @@ class BFSCluster(Function):
         :return: cluster_idxs:  int (sumNPoint, 2), dim 0 for cluster_id, dim 1 for corresponding point idxs in N
         :return: cluster_offsets: int (nCluster + 1)
         """
-        N = start_len.size(0)
-        assert semantic_label.is_contiguous() and semantic_label.dtype == torch.int32
-        assert ball_query_idxs.is_contiguous() and ball_query_idxs.dtype == torch.int32
-        assert start_len.is_contiguous() and start_len.dtype == torch.int32
         on_cpu = not semantic_label.is_cuda
         dev = _device_of(semantic_label, ball_query_idxs, start_len)
-        sem, idx, sl = (t.to(dev) for t in (semantic_label, ball_query_idxs, start_len))
-        if idx.numel() == 0:
-            idx = torch.zeros(1, dtype=torch.int32, device=dev)
-        L = _lib.lib()
+        S, P = C.c_int(0), C.c_int(0)
         with _on(dev):
-            ws = _workspace(L.d3_bfs_cluster_ws_bytes(N), dev, "cl")
-            S, P = C.c_int(0), C.c_int(0)
-            nact = int(idx.numel())
-            rec = _workspace(L.d3_bfs_cluster_erec_bytes(nact), dev, "clrec")
-            # ONE native call for count + fill: outputs at their upper bounds (N points, N / threshold + 1 clusters), sliced below --
-            # going back to the interpreter between the phases costs the interpreter lock when the other clustering branch is busy
-            capP, capC = max(N, 1), N // max(int(threshold), 1) + 1
-            cluster_idxs = torch.empty((capP, 2), dtype=torch.int32, device=dev)
-            cluster_offsets = torch.empty(capC + 1, dtype=torch.int32, device=dev)
-            check(L.d3_bfs_cluster_run(_ptr(sem), _ptr(idx), _ptr(sl), N, int(threshold), _ptr(ws), ws.numel(), _ptr(rec), rec.numel(), nact,
-                                       1 if ascending else 0, _ptr(cluster_idxs), capP, _ptr(cluster_offsets), capC,
-                                       C.byref(S), C.byref(P), _stream()), "bfs_cluster_run")
+            # ONE native call for count + fill: going back to the interpreter between the phases costs the interpreter lock when the
+            # other clustering branch is busy
+            args, _keep, cluster_idxs, cluster_offsets = _cluster_args(*(t.to(dev) for t in (semantic_label, ball_query_idxs, start_len)),
+                                                                       threshold, ascending, "")
+            check(_lib.lib().d3_bfs_cluster_run(*args, C.byref(S), C.byref(P), _stream()), "bfs_cluster_run")
             cluster_idxs, cluster_offsets = cluster_idxs[:S.value], cluster_offsets[:P.value + 1]
-            if N == 0:
+            if start_len.size(0) == 0:
                 cluster_offsets.zero_()
         if on_cpu:
             return cluster_idxs.cpu(), cluster_offsets.cpu()
@@ -337,26 +346,14 @@ def bfs_cluster_begin(semantic_label, ball_query_idxs, start_len, threshold, asc
     """`bfs_cluster` cut at its one host wait (d3_bfs_cluster_begin / _end): everything is enqueued on the current stream here, the
     cluster counts are read by `bfs_cluster_end`.  One thread keeps several clusterings in flight on different streams (begin, begin,
     end, end); ws_tag separates their cached workspaces.  Device tensors only."""
-    N = start_len.size(0)
-    assert semantic_label.is_cuda and semantic_label.is_contiguous() and semantic_label.dtype == torch.int32
-    assert ball_query_idxs.is_contiguous() and ball_query_idxs.dtype == torch.int32
-    assert start_len.is_contiguous() and start_len.dtype == torch.int32
+    assert semantic_label.is_cuda
     dev = semantic_label.device
-    idx = ball_query_idxs if ball_query_idxs.numel() > 0 else torch.zeros(1, dtype=torch.int32, device=dev)
-    L = _lib.lib()
     r = _ClusterRun()
+    tk = C.c_void_p()
     with _on(dev):
-        ws = _workspace(L.d3_bfs_cluster_ws_bytes(N), dev, "cl" + ws_tag)
-        nact = int(idx.numel())
-        rec = _workspace(L.d3_bfs_cluster_erec_bytes(nact), dev, "clrec" + ws_tag)
-        capP, capC = max(N, 1), N // max(int(threshold), 1) + 1
-        r.cluster_idxs = torch.empty((capP, 2), dtype=torch.int32, device=dev)
-        r.cluster_offsets = torch.empty(capC + 1, dtype=torch.int32, device=dev)
-        tk = C.c_void_p()
-        check(L.d3_bfs_cluster_begin(_ptr(semantic_label), _ptr(idx), _ptr(start_len), N, int(threshold), _ptr(ws), ws.numel(), _ptr(rec),
-                                     rec.numel(), nact, 1 if ascending else 0, _ptr(r.cluster_idxs), capP, _ptr(r.cluster_offsets), capC,
-                                     C.byref(tk), _stream()), "bfs_cluster_begin")
-    r.ticket, r.keep, r.N, r.dev = tk, (semantic_label, idx, start_len, ws, rec), N, dev
+        args, r.keep, r.cluster_idxs, r.cluster_offsets = _cluster_args(semantic_label, ball_query_idxs, start_len, threshold, ascending, ws_tag)
+        check(_lib.lib().d3_bfs_cluster_begin(*args, C.byref(tk), _stream()), "bfs_cluster_begin")     # (a failing begin leaves no ticket)
+    r.ticket, r.N, r.dev = tk, start_len.size(0), dev
     return r
 
 

@@ -154,53 +154,49 @@ int d3_ballquery_cap(void);
 int d3_ballquery_padded(const float *xyz, const int *batch_idxs, const int *batch_offsets, int n, float radius,
                         int *start_len, void *ws, size_t ws_bytes, int *idx_padded, void *stream);
 
-/* PG_OP.bfs_cluster  (src/bfs_cluster/bfs_cluster.cpp:28-112), on the device, two-phase.
- * count: connected components (same semantic label, directed ball-query lists, seeds in
- *        ascending index) with size >= threshold -> *sumNPoint_host, *nCluster_host.
- * fill : cluster_idxs (sumNPoint,2) = (cluster_id, point_idx) in the reference's FIFO-BFS
- *        visitation order, cluster_offsets (nCluster+1). */
-size_t d3_bfs_cluster_ws_bytes(int n);
-int d3_bfs_cluster_count(const int *semantic_label, const int *ball_query_idxs, const int *start_len, int n,
-                         int threshold, void *ws, size_t ws_bytes, int *sumNPoint_host, int *nCluster_host,
-                         void *stream);
-/* d3_bfs_cluster_count with flags.  D3_BFS_ASCENDING: the caller guarantees that every neighbour list is in ascending index
- * order (ballquery_batch_p's order, src/bfs_cluster/bfs_cluster.cu:27-47): the label propagation then skips, per node, the
- * prefix of neighbours whose label cannot change (two 64-way probes).  Same results. */
+/* PG_OP.bfs_cluster  (src/bfs_cluster/bfs_cluster.cpp:28-112), on the device (csrc/cluster.hip).
+ * count: connected components (same semantic label, directed ball-query lists, seeds in ascending index) with
+ *        size >= threshold -> sumNPoint, nCluster.  Union-find over the mutual edges, then label pushes over all edges
+ *        until nothing changes: one pair of sweeps unless capped lists form a chain.
+ * fill : cluster_idxs (sumNPoint,2) = (cluster_id, point_idx) in the reference's FIFO-BFS visitation order,
+ *        cluster_offsets (nCluster+1).  The level loop runs in "record form": a parallel pre-pass rewrites the lists of the
+ *        kept clusters as (node, dense id, list start, list length) records and one workgroup per cluster replays the BFS
+ *        with visited bits, frontier and first-discoverer arbitration in LDS -- one global round trip per batch of 3072
+ *        edges.  A cluster that is its seed's own list is written without a level loop; one of more than 262,144 points
+ *        (the LDS bitmap) by a level loop on the lists themselves.
+ * ws  : d3_bfs_cluster_ws_bytes(n) bytes;  erec: d3_bfs_cluster_erec_bytes(nActive) bytes of scratch for the records,
+ *       nActive = length of ball_query_idxs.
+ * Outputs at their upper bounds: cluster_idxs cap_points x 2 ints, cap_points >= sumNPoint -- n always suffices;
+ * cluster_offsets cap_clusters + 1 ints -- n / max(threshold, 1) + 1 suffices.  D3_ERR_WORKSPACE when ws, erec or a bound
+ * is too small.
+ * flags: D3_BFS_ASCENDING -- the caller guarantees that every neighbour list is in ascending index order
+ *        (ballquery_batch_p's order, src/bfs_cluster/bfs_cluster.cu:27-47): the label push then skips, per node, the
+ *        prefix of neighbours whose label cannot change (two 64-way probes).  Same results. */
 #define D3_BFS_ASCENDING 1
-int d3_bfs_cluster_count_ex(const int *semantic_label, const int *ball_query_idxs, const int *start_len, int n, int threshold,
-                            void *ws, size_t ws_bytes, int *sumNPoint_host, int *nCluster_host, int flags, void *stream);
-int d3_bfs_cluster_fill(const int *semantic_label, const int *ball_query_idxs, const int *start_len, int n,
-                        void *ws, size_t ws_bytes, int *cluster_idxs, int *cluster_offsets, int sumNPoint,
-                        int nCluster, void *stream);
-
-/* d3_bfs_cluster_fill with the level loop in "record form" (csrc/cluster.hip): a parallel pre-pass rewrites the lists of
- * the kept clusters as (node, dense id, list start, list length) records and the BFS keeps visited bits, frontier and
- * first-discoverer arbitration in LDS -- one global round trip per batch of 3072 edges instead of four per level.
- * erec: d3_bfs_cluster_erec_bytes(nActive) bytes of scratch, nActive = length of ball_query_idxs.  Outputs are
- * bit-identical to d3_bfs_cluster_fill. */
+size_t d3_bfs_cluster_ws_bytes(int n);
 size_t d3_bfs_cluster_erec_bytes(long long nActive);
-int d3_bfs_cluster_fill2(const int *semantic_label, const int *ball_query_idxs, const int *start_len, int n, void *ws,
-                         size_t ws_bytes, void *erec, size_t erec_bytes, long long nActive, int *cluster_idxs,
-                         int *cluster_offsets, int sumNPoint, int nCluster, void *stream);
-
-/* d3_bfs_cluster_count_ex + d3_bfs_cluster_fill2 as one call: outputs at their upper bounds (cluster_idxs: cap_points x 2
- * ints, cap_points >= sumNPoint -- n always suffices; cluster_offsets: cap_clusters + 1 ints -- n / max(threshold, 1) + 1
- * suffices), the used sizes come back in *sumNPoint_host / *nCluster_host.  D3_ERR_WORKSPACE when a bound is too small.
- * Replaces the pair bfs_cluster.cpp:28-112 is called through (functions/pointgroup_ops.py:203-231) without the return to
- * the caller between the phases (a Python caller re-acquires its interpreter lock there: idle device time). */
-int d3_bfs_cluster_run(const int *semantic_label, const int *ball_query_idxs, const int *start_len, int n, int threshold,
-                       void *ws, size_t ws_bytes, void *erec, size_t erec_bytes, long long nActive, int flags,
-                       int *cluster_idxs, long long cap_points, int *cluster_offsets, long long cap_clusters,
-                       int *sumNPoint_host, int *nCluster_host, void *stream);
-/* d3_bfs_cluster_run cut at its one host wait: `begin` enqueues everything (count kernels, the copy of their scalars + an event,
- * the fill with its sizes read on the device) and returns a ticket; `end` waits for the event, finishes the rare cases and
- * returns the sizes (the ticket is consumed whatever it returns).  One host thread keeps several clusterings in flight on
- * different streams: begin, begin, end, end.  The buffers handed to `begin` must stay alive until `end`. */
+/* `begin` enqueues everything on `stream` -- the first pair of sweeps with the sizes behind them, the copy of the counts to
+ * the host and an event, then the whole fill with its sizes read on the device (upper-bound grids: the speculative fill) --
+ * and returns without waiting.  `end` waits for the event, not for the stream, returns the sizes, and finishes the rare
+ * cases: more than 2048 kept clusters, a cluster beyond the LDS bitmap, more sweeps (the fill then runs again over the
+ * speculative one).  One host thread keeps several clusterings in flight on different streams: begin, begin, end, end.
+ * Without the speculative form (D3_CL_SPEC=0, cap_points < n) `begin` waits for the counts itself and `end` only hands the
+ * sizes over.
+ * Contract: `begin` returns 0 and a ticket, or a non-zero status and *ticket == NULL with nothing left allocated -- `end`
+ * is then not called.  A ticket is consumed by exactly one `end`, whatever that returns; the buffers handed to `begin`
+ * must stay alive until then. */
 int d3_bfs_cluster_begin(const int *semantic_label, const int *ball_query_idxs, const int *start_len, int n, int threshold,
                          void *ws, size_t ws_bytes, void *erec, size_t erec_bytes, long long nActive, int flags,
                          int *cluster_idxs, long long cap_points, int *cluster_offsets, long long cap_clusters,
                          void **ticket, void *stream);
 int d3_bfs_cluster_end(void *ticket, int *sumNPoint_host, int *nCluster_host);
+/* `begin` + `end` as one call; both sizes are 0 when it fails.  Replaces the pair bfs_cluster.cpp:28-112 is called through
+ * (functions/pointgroup_ops.py:203-231) without a return to the caller between the phases (a Python caller re-acquires
+ * its interpreter lock there: idle device time). */
+int d3_bfs_cluster_run(const int *semantic_label, const int *ball_query_idxs, const int *start_len, int n, int threshold,
+                       void *ws, size_t ws_bytes, void *erec, size_t erec_bytes, long long nActive, int flags,
+                       int *cluster_idxs, long long cap_points, int *cluster_offsets, long long cap_clusters,
+                       int *sumNPoint_host, int *nCluster_host, void *stream);
 
 /* ---- sparse 3-D convolution (MinkowskiEngine subset) ---------------------------------- */
 /* Coordinates are (M,4) int32 rows [batch, x, y, z] (ME.SparseTensor(coordinates=...),

@@ -27,6 +27,9 @@ def test_every_declared_symbol_is_exported(built_lib):
 def test_binding_table_matches_header(built_lib):
     from d3net_amd import _lib
     assert set(_lib.SIGNATURES) == _declared()
+    # the clustering's entry points: the two size queries, the one-call form and its two halves -- no earlier generation beside them
+    assert {n for n in _declared() if n.startswith("d3_bfs_cluster_")} == \
+        {"d3_bfs_cluster_" + s for s in ("ws_bytes", "erec_bytes", "run", "begin", "end")}
     l = _lib.lib()
     assert l.d3_arch() == b"gfx950"
     assert l.d3_version() >= 100
@@ -90,6 +93,18 @@ def test_workspace_layouts_are_written_once():
     assert not bad, bad
     assert len(decl.findall(open(os.path.join(csrc, "hgemm.hip")).read())) == 3
     assert len(decl.findall(open(os.path.join(csrc, "common.h")).read())) == 3
+
+
+def test_clustering_host_side_is_written_once():
+    """csrc/cluster.hip: ONE loop waits for the stream between count iterations and ONE place launches the generic level loop for the
+    clusters beyond the record form's LDS bitmap -- the blocking path and `end` share both; the 64-bit pair sort, which lost its
+    caller, is gone"""
+    csrc = os.path.join(ROOT, "d3net_amd", "csrc")
+    t = open(os.path.join(csrc, "cluster.hip")).read()
+    assert len(re.findall(r"cl_bfs_kernel\s*<<<[^;]*B2_MAXSIZE\s*\)\s*;", t)) == 1
+    assert t.count("cl_bfs_kernel<<<") == 1 and t.count("hipStreamSynchronize") == 1
+    bad = [f for f in sorted(os.listdir(csrc)) if "d3_sort_pairs_u64" in open(os.path.join(csrc, f), errors="ignore").read()]
+    assert not bad, bad
 
 
 def test_workspace_sizes_are_pinned(built_lib):

@@ -508,6 +508,17 @@ def test_bfs_cluster_begin_end_two_in_flight(dev, spec):
         e = torch.zeros(0, dtype=torch.int32, device=dev)
         ci, co = P.bfs_cluster_end(P.bfs_cluster_begin(e, e, torch.zeros((0, 2), dtype=torch.int32, device=dev), 10, True))
         assert N(co).tolist() == [0] and ci.shape[0] == 0
+        # a workspace one byte short: D3_ERR_WORKSPACE and no ticket -- nothing is left allocated, no `end` is owed
+        import ctypes as C
+        i1, s1 = P.ballquery_batch_p(x1, bid, bod, 0.03, 50)
+        ws = torch.empty(L.d3_bfs_cluster_ws_bytes(n) - 1, dtype=torch.uint8, device=dev)
+        rec = torch.empty(L.d3_bfs_cluster_erec_bytes(i1.numel()), dtype=torch.uint8, device=dev)
+        ci = torch.empty((n, 2), dtype=torch.int32, device=dev)
+        co = torch.empty(n // 15 + 2, dtype=torch.int32, device=dev)
+        tk = C.c_void_p(1)
+        rc = L.d3_bfs_cluster_begin(P._ptr(semd), P._ptr(i1), P._ptr(s1), n, 15, P._ptr(ws), ws.numel(), P._ptr(rec), rec.numel(), i1.numel(), 1,
+                                    P._ptr(ci), n, P._ptr(co), n // 15 + 1, C.byref(tk), P._stream())
+        assert rc == -1 and not tk.value, (spec, rc, tk.value)
     finally:
         L.d3_tuning_set(b"D3_CL_SPEC", 1)
 
@@ -541,6 +552,51 @@ def test_bfs_replay_agrees_with_the_oracle_on_wide_frontiers_and_long_lists(dev)
         ci, co = P.bfs_cluster(T(sem, dev), T(idx, dev), T(sl, dev), 50, asc)
         assert np.array_equal(N(co), rco), asc
         assert np.array_equal(N(ci), rci), (asc, int((N(ci) != rci).any(1).argmax()))
+
+
+_BIG_SHEET = {}
+
+
+def _big_sheet(dev):
+    """the input of the test below and the oracle's clusters on it, computed once for both of its cases"""
+    if not _BIG_SHEET:
+        from d3net_amd import pointgroup_ops as P
+        rng = np.random.default_rng(87)
+        g = np.stack(np.meshgrid(np.arange(513), np.arange(513), indexing="ij"), -1).reshape(-1, 2).astype(np.float32) * 0.02
+        sheet = np.concatenate([g, np.zeros((len(g), 1), np.float32)], 1)
+        rod = np.stack([np.arange(40) * 0.02, np.full(40, 20.0), np.zeros(40)], 1).astype(np.float32)
+        tri = (np.array([[3.0, 30.0, 0.0], [6.0, 40.0, 0.0]], np.float32)[:, None, :] + rng.normal(0, 0.004, (2, 3, 3)).astype(np.float32)).reshape(-1, 3)
+        xyz = np.concatenate([sheet, rod, tri]).astype(np.float32)
+        xyz = xyz[rng.permutation(len(xyz))]
+        n = len(xyz)
+        sem = np.ones(n, np.int32)
+        bi = np.zeros(n, np.int32); bo = np.array([0, n], np.int32)
+        idx, sl = P.ballquery_batch_p(T(xyz, dev), T(bi, dev), T(bo, dev), 0.03, 50)
+        idx, sl = N(idx), N(sl)
+        assert sl[:, 1].max() == 9 and idx.size > 2_300_000
+        rci, rco = o.bfs_cluster(sem, idx, sl, 20)
+        _BIG_SHEET.update(sem=sem, idx=idx, sl=sl, rci=rci, rco=rco)
+    return _BIG_SHEET
+
+
+@pytest.mark.parametrize("spec", [1, 0])
+def test_bfs_cluster_cluster_beyond_the_lds_bitmap(dev, spec):
+    """A component of more than 262,144 points does not fit the record-form replay's LDS bitmap and is written by the generic level
+    loop (cl_bfs_kernel), launched by `end` behind the speculative fill (D3_CL_SPEC=1) or by the fill with the counts known on the
+    host (D3_CL_SPEC=0): a 513 x 513 sheet in shuffled order (263,169 points, 9 list entries per interior point), next to a 40-point
+    rod that the record form replays and two triples below the threshold."""
+    from d3net_amd import pointgroup_ops as P, _lib
+    d = _big_sheet(dev)
+    sizes = np.diff(d["rco"])
+    assert 263169 in sizes and 40 in sizes and len(sizes) == 2
+    L = _lib.lib()
+    try:
+        assert L.d3_tuning_set(b"D3_CL_SPEC", spec) == 0
+        ci, co = P.bfs_cluster(T(d["sem"], dev), T(d["idx"], dev), T(d["sl"], dev), 20, True)
+        assert np.array_equal(N(co), d["rco"]), spec
+        assert np.array_equal(N(ci), d["rci"]), (spec, int((N(ci) != d["rci"]).any(1).argmax()))
+    finally:
+        L.d3_tuning_set(b"D3_CL_SPEC", 1)
 
 
 def test_bfs_cluster_no_clusters(dev):
