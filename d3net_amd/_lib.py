@@ -159,6 +159,9 @@ SIGNATURES = {
     "d3_dense_caption_assign": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]),
     "d3_det_match": (i32, [vp, vp, vp, vp, f64, vp, vp, vp, i32, i32, i32, i32, C.POINTER(f64), i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "d3_det_ap": (i32, [vp, vp, vp, i32, i64, i32, i32, vp, vp]),
+    "d3_caption_collect": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i64, vp, vp, vp,
+                                 vp, vp, vp, vp]),
+    "d3_caption_stats": (i32, [vp, i32, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp]),
     "d3_scene_limits": (i32, [pi, pi, pi]),
     "d3_scene_transform": (i32, [vp, i32, vp, f64, i32, vp, vp, vp]),
     "d3_scene_reduce": (i32, [vp, vp, i32, vp, vp]),

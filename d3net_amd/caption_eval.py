@@ -9,9 +9,16 @@ cost matrix is never stored and nothing is read back.  On the host (the referenc
 (B, K1, K2) generalised-IoU cost matrix is computed batched on whatever device the boxes live on (the reference loops over the
 batch in python to mask the padded GT columns), copied to the host and handed to scipy scene by scene.  `device_assign=None`
 takes the device form when the boxes are on a GPU and K, G <= 256 (DESIGN.md section 3.6 has the measurement behind that
-default).  CIDEr is d3net_amd.cider (bit-identical to lib/capeval/cider).  BLEU / ROUGE / METEOR are not restated (METEOR
-needs a Java runtime).  Pinned to golden vectors produced by the reference's own functions
+default).  CIDEr is d3net_amd.cider (bit-identical to lib/capeval/cider), BLEU-1..4 and ROUGE-L are d3net_amd.caption_metrics;
+METEOR is not restated (it needs a Java runtime).  Pinned to golden vectors produced by the reference's own functions
 (tests/golden/gen_caption_eval_golden.py).
+
+The whole validation also runs on the device (`CaptionEvaluator`): per batch the assignment and
+csrc/caption_eval.hip's d3_caption_collect keep the winning caption (token ids) and IoU of every described object on the GPU under
+the host's merge rule, and at the end of the epoch d3_cider_scores and d3_caption_stats score them against `EvalCorpus`, the
+token-id twin of `prepare_corpus`.  BLEU and ROUGE need only integers from the sentences (clipped n-gram counts, lengths, LCS
+lengths), so they equal the host's bit for bit; CIDEr is within the 1e-12 the device scorer is held to.  The host functions
+below stay as they are: they are the reference form, and they keep the box lists the visualisers read.
 
 Quirk kept on purpose: the reference's "footprint" rectangle of a box is read from corner columns (x, z) of corners 2 and 0
 and the height from the z of corners 0 and 4 -- conventions inherited from a y-up code base -- so for this repo's z-up corner
@@ -224,3 +231,252 @@ def eval_caption_epoch(candidates, raw_data, max_len=30, min_iou=0.5):
     cider = cider_scores(refs, cands)
     rouge = rouge_l_scores(refs, cands)
     return bleu, cider, rouge, (0.0, np.zeros(len(keys)))
+
+
+# ---------------------------------------------------------------------------------------------------- the device form
+EVAL_MAX_TOKENS = 64             # tokens per sentence of csrc/caption_eval.hip, sos and eos included
+EVAL_MAX_OBJECT_ID = 4095        # columns of the per-scene slot table
+EVAL_MAX_SLOTS_PER_BATCH = 1 << 20
+
+
+class EvalCorpus:
+    """`prepare_corpus` as token ids for csrc/caption_eval.hip and csrc/cider.hip, built once per split: one int32 row
+    [sos] + token[:max_len] + [eos] per description, ids canonical as in captioning_loss.CiderCorpus (the lower id of two that spell
+    one word, corpus-private ids >= V for words outside the vocabulary, so string equality == id equality).  Keys "scene|object" are
+    numbered as slots in order of first appearance; the rows of a slot are contiguous, in order of appearance.  Data beyond the
+    kernels' fixed sizes raises ValueError (the host path, eval_caption_step + eval_caption_epoch, takes it)."""
+    MAX_SET_NGRAMS, MAX_ID = 2048, 65534
+
+    def __init__(self, raw_data, idx2word, special_tokens, max_len=30, device="cuda"):
+        from .captioning_loss import canonical_ids
+        if special_tokens["bos_token"] != "sos" or special_tokens["eos_token"] != "eos":
+            raise ValueError("EvalCorpus: prepare_corpus writes the literal words 'sos' / 'eos'; the vocabulary's are %r / %r"
+                             % (special_tokens["bos_token"], special_tokens["eos_token"]))
+        canon, V = canonical_ids(idx2word)
+        one_word = lambda w: isinstance(w, str) and w.split() == [w]          # then split(), split(" ") and id equality agree
+        for w in canon:
+            if not one_word(w):
+                raise ValueError("EvalCorpus: vocabulary word %r is empty or contains whitespace" % (w,))
+        if "sos" not in canon or "eos" not in canon:
+            raise ValueError("EvalCorpus: the vocabulary has no 'sos' / 'eos'")
+        extra, per_slot, self.keys, self.scene_index, slot_scene, slot_obj = {}, [], [], {}, [], []
+        slot_of_key = {}
+        for d in raw_data:
+            sid, oid = d["scene_id"], d["object_id"]
+            key = "{}|{}".format(sid, oid)
+            slot = slot_of_key.get(key)
+            if slot is None:
+                try:
+                    o = int(oid)
+                except (TypeError, ValueError):
+                    raise ValueError("EvalCorpus: object id %r of %s is not an integer" % (oid, sid))
+                if not 0 <= o <= EVAL_MAX_OBJECT_ID:
+                    raise ValueError("EvalCorpus: object id %d of %s outside [0, %d]" % (o, sid, EVAL_MAX_OBJECT_ID))
+                slot = slot_of_key[key] = len(self.keys)
+                self.keys.append(key); per_slot.append([])
+                slot_scene.append(self.scene_index.setdefault(sid, len(self.scene_index)))
+                slot_obj.append(o if str(o) == str(oid) else -1)       # the candidates' keys are written with str(int)
+            words = list(d["token"][:max_len])
+            if len(words) + 2 > EVAL_MAX_TOKENS:
+                raise ValueError("EvalCorpus: a description of %s has %d tokens with sos and eos, the kernels hold %d"
+                                 % (key, len(words) + 2, EVAL_MAX_TOKENS))
+            for w in words:
+                if not one_word(w):
+                    raise ValueError("EvalCorpus: word %r of %s is empty or contains whitespace" % (w, key))
+            per_slot[slot].append([canon[w] if w in canon else extra.setdefault(w, V + len(extra)) for w in ["sos"] + words + ["eos"]])
+        if not self.keys:
+            raise ValueError("EvalCorpus: no descriptions")
+        if V + len(extra) > self.MAX_ID:
+            raise ValueError("EvalCorpus: %d distinct words, ids end at %d" % (V + len(extra), self.MAX_ID))
+        rows, self.row_off = [], [0]
+        for key, rs in zip(self.keys, per_slot):
+            if 4 * sum(len(r) for r in rs) > self.MAX_SET_NGRAMS:
+                raise ValueError("EvalCorpus: the references of %s hold %d n-gram positions, the per-set table %d"
+                                 % (key, 4 * sum(len(r) for r in rs), self.MAX_SET_NGRAMS))
+            rows.extend(rs); self.row_off.append(len(rows))
+        self.row_len = [len(r) for r in rows]
+        self.ldt = EVAL_MAX_TOKENS
+        tok = np.zeros((len(rows), self.ldt), np.int32)
+        for i, r in enumerate(rows):
+            tok[i, :len(r)] = r
+        self.V, self.sos, self.eos, self.device = V, canon["sos"], canon["eos"], torch.device(device)
+        self.n_scenes, self.n_obj, self.slot_scene = len(self.scene_index), max(max(slot_obj), 0) + 1, slot_scene
+        table = np.full((self.n_scenes, self.n_obj), -1, np.int32)
+        for s, (sc, o) in enumerate(zip(slot_scene, slot_obj)):
+            if o >= 0:
+                table[sc, o] = s
+        lut = np.full(V, -1, np.int32)
+        for i, w in idx2word.items():
+            lut[int(i)] = canon[w]
+        self.words = {i: w for w, i in list(canon.items()) + list(extra.items())}          # canonical id -> word
+        self.tokens = torch.from_numpy(tok).to(self.device)
+        self.lens = torch.tensor(self.row_len, dtype=torch.int32, device=self.device)
+        self.slot_of = torch.from_numpy(table).to(self.device)
+        self.lut = torch.from_numpy(lut).to(self.device)
+
+    def decode(self, ids):
+        return " ".join(self.words[int(i)] for i in ids)
+
+
+_CAP_KEYS = ("lang_cap", "proposal_bbox_batched", "gt_bbox", "gt_bbox_object_id", "gt_bbox_label", "scene_id")
+
+
+class CaptionEvaluator:
+    """eval_caption_step + the candidate merge of validation_epoch_end + eval_caption_epoch on the device: `add_batch` runs the
+    Hungarian assignment (csrc/assign.hip) and d3_caption_collect, which keeps the epoch's winning caption and IoU per corpus slot
+    on the GPU (state sized by the corpus, no read-back); `compute` reads the seen-scene flags, runs d3_cider_scores and
+    d3_caption_stats over the entries and reads one block back -> what eval_caption_epoch returns, BLEU and ROUGE formed by
+    caption_metrics' floating-point halves from the kernel's integers."""
+
+    def __init__(self, raw_data, vocabulary, max_len=30, min_iou=0.5, device="cuda", strategy="giou"):
+        if strategy not in ("giou", "center"):
+            raise ValueError("invalid strategy.")
+        self.corpus = EvalCorpus(raw_data, vocabulary["idx2word"], vocabulary["special_tokens"], max_len, device)
+        self.min_iou, self.strategy, self.keys = float(min_iou), strategy, None
+        self.reset()
+
+    def reset(self):
+        c, dev = self.corpus, self.corpus.device
+        S = len(c.keys)
+        self._owner = torch.full((S,), -1, dtype=torch.int64, device=dev)             # (uint64 all ones: unowned)
+        self._cap = torch.zeros((S, EVAL_MAX_TOKENS), dtype=torch.int32, device=dev)
+        self._cap_len = torch.zeros(S, dtype=torch.int32, device=dev)
+        self._iou = torch.zeros(S, dtype=torch.float32, device=dev)
+        self._seen = torch.zeros(c.n_scenes, dtype=torch.int32, device=dev)
+        self._status = torch.zeros(1, dtype=torch.int32, device=dev)
+        self._seq, self._entries = 0, {}
+
+    def _checked(self, data_dict):
+        missing = [k for k in _CAP_KEYS if k not in data_dict]
+        if missing:
+            raise ValueError("CaptionEvaluator.add_batch: missing %s" % missing)
+        caps, pb, gb, ids, mask, scenes = (data_dict[k] for k in _CAP_KEYS)
+        dev = self.corpus.device
+        for k in _CAP_KEYS[:5]:
+            t = data_dict[k]
+            if not torch.is_tensor(t) or not t.is_cuda or t.device != dev:
+                raise ValueError("CaptionEvaluator.add_batch: %s must be a tensor on the corpus's GPU (%s)" % (k, dev))
+        if pb.dim() != 4 or tuple(pb.shape[2:]) != (8, 3) or gb.dim() != 4 or tuple(gb.shape[2:]) != (8, 3) or gb.shape[0] != pb.shape[0]:
+            raise ValueError("CaptionEvaluator.add_batch: corners (B,K,8,3) and (B,G,8,3) expected")
+        B, K, G = pb.shape[0], pb.shape[1], gb.shape[1]
+        if B < 1 or K < 1 or G < 1 or K > DEVICE_ASSIGN_MAX or G > DEVICE_ASSIGN_MAX:
+            raise ValueError("CaptionEvaluator.add_batch: B >= 1, 1 <= K, G <= %d (got B %d, K %d, G %d)" % (DEVICE_ASSIGN_MAX, B, K, G))
+        if B * G > EVAL_MAX_SLOTS_PER_BATCH:
+            raise ValueError("CaptionEvaluator.add_batch: B * G = %d exceeds %d" % (B * G, EVAL_MAX_SLOTS_PER_BATCH))
+        if caps.dim() != 3 or tuple(caps.shape[:2]) != (B, K):
+            raise ValueError("CaptionEvaluator.add_batch: lang_cap must be (%d, %d, T)" % (B, K))
+        T = caps.shape[2]
+        if T > EVAL_MAX_TOKENS - 2:
+            raise ValueError("CaptionEvaluator.add_batch: captions of T = %d tokens, the kernel holds %d" % (T, EVAL_MAX_TOKENS - 2))
+        for k, t in ((_CAP_KEYS[3], ids), (_CAP_KEYS[4], mask)):
+            if tuple(t.shape) != (B, G):
+                raise ValueError("CaptionEvaluator.add_batch: %s must be (%d, %d)" % (k, B, G))
+        ints = (torch.int32, torch.int64)
+        for k, t, ok in ((_CAP_KEYS[0], caps, (torch.int64,)), (_CAP_KEYS[1], pb, (torch.float32,)), (_CAP_KEYS[2], gb, (torch.float32,)),
+                         (_CAP_KEYS[3], ids, ints), (_CAP_KEYS[4], mask, (torch.float32, torch.bool, torch.uint8) + ints)):
+            if t.dtype not in ok:
+                raise ValueError("CaptionEvaluator.add_batch: %s has dtype %s, expected one of %s" % (k, t.dtype, ok))
+        if len(scenes) != B:
+            raise ValueError("CaptionEvaluator.add_batch: scene_id must name the %d scenes" % B)
+        return caps, pb, gb, ids, mask, scenes, B, K, G, T
+
+    def add_batch(self, data_dict):
+        """the six keys eval_caption_step reads, tensors on the GPU; returns nothing and reads nothing back"""
+        import ctypes as C
+        from . import _lib
+        caps, pb, gb, ids, mask, scenes, B, K, G, T = self._checked(data_dict)
+        c, dev = self.corpus, self.corpus.device
+        nactual = mask.sum(1).long()
+        pb, gb = pb.detach().contiguous(), gb.detach().contiguous()
+        per_gt, astatus, _ = _assign_launch(pb, gb, nactual, self.strategy, False)
+        scene_idx = torch.tensor([c.scene_index.get(s, -1) for s in scenes], dtype=torch.int32).to(dev, non_blocking=True)
+        m32, ids64, caps = (mask != 0).to(torch.int32).contiguous(), ids.long().contiguous(), caps.detach().contiguous()
+        p = lambda t: C.c_void_p(t.data_ptr())
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().d3_caption_collect(p(per_gt), p(pb), p(gb), p(m32), p(ids64), p(caps) if T else None, p(c.lut), p(scene_idx),
+                                                     p(c.slot_of), p(astatus), B, K, G, T, c.V, c.n_scenes, c.n_obj, len(c.keys), c.sos,
+                                                     c.eos, self._seq, p(self._owner), p(self._cap), p(self._cap_len), p(self._iou),
+                                                     p(self._seen), p(self._status), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+                       "caption_collect")
+        self._seq += 1
+
+    def _entry_tables(self, seen):
+        """the entries of a set of seen scenes: slots in slot order (prepare_corpus's keys) and the d3_cider_scores batch description"""
+        ent = self._entries.get(seen)
+        if ent is None:
+            c = self.corpus
+            slots = [s for s in range(len(c.keys)) if seen[c.slot_scene[s]]]
+            slot_row, u_off = [], [0]
+            for s in slots:
+                slot_row.extend(range(c.row_off[s], c.row_off[s + 1])); u_off.append(len(slot_row))
+            E, SR = len(slots), len(slot_row)
+            ngrams = 4 * sum(c.row_len[r] for r in slot_row)
+            hash_slots = 1024
+            while hash_slots < 4 * ngrams:
+                hash_slots *= 2
+            meta = torch.tensor(slots + slot_row + u_off + [1] * E + list(range(E)), dtype=torch.int32).to(c.device)
+            o = np.cumsum([0, E, SR, E + 1, E, E])
+            self._entries = {seen: (slots, slot_row, u_off, hash_slots) + tuple(meta[o[i]:o[i + 1]] for i in range(5))}
+            ent = self._entries[seen]
+        return ent
+
+    def compute(self, min_iou=None):
+        """-> (bleu, cider, rouge, meteor) as eval_caption_epoch returns them for the epoch's merged candidates; sets self.keys"""
+        import ctypes as C
+        from . import _lib
+        from .caption_metrics import bleu_from_counts, rouge_from_lcs
+        min_iou = self.min_iou if min_iou is None else float(min_iou)
+        c, dev = self.corpus, self.corpus.device
+        seen = tuple(bool(x) for x in self._seen.cpu().tolist())                    # read-back 1: decides the entry set
+        slots, slot_row, u_off, hash_slots, d_slots, d_rows, d_uoff, d_mult, d_ent = self._entry_tables(seen)
+        self.keys = [c.keys[s] for s in slots]
+        E, SR = len(slots), len(slot_row)
+        if E == 0:
+            self._raise_on(int(self._status.cpu()[0]))
+            z = (0.0, np.zeros(0))
+            return ([0.0] * 4, [[] for _ in range(4)]), z, z, z
+        sel = d_slots.long()
+        keep = (self._owner[sel] != -1) & (self._iou[sel].double() >= min_iou)      # a NaN IoU compares false, as on the host
+        empty = torch.zeros(EVAL_MAX_TOKENS, dtype=torch.int32, device=dev)
+        empty[0], empty[1] = c.sos, c.eos
+        cand = torch.where(keep[:, None], self._cap[sel], empty[None]).contiguous()
+        clen = torch.where(keep, self._cap_len[sel], torch.full_like(self._cap_len[sel], 2)).contiguous()
+        L = _lib.lib()
+        ws = torch.empty(L.d3_cider_ws_bytes(SR, E, hash_slots), dtype=torch.uint8, device=dev)
+        scores = torch.empty(E, dtype=torch.float64, device=dev)
+        flag = torch.empty(1, dtype=torch.int32, device=dev)
+        stats = torch.empty((E, 6), dtype=torch.int32, device=dev)
+        lcs = torch.empty(SR, dtype=torch.int32, device=dev)
+        p = lambda t: C.c_void_p(t.data_ptr())
+        with torch.cuda.device(dev):
+            stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            _lib.check(L.d3_cider_scores(p(c.tokens), c.ldt, p(c.lens), p(d_rows), p(d_uoff), p(d_mult), p(d_ent), E, SR, p(cand),
+                                         EVAL_MAX_TOKENS, p(clen), E, c.eos, 6.0, hash_slots, p(scores), p(flag), p(ws), ws.numel(), stream),
+                       "cider_scores")
+            _lib.check(L.d3_caption_stats(p(cand), EVAL_MAX_TOKENS, p(clen), p(c.tokens), c.ldt, p(c.lens), p(d_rows), p(d_uoff), E, p(stats),
+                                          p(lcs), stream), "caption_stats")
+        host = torch.cat([stats.view(-1).double(), lcs.double(), scores, flag.double(), self._status.double()]).cpu().numpy()   # read-back 2
+        if int(host[-2]):
+            raise _lib.D3Error("CaptionEvaluator: a CIDEr hash table overflowed")
+        self._raise_on(int(host[-1]))
+        counts = host[:6 * E].astype(np.int64).reshape(E, 6).tolist()
+        lcs_h = host[6 * E:6 * E + SR].astype(np.int64).tolist()
+        cider = host[6 * E + SR:6 * E + SR + E].copy()
+        bleu = bleu_from_counts(counts, 4)
+        rouge = rouge_from_lcs([(counts[e][4], [c.row_len[r] for r in slot_row[u_off[e]:u_off[e + 1]]], lcs_h[u_off[e]:u_off[e + 1]])
+                                for e in range(E)])
+        return bleu, (float(np.mean(cider)), cider), rouge, (0.0, np.zeros(E))
+
+    @staticmethod
+    def _raise_on(status):
+        from . import _lib
+        if status & 1:
+            raise _lib.D3Error("CaptionEvaluator: a matched caption holds a token outside the vocabulary")
+        if status & 6:
+            raise ValueError(_ASSIGN_ERRORS[1 if status & 2 else 2])
+
+    def candidates(self):
+        """the debugging / parity view: the state read back -> {key: {"caption": str, "iou": float}} for the owned slots"""
+        c = self.corpus
+        owner, cap, n, iou = (t.cpu().numpy() for t in (self._owner, self._cap, self._cap_len, self._iou))
+        return {c.keys[s]: {"caption": c.decode(cap[s, :n[s]]), "iou": float(iou[s])} for s in range(len(c.keys)) if owner[s] != -1}

@@ -2,7 +2,9 @@
 lib/capeval/bleu/bleu_scorer.py:23-264 with the "closest" reference length that lib/capeval/bleu/bleu.py:39 selects,
 lib/capeval/rouge/rouge.py:13-100; called from lib/captioning/eval_helper.py:289-291).  Host-side string work as in the
 reference; the n-gram counter is shared with d3net_amd.cider.  Same accumulation order, so the float64 results equal the
-reference's.  METEOR (a Java subprocess in the reference) is not provided.
+reference's.  METEOR (a Java subprocess in the reference) is not provided.  Both scorers are split into a counting half
+(integers: `bleu_counts`, `rouge_lcs`) and a floating-point half (`bleu_from_counts`, `rouge_from_lcs`): the device evaluation
+(caption_eval.CaptionEvaluator) feeds the second half with the integers of csrc/caption_eval.hip, so its scores equal these.
 """
 import math
 
@@ -13,12 +15,11 @@ from .cider import ngram_counts
 _SMALL, _TINY = 1e-9, 1e-15
 
 
-def bleu_scores(references, candidates, n=4):
-    """references: list of lists of sentences, candidates: list of sentences ->
-    ([corpus BLEU-1..n], [per-entry BLEU-k lists]) == Bleu(n).compute_score(gts, res)"""
+def bleu_counts(references, candidates, n=4):
+    """the counting half of bleu_scores: per entry [clipped matches of order 1..n, candidate length, "closest" reference
+    length] as python ints (bleu_scorer.py cook_refs / cook_test)"""
     assert len(references) == len(candidates)
-    per = [[] for _ in range(n)]
-    tot_guess, tot_correct, tot_test, tot_ref = [0] * n, [0] * n, 0, 0
+    counts = []
     for refs, cand in zip(references, candidates):
         maxc, reflens = {}, []
         for r in refs:
@@ -28,10 +29,21 @@ def bleu_scores(references, candidates, n=4):
                     maxc[g] = c
         testlen = len(cand.split())
         reflen = min((abs(l - testlen), l) for l in reflens)[1]            # "closest"
-        guess = [max(0, testlen - k + 1) for k in range(1, n + 1)]
         correct = [0] * n
         for g, c in ngram_counts(cand, n).items():
             correct[len(g) - 1] += min(maxc.get(g, 0), c)
+        counts.append(correct + [testlen, reflen])
+    return counts
+
+
+def bleu_from_counts(counts, n=4):
+    """the floating-point half: counts as bleu_counts returns them (python ints; csrc/caption_eval.hip's d3_caption_stats rows)
+    -> ([corpus BLEU-1..n], [per-entry BLEU-k lists])"""
+    per = [[] for _ in range(n)]
+    tot_guess, tot_correct, tot_test, tot_ref = [0] * n, [0] * n, 0, 0
+    for row in counts:
+        correct, testlen, reflen = row[:n], row[n], row[n + 1]
+        guess = [max(0, testlen - k + 1) for k in range(1, n + 1)]
         tot_test += testlen; tot_ref += reflen
         b = 1.0
         for k in range(n):
@@ -52,6 +64,12 @@ def bleu_scores(references, candidates, n=4):
     return bleus, per
 
 
+def bleu_scores(references, candidates, n=4):
+    """references: list of lists of sentences, candidates: list of sentences ->
+    ([corpus BLEU-1..n], [per-entry BLEU-k lists]) == Bleu(n).compute_score(gts, res)"""
+    return bleu_from_counts(bleu_counts(references, candidates, n), n)
+
+
 def _lcs(a, b):
     """length of the longest common subsequence of two token lists (two-row dynamic programme)"""
     if len(a) < len(b):
@@ -65,18 +83,32 @@ def _lcs(a, b):
     return prev[len(b)]
 
 
-def rouge_l_scores(references, candidates, beta=1.2):
-    """-> (mean ROUGE-L, per-entry float64 array) == Rouge().compute_score(gts, res); tokens split on single spaces, as
-    the reference does (rouge.py:58,62)"""
-    scores = []
+def rouge_lcs(references, candidates):
+    """the counting half of rouge_l_scores: per entry (candidate length, [reference lengths], [LCS lengths]) as python ints;
+    tokens split on single spaces, as the reference does (rouge.py:58,62)"""
+    out = []
     for refs, cand in zip(references, candidates):
         tc = cand.split(" ")
+        trs = [r.split(" ") for r in refs]
+        out.append((len(tc), [len(tr) for tr in trs], [_lcs(tr, tc) for tr in trs]))
+    return out
+
+
+def rouge_from_lcs(entries, beta=1.2):
+    """the floating-point half: entries as rouge_lcs returns them (python ints; the LCS lengths of csrc/caption_eval.hip's
+    d3_caption_stats) -> (mean ROUGE-L, per-entry float64 array)"""
+    scores = []
+    for clen, rlens, lcs in entries:
         prec, rec = [], []
-        for r in refs:
-            tr = r.split(" ")
-            l = _lcs(tr, tc)
-            prec.append(l / float(len(tc))); rec.append(l / float(len(tr)))
+        for l, rl in zip(lcs, rlens):
+            prec.append(l / float(clen)); rec.append(l / float(rl))
         p, r = max(prec), max(rec)
         scores.append(((1 + beta ** 2) * p * r) / float(r + beta ** 2 * p) if p != 0 and r != 0 else 0.0)
     scores = np.array(scores)
     return float(np.mean(scores)), scores
+
+
+def rouge_l_scores(references, candidates, beta=1.2):
+    """-> (mean ROUGE-L, per-entry float64 array) == Rouge().compute_score(gts, res); tokens split on single spaces, as
+    the reference does (rouge.py:58,62)"""
+    return rouge_from_lcs(rouge_lcs(references, candidates), beta)

@@ -7,6 +7,14 @@ import torch.nn.functional as F
 from .cider import cider_scores
 
 
+def canonical_ids(idx2word):
+    """idx2word -> ({word: its lowest id}, V): two ids spelling one word are one word to the string scorers"""
+    canon = {}
+    for i, w in idx2word.items():
+        canon[w] = min(int(i), canon.get(w, int(i)))
+    return canon, max(int(i) for i in idx2word) + 1
+
+
 class CiderCorpus:
     """The annotation store (`organized[scene_id][object_id]` -> tokenised descriptions) as device tensors for
     csrc/cider.hip: one row of token ids per reference sentence (+ "eos", as the reference joins them, loss_helper.py:60),
@@ -15,10 +23,7 @@ class CiderCorpus:
     MAX_TOKENS, MAX_SET_NGRAMS, MAX_ID = 160, 2048, 65534
 
     def __init__(self, organized, idx2word, device):
-        canon = {}
-        for i, w in idx2word.items():
-            canon[w] = min(int(i), canon.get(w, int(i)))
-        V = max(int(i) for i in idx2word) + 1
+        canon, V = canonical_ids(idx2word)
         extra, rows, self.sets = {}, [], {}
         for sid, objs in organized.items():
             for oid, descs in objs.items():

@@ -272,6 +272,31 @@ class PipelineNet(nn.Module):
             raise NotImplementedError("evaluate_detection needs the detector (model.no_detection is set)")
         return self.detector.evaluate_detection(batches, evaluator)
 
+    def evaluate_captioning(self, batches, evaluator=None):
+        """the captioning keys of validation_epoch_end's log over `batches`, scored on the device: per batch the detector, the
+        speaker's evaluation decode and CaptionEvaluator.add_batch (no read-back), one compute at the end (caption_eval.py;
+        lib/captioning/eval_helper.py:248-340).  Modes 1 and 3."""
+        from .caption_eval import CaptionEvaluator
+        if self.mode not in (1, 3):
+            raise NotImplementedError("evaluate_captioning needs the detector and the speaker (modes 1 and 3), this is mode %d" % self.mode)
+        ev = evaluator
+        if ev is None:
+            ev = CaptionEvaluator(self.val_raw_data or [], self.vocabulary, max_len=self.cfg.eval.max_des_len + 2,
+                                  min_iou=self.cfg.eval.min_iou_threshold, device=next(self.parameters()).device)
+        was_training = self.training
+        self.eval()
+        try:
+            with torch.no_grad():
+                for batch in batches:
+                    self._lazy_proposals = False
+                    d = self.speaker(self._detect(batch), use_tf=False, use_rl=False, is_eval=True, beam_opt=self.beam_opt)
+                    ev.add_batch(d)
+        finally:
+            self.train(was_training)
+        bleu, cider, rouge, meteor = ev.compute()
+        return {"bleu-1": bleu[0][0], "bleu-2": bleu[0][1], "bleu-3": bleu[0][2], "bleu-4": bleu[0][3], "cider": cider[0],
+                "meteor": meteor[0], "rouge": rouge[0]}
+
     def forward(self, data_dict):
         """inference entry point (model/pipeline.py:894-925): detector -> speaker -> listener, whichever exist"""
         if not self.no_detection:

@@ -830,6 +830,35 @@ int d3_det_match(const float *pred_corners, const int *pred_cls, const float *sc
 int d3_det_ap(const int *tp_sorted, const int *seg_offsets, const int *gt_count, int S, long long N, int num_class, int T,
               double *table, void *stream);
 
+/* ---- captioning validation (csrc/caption_eval.hip, driven by d3net_amd.caption_eval.CaptionEvaluator) -----------------------
+ * d3_caption_collect: per validation batch, in place of the B x G loop of lib/captioning/eval_helper.py:102-307
+ *   (assign_dense_caption after its Hungarian step, and the `candidates.setdefault` merge of the epoch).  All pointers are device
+ *   memory.  per_gt (B,G) int32 as d3_dense_caption_assign leaves it; pred_boxes (B,K,8,3), gt_boxes (B,G,8,3) float32; gt_mask
+ *   (B,G) int32 (!= 0: a GT box); gt_obj_ids (B,G) int64; lang_cap (B,K,T) int64 token ids, T <= 62; lut (V) int32: the canonical
+ *   id of a vocabulary id, -1 where the vocabulary has none; scene_idx (B) int32 scene of the corpus, -1: none; slot_of
+ *   (n_scenes,n_obj) int32 corpus slot of (scene, object id), -1: none; assign_status: NULL or (B) int32, the assignment's status.
+ *   State, sized by the corpus (S slots): owner (S) uint64, all ones = unowned; cap (S,64) int32; cap_len (S) int32; iou (S)
+ *   float32; scene_seen (n_scenes) int32; *status int32.  A GT slot (b,g) with mask != 0 marks its scene seen and claims its
+ *   corpus slot with prio = batch_seq * 2^20 + (2^20 - 1 - (b*G + g)) by integer atomicMin: the first batch wins, within a batch
+ *   the last (b,g).  The winner writes iou = bbox.py:273-305 box3d_iou of (pred_boxes[b, per_gt[b,g]], gt_boxes[b,g]) in float32,
+ *   torch's operation order, and cap = [sos] + lut[tokens] up to and including the first eos (eos appended when absent), as
+ *   decode_caption builds it.  *status is OR-ed with 1 when a winner's caption holds a token outside the vocabulary before its
+ *   eos, 2 / 4 when assign_status holds a 1 / 2.  Two launches, nothing read back.
+ *   T > 62, B*G > 2^20 or batch_seq outside [0, 2^43): D3_ERR_RANGE before any launch.
+ * d3_caption_stats: the counting halves of lib/capeval/bleu/bleu_scorer.py (cook_refs, cook_test, "closest" reference length)
+ *   and lib/capeval/rouge/rouge.py (my_lcs), one workgroup per entry.  Entry e = candidate cand[e, :clen[e]] (E,ldc) int32
+ *   against the corpus rows slot_row[u_off[e] .. u_off[e+1]) of tokens (R,ldt) / lens (R) (the layout d3_cider_scores reads
+ *   with U = E); sentences are cut at 64 tokens, ids < 65535.  stats (E,6) int32 = clipped n-gram matches of order 1..4, the
+ *   candidate length, the closest reference length (the shorter on equal distance); lcs (SR) int32 = LCS length of the entry's
+ *   candidate with each of its rows, in slot_row order.  Integers only: the scores are formed on the host. */
+int d3_caption_collect(const int *per_gt, const float *pred_boxes, const float *gt_boxes, const int *gt_mask,
+                       const long long *gt_obj_ids, const long long *lang_cap, const int *lut, const int *scene_idx,
+                       const int *slot_of, const int *assign_status, int B, int K, int G, int T, int V, int n_scenes, int n_obj,
+                       int S, int sos, int eos, long long batch_seq, unsigned long long *owner, int *cap, int *cap_len,
+                       float *iou, int *scene_seen, int *status, void *stream);
+int d3_caption_stats(const int *cand, int ldc, const int *clen, const int *tokens, int ldt, const int *lens,
+                     const int *slot_row, const int *u_off, int E, int *stats, int *lcs, void *stream);
+
 /* ---- PointGroup scene preparation (csrc/scene_prep.hip, driven by d3net_amd/scene_prep.py) ----------------------------------
  * One scene of n points: xyz (n,3) float32, ids / sem (n) int32 (ids -1 = none).  Coordinates are fp64 (numpy's float32 @ float64
  * promotion) unless fp32 != 0 (the validation path, float32 throughout like the reference's `points.copy() * scale`).
