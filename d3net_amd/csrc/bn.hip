@@ -8,33 +8,36 @@
 
 #define BN_T 256
 
-// per-channel sum / sum of squares -> per-workgroup fp64 partials ws[block][2C] (no memset, no atomics,
-// deterministic); the finalize kernel adds the partials
+// per-channel sum / sum of squares of x - K, K = row 0 of the channel (a pivot near the data: E[x^2] - mean^2 from fp32
+// sums of the raw values keeps no digit of the variance once |mean| / std reaches ~1e3), accumulated in fp64 so that a row 0
+// far from the rest of its column (an outlier as pivot) costs nothing either -> per-workgroup fp64 partials ws[block][2C]
+// (no memset, no atomics, deterministic); the finalize kernel adds the partials and puts K back
 __global__ __launch_bounds__(BN_T) void bn_stats_kernel(const float *__restrict__ x, int M, int C, double *acc) {
-    __shared__ float s1[BN_T], s2[BN_T];
+    __shared__ double s1[BN_T], s2[BN_T];
     const int t = threadIdx.x;
     const int active = (BN_T / C) * C, rpp = active / C;
-    float a = 0.f, b = 0.f;
+    double a = 0., b = 0.;
     if (t < active) {
         const int c = t % C;
+        const double K = (double)x[c];
         for (long long r = (long long)blockIdx.x * rpp + t / C; r < M; r += (long long)gridDim.x * rpp) {
-            const float v = x[r * C + c];
-            a += v; b = fmaf(v, v, b);
+            const double v = (double)x[r * C + c] - K;
+            a += v; b = fma(v, v, b);
         }
     }
     s1[t] = a; s2[t] = b;
     __syncthreads();
     if (t < C) {
         double da = 0., db = 0.;
-        for (int k = t; k < active; k += C) { da += (double)s1[k]; db += (double)s2[k]; }
+        for (int k = t; k < active; k += C) { da += s1[k]; db += s2[k]; }
         acc[(size_t)blockIdx.x * 2 * C + t] = da;
         acc[(size_t)blockIdx.x * 2 * C + C + t] = db;
     }
 }
 // mean / biased variance + (optionally) the running-statistics update of nn.BatchNorm1d in training mode:
 // running = (1-momentum)*running + momentum*stat, with the UNBIASED variance (M/(M-1))
-__global__ void bn_finalize_kernel(const double *acc, int nblocks, int M, int C, float *mean, float *var,
-                                   float *running_mean, float *running_var, float momentum) {
+__global__ void bn_finalize_kernel(const float *__restrict__ x, const double *acc, int nblocks, int M, int C, float *mean,
+                                   float *var, float *running_mean, float *running_var, float momentum) {
     // one wave per channel: lanes stride over the workgroup partials, fp64 wave reduction (fixed order: deterministic)
     const int c = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6), lane = threadIdx.x & 63;
     if (c >= C) return;
@@ -42,9 +45,10 @@ __global__ void bn_finalize_kernel(const double *acc, int nblocks, int M, int C,
     for (int b = lane; b < nblocks; b += 64) { sa += acc[(size_t)b * 2 * C + c]; sb += acc[(size_t)b * 2 * C + C + c]; }
     for (int o = 32; o > 0; o >>= 1) { sa += __shfl_xor(sa, o); sb += __shfl_xor(sb, o); }
     if (lane != 0) return;
-    const double m = sa / (double)M;
-    double v = sb / (double)M - m * m;
+    const double ms = sa / (double)M;        // mean of x - K
+    double v = sb / (double)M - ms * ms;
     if (v < 0.) v = 0.;
+    const double m = (double)x[c] + ms;
     mean[c] = (float)m; var[c] = (float)v;  // biased variance (what the normalisation uses)
     if (running_mean) {
         running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * (float)m;
@@ -112,10 +116,10 @@ __global__ __launch_bounds__(BN_T) void bn_bwd_reduce_kernel(const float *__rest
                                                             const float *__restrict__ gamma,
                                                             const float *__restrict__ beta, int M, int C, float eps,
                                                             int relu, double *acc) {
-    __shared__ float s1[BN_T], s2[BN_T];
+    __shared__ double s1[BN_T], s2[BN_T];     // fp64 like the statistics: both sums cancel (g has both signs)
     const int t = threadIdx.x;
     const int active = (BN_T / C) * C, rpp = active / C;
-    float a = 0.f, b = 0.f;
+    double a = 0., b = 0.;
     if (t < active) {
         const int c = t % C;
         const float mu = mean[c], inv = rsqrtf(var[c] + eps), ga = gamma[c], be = beta[c];
@@ -123,14 +127,14 @@ __global__ __launch_bounds__(BN_T) void bn_bwd_reduce_kernel(const float *__rest
             const float xh = (x[r * C + c] - mu) * inv;
             float g = dy[r * C + c];
             if (relu && fmaf(xh, ga, be) <= 0.f) g = 0.f;
-            a += g; b = fmaf(g, xh, b);
+            a += (double)g; b = fma((double)g, (double)xh, b);
         }
     }
     s1[t] = a; s2[t] = b;
     __syncthreads();
     if (t < C) {
         double da = 0., db = 0.;
-        for (int k = t; k < active; k += C) { da += (double)s1[k]; db += (double)s2[k]; }
+        for (int k = t; k < active; k += C) { da += s1[k]; db += s2[k]; }
         acc[(size_t)blockIdx.x * 2 * C + t] = da;
         acc[(size_t)blockIdx.x * 2 * C + C + t] = db;
     }
@@ -186,7 +190,7 @@ extern "C" int d3_bn_stats(const float *x, int M, int C, float *mean, float *var
     hipStream_t s = d3_stream(stream);
     const int nb = bn_blocks(M, C);
     bn_stats_kernel<<<nb, BN_T, 0, s>>>(x, M, C, (double *)ws);
-    bn_finalize_kernel<<<(C + 3) / 4, 256, 0, s>>>((const double *)ws, nb, M, C, mean, var, running_mean, running_var,
+    bn_finalize_kernel<<<(C + 3) / 4, 256, 0, s>>>(x, (const double *)ws, nb, M, C, mean, var, running_mean, running_var,
                                                   momentum);
     D3_LAUNCH_CHECK();
     return 0;

@@ -403,13 +403,12 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const float *__restrict__ z
         for (int c = 0; c < C; c++) m = fmaxf(m, zr[c]);
         float se = 0.f;
         for (int c = 0; c < C; c++) se += expf(zr[c] - m);
-        const float lse = m + logf(se);
         if (lb == ignore || lb < 0 || lb >= C) {
             for (int c = 0; c < C; c++) gr[c] = 0.f;
         } else {
             const float inv = 1.f / se;
             for (int c = 0; c < C; c++) gr[c] = expf(zr[c] - m) * inv - (c == lb ? 1.f : 0.f);
-            ls += lse - zr[lb]; cnt += 1.f;
+            ls += logf(se) - (zr[lb] - m); cnt += 1.f;    // not (m + log se) - z: that rounds at the magnitude of the logits
         }
     }
     s1[threadIdx.x] = ls; s2[threadIdx.x] = cnt;
@@ -444,13 +443,12 @@ __global__ __launch_bounds__(256) void ce_fwd_lds_kernel(const float *__restrict
             for (int c = 0; c < C; c++) m = fmaxf(m, zr[c]);
             float se = 0.f;
             for (int c = 0; c < C; c++) se += expf(zr[c] - m);
-            const float lse = m + logf(se);
             if (lb == ignore || lb < 0 || lb >= C) {
                 for (int c = 0; c < C; c++) zr[c] = 0.f;
             } else {
                 const float inv = 1.f / se, zl = zr[lb];
                 for (int c = 0; c < C; c++) zr[c] = expf(zr[c] - m) * inv - (c == lb ? 1.f : 0.f);
-                ls += lse - zl; cnt += 1.f;
+                ls += logf(se) - (zl - m); cnt += 1.f;
             }
         }
         __syncthreads();
@@ -656,18 +654,19 @@ __global__ __launch_bounds__(SL_T) void score_rows_kernel(const float *__restric
         dscore[p] = (1.f / (1.f + expf(-x)) - z) / (float)P;
     }
 }
-// the terms added by one thread in proposal order: deterministic, and the order of the former single-workgroup kernel
+// the terms added by one thread in proposal order: deterministic, and the order of the former single-workgroup kernel; in fp64
+// (a serial fp32 sum of a thousand terms is off by several ulps of the result)
 __global__ void score_sum_kernel(const float *__restrict__ term, int P, float *__restrict__ out) {
     __shared__ float buf[1024];
-    float part = 0.f;
+    double part = 0.;
     for (int p0 = 0; p0 < P; p0 += 1024) {
         const int n = min(1024, P - p0);
         if ((int)threadIdx.x < n) buf[threadIdx.x] = term[p0 + threadIdx.x];
         __syncthreads();
-        if (threadIdx.x == 0) for (int i = 0; i < n; i++) part += buf[i];
+        if (threadIdx.x == 0) for (int i = 0; i < n; i++) part += (double)buf[i];
         __syncthreads();
     }
-    if (threadIdx.x == 0) out[0] = part / (float)P;
+    if (threadIdx.x == 0) out[0] = (float)(part / (double)P);
 }
 extern "C" int d3_score_loss(const float *scores, const float *ious, int P, int nInst, float fg, float bg, float *gt_iou,
                              float *dscore, float *out, void *stream) {
@@ -742,18 +741,18 @@ __global__ __launch_bounds__(XE_T) void xe_rows_kernel(const float *__restrict__
     }
 }
 __global__ __launch_bounds__(XE_T) void xe_reduce_kernel(const float *__restrict__ rowterm, int R, float *__restrict__ out) {
-    __shared__ float a[XE_T], b[XE_T];
+    __shared__ double a[XE_T], b[XE_T];      // fp64: the fixed-order sum adds no rounding of its own to the fp32 row terms
     const int t = threadIdx.x;
     const int per = (R + XE_T - 1) / XE_T;
-    float sa = 0.f, sb = 0.f;
-    for (int i = t * per; i < min(R, (t + 1) * per); i++) { sa += rowterm[i * 2]; sb += rowterm[i * 2 + 1]; }
+    double sa = 0., sb = 0.;
+    for (int i = t * per; i < min(R, (t + 1) * per); i++) { sa += (double)rowterm[i * 2]; sb += (double)rowterm[i * 2 + 1]; }
     a[t] = sa; b[t] = sb;
     __syncthreads();
     if (t == 0) {
-        float x = 0.f, y = 0.f;
+        double x = 0., y = 0.;
         for (int i = 0; i < XE_T; i++) { x += a[i]; y += b[i]; }
-        const float denom = rowterm[(long long)R * 2];
-        out[0] = x / denom; out[1] = y / denom;
+        const double denom = (double)rowterm[(long long)R * 2];
+        out[0] = (float)(x / denom); out[1] = (float)(y / denom);
     }
 }
 extern "C" size_t d3_masked_xe_ws_bytes(int N, int S) { return ((size_t)N * S * 2 + 1) * sizeof(float); }
