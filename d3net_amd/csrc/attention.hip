@@ -11,7 +11,7 @@
 // (B, h, nq, nk) tensor (index b / bias_div) and the mask from (B, nk).
 // Two forms: the scalar one below (exact fp32 FMA; round 1, kept behind D3_ATTN_SCALAR=1 as the cross-check) and the MFMA
 // form further down, which d3_attn_fwd / d3_attn_bwd launch.  Bytes: q,k,v,out once + P written once (kept for backward).
-#include "common.h"
+#include "dispatch.h"
 #include <stdlib.h>
 
 #define AT_MAXN 128   // max queries / keys
@@ -423,15 +423,8 @@ __global__ __launch_bounds__(AM_NW * 64) void attn_bwd_cols_mfma_kernel(const fl
 
 static bool am_scalar() { return d3_tune(D3T_ATTN_SCALAR) == 1; }   // (A/B measurements, tests)
 static int am_attrs() {
-    static bool done[64] = {false};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (!done[dev]) {
-        D3_CHECK(hipFuncSetAttribute((const void *)attn_fwd_mfma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, AM_LDS_FWD));
-        D3_CHECK(hipFuncSetAttribute((const void *)attn_bwd_rows_mfma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, AM_LDS_FWD));
-        done[dev] = true;
-    }
-    return 0;
+    if (const int rc = d3_allow_lds<attn_fwd_mfma_kernel>(AM_LDS_FWD)) return rc;
+    return d3_allow_lds<attn_bwd_rows_mfma_kernel>(AM_LDS_FWD);
 }
 
 extern "C" int d3_attn_fwd(const float *q, const float *k, const float *v, const float *bias, const float *mask,

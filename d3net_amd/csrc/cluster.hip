@@ -25,7 +25,7 @@
 //      (atomicMin of the parent's queue position), B: children per parent, scan, C: children
 //      written in (parent position, list order) -- which is the FIFO order.
 // All passes stream the neighbour lists: bytes = 4*nActive per pass + 12*n, HBM/L2 bound.
-#include "common.h"
+#include "dispatch.h"
 #include "prof.h"
 #include <stdio.h>
 #include <stdlib.h>
@@ -995,10 +995,8 @@ static int cl_fill(const ClRun &r, ClWs &w, int sumNPoint, int nCluster, bool de
     if (c0 == 0)
         cl_seed_kernel<<<nb, T, 0, s>>>(w.flag, w.cid, w.koff, n, w.seeds, r.cluster_offsets, nCluster, sumNPoint, nCluster > 0 ? w.lcnt : nullptr, w.star, cnt);
     if (nCluster > 0) {
-        static bool attr_done_dev[64] = {false};
         const size_t lds = (size_t)B2_LDS_INTS * sizeof(int);
-        if (d3_once_per_device(attr_done_dev))
-            D3_CHECK(hipFuncSetAttribute((const void *)cl_bfs2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        if (const int rc = d3_allow_lds<cl_bfs2_kernel>((int)lds)) return rc;
         if (c0 == 0) {
             if (d3_tune(D3T_BFS_NO_STAR) == 0)   // (tests: the switch forces the level loop for every cluster)
                 cl_star_kernel<<<(nCluster + 3) / 4, T, 0, s>>>(r.idx, r.start_len, w.own, w.seeds, w.koff, w.sizes, nCluster, w.star, r.cluster_idxs, cnt);

@@ -26,16 +26,6 @@ static inline hipStream_t d3_stream(void *s) { return (hipStream_t)s; }
 
 static inline size_t d3_align(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
 
-// true on the first call per device for a flag array `done[64]` (a dynamic-LDS attribute is set per device), and whenever the device
-// cannot be told
-static inline bool d3_once_per_device(bool *done) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return true;
-    if (done[dev]) return false;
-    done[dev] = true;
-    return true;
-}
-
 // carve typed, 256-byte aligned regions out of a workspace.  A layout function lists the regions once; the run carves
 // with it and checks ok() before its first launch, the *_ws_bytes query runs it on a null base (take() then returns
 // nullptr and only advances off) and reads off.

@@ -3,6 +3,7 @@
 // -- it travels as arguments.
 #pragma once
 #include "common.h"
+#include "dispatch.h"
 
 // ------------------------------------------------------------------------------ shared by the kernels
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -27,6 +28,15 @@ void d3_conv_count_t16();
 // ------------------------------------------------------------------------------ dispatchers <-> executor
 // fused BatchNorm backward of a data-gradient call (d3_spconv_fwd2_bnbwd): x is the BatchNorm INPUT, fp32, or bf16 with xbf16
 struct ConvBn { const void *x; const float *mean, *var, *gamma, *beta; int ldx, relu, xbf16; float eps; };
+// the BatchNorm fields of a kernel's argument struct (Conv2Args, Conv3Args) from bn; all zero for no BatchNorm (bn NULL).  Whether
+// the BatchNorm input is bf16 (bn->xbf16) stays with the caller: a field of one struct, a template argument for the other
+template <typename Args>
+static inline void d3_conv_bn_args(Args &a, const ConvBn *bn) {
+    static const ConvBn none{};
+    const ConvBn &b = bn ? *bn : none;
+    a.bnx = (decltype(a.bnx))b.x; a.bn_mean = b.mean; a.bn_var = b.var; a.bn_gamma = b.gamma; a.bn_beta = b.beta;
+    a.ldbx = b.ldx; a.bn_relu = b.relu; a.bn_eps = b.eps;
+}
 
 // optional tables of one forward / data-gradient call (all NULL: what a caller of the C ABI gets).  The caller has VALIDATED
 // tbl16 / tblq (d3_kmap_k3_pack16's / d3_kmap_k3_packq's flag read on the host).

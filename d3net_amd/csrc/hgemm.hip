@@ -26,7 +26,7 @@
 // Roofline: these GEMMs are latency / launch bound at M = 32 (0.3 GFLOP per decode step); the batched ones (classifier
 // over all time steps: 992 x 512 x 3004) are bound by the fp32 matrix rate.
 #include <mutex>
-#include "common.h"
+#include "dispatch.h"
 #include "prof.h"
 #include <stdlib.h>
 
@@ -445,25 +445,28 @@ static int hg_launch_batch(const d3_gemm_prob *probs, int nprobs, hipStream_t s)
     }
     void *pr = d3_prof_begin(3, pbytes, pflops, s);
     int variant[3] = {0, 0, 0};          // {kernel: 0 hg_gemm_tiled_kernel, 1 hg_gemm_kernel, RT, waves}
-#define HG_SPLIT(RTV, GY)                                                                                  \
-    do {                                                                                                   \
-        variant[0] = 1; variant[1] = RTV; variant[2] = kblocks >= 40 ? 16 : (kblocks >= 20 ? 8 : 4);        \
-        if (kblocks >= 40) hg_gemm_kernel<RTV, true, 16><<<dim3(ctiles, GY, nprobs), 1024, 0, s>>>(b);      \
-        else if (kblocks >= 20) hg_gemm_kernel<RTV, true, 8><<<dim3(ctiles, GY, nprobs), 512, 0, s>>>(b);   \
-        else hg_gemm_kernel<RTV, true, 4><<<dim3(ctiles, GY, nprobs), 256, 0, s>>>(b);                      \
-    } while (0)
-    if (maxM <= 32) {            // a decode step: K split over the waves of a workgroup
-        if (maxM <= 16) HG_SPLIT(1, 1);
-        else HG_SPLIT(1, 2);     // (one row tile per workgroup: twice the workgroups of two tiles per workgroup)
+    // hg_gemm_kernel with K split over the waves of a workgroup: rt row tiles per workgroup, gy workgroups down the rows
+    const auto split = [&](int rt, int gy) {
+        const int nw = kblocks >= 40 ? 16 : (kblocks >= 20 ? 8 : 4);
+        variant[0] = 1; variant[1] = rt; variant[2] = nw;
+        d3_with_value<1, 2>(rt, [&](auto r) {
+            constexpr int RT = decltype(r)::value;
+            return d3_with_value<4, 8, 16>(nw, [&](auto w) {
+                hg_gemm_kernel<RT, true, w.value><<<dim3(ctiles, gy, nprobs), w.value * 64, 0, s>>>(b);
+                return 0;
+            });
+        });
+    };
+    if (maxM <= 32) {            // a decode step
+        split(1, maxM <= 16 ? 1 : 2);     // (one row tile per workgroup: twice the workgroups of two tiles per workgroup)
     } else {
         const long long tiles16 = (long long)ctiles * ((maxM + 15) / 16);
         if (tiles16 < 2048) {    // few tiles: still split K so that the chip is covered
-            HG_SPLIT(2, (maxM + 31) / 32);
+            split(2, (maxM + 31) / 32);
         } else {
             hg_gemm_tiled_kernel<<<dim3((ctiles * 16 + HT_BN - 1) / HT_BN, (maxM + HT_BM - 1) / HT_BM, nprobs), 256, 0, s>>>(b);
         }
     }
-#undef HG_SPLIT
     if (pr) {
         const int tags[7] = {maxM, maxN, kblocks * 16, nprobs, variant[0], variant[1], variant[2]};
         for (int i = 0; i < 7; i++) d3_prof_tag(pr, i, tags[i]);

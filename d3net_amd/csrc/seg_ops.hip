@@ -7,7 +7,7 @@
 // workgroup owns a segment and reads it as one flat, fully coalesced stream of rows*C floats;
 // lane t always sees channel t % C (the active thread count is rounded down to a multiple of C).
 // All of these are HBM-bound: algorithmic bytes = 4*(rows*C) in + 4*(P*C) out + 4*(P+1).
-#include "common.h"
+#include "dispatch.h"
 
 #define SEG_THREADS 256
 
@@ -664,12 +664,7 @@ static int cluster_mean_launch(const float *inp, const int *offsets, float *mean
     // (segments of tens of thousands of points -- a floor, a wall -- set this launch's time: the 6-producer instance: 8 waves, wave 4 idle)
     constexpr int NP = 6;
     const size_t lds = (size_t)2 * NP * MEANW_CHUNK * sizeof(float) + 256;
-    static bool attr_done[64] = {false};
-    int dev_id = 0;
-    if (hipGetDevice(&dev_id) != hipSuccess || dev_id < 0 || dev_id >= 64 || !attr_done[dev_id]) {
-        D3_CHECK(hipFuncSetAttribute((const void *)sec_mean_pc_kernel<NP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        if (dev_id >= 0 && dev_id < 64) attr_done[dev_id] = true;
-    }
+    if (const int rc = d3_allow_lds<sec_mean_pc_kernel<NP>>((int)lds)) return rc;
     sec_mean_pc_kernel<NP><<<nProposal, MEANW_WAVES(NP) * 64, lds, s>>>(inp, offsets, mean, nProposal, 3, gidx, prediv);
     return 0;
 }

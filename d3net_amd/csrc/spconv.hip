@@ -227,18 +227,11 @@ static int launch_fwd_mfma(const float *x, const int *tbl, const float *W, float
     ksplit = (K + kper - 1) / kper;
     if (ksplit > 1) D3_CHECK(hipMemsetAsync(out, 0, (size_t)Mout * Cout * sizeof(float), s));
     const dim3 grid(tiles, ksplit);
-#define CV_CASE(NTV)                                                                                              \
-    case NTV:                                                                                                     \
-        spconv_fwd_mfma_kernel<NTV, TRANSW><<<grid, 256, 0, s>>>(x, tbl, W, out, Mout, K, Cin, Cout, flipk, kper, xbf16); \
-        break;
-    switch ((Cout + 15) / 16) {
-        CV_CASE(1) CV_CASE(2) CV_CASE(3) CV_CASE(4) CV_CASE(5) CV_CASE(6) CV_CASE(7) CV_CASE(8) CV_CASE(9)
-        CV_CASE(10) CV_CASE(11) CV_CASE(12) CV_CASE(13) CV_CASE(14)
-        default: return D3_ERR_ARG;
-    }
-#undef CV_CASE
-    D3_LAUNCH_CHECK();
-    return 0;
+    return d3_with_value<1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14>((Cout + 15) / 16, [&](auto nt) {
+        spconv_fwd_mfma_kernel<nt.value, TRANSW><<<grid, 256, 0, s>>>(x, tbl, W, out, Mout, K, Cin, Cout, flipk, kper, xbf16);
+        D3_LAUNCH_CHECK();
+        return 0;
+    });
 }
 
 extern "C" int d3_spconv_fwd(const float *x, const int *tbl, const float *W, float *out, int Min, int Mout, int K,

@@ -848,49 +848,42 @@ void d3_conv_count_t16() { g_t16_launches++; }         // (conv.h: the weight gr
 static inline void c2_inst(int *inst, int a0, int a1, int a2, int a3, int a4, int a5, int a6) {
     inst[0] = a0; inst[1] = a1; inst[2] = a2; inst[3] = a3; inst[4] = a4; inst[5] = a5; inst[6] = a6;
 }
-template <int NT>
-static int launch_fwd2_f32(const Conv2Args &a, const Conv2Plan &p, int *inst, hipStream_t s) {
-    static bool attr_done_dev[64] = {false};
-    if (d3_once_per_device(attr_done_dev)) {
-        D3_CHECK(hipFuncSetAttribute((const void *)spconv_fwd2_kernel<NT, true, false, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-        D3_CHECK(hipFuncSetAttribute((const void *)spconv_fwd2_kernel<NT, false, false, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-        if constexpr (NT <= C2_NW16_MAXNT)
-            D3_CHECK(hipFuncSetAttribute((const void *)spconv_fwd2_kernel<NT, true, false, 16, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    }
-    if constexpr (NT <= C2_NW16_MAXNT) {
-        if (p.nw == 16) { c2_inst(inst, NT, 1, 0, 16, 1, 0, 0); spconv_fwd2_kernel<NT, true, false, 16, true><<<p.grid, 1024, p.lds, s>>>(a); D3_LAUNCH_CHECK(); return 0; }
-    }
-    c2_inst(inst, NT, p.wlds ? 1 : 0, 0, 4, 1, 0, 0);
-    if (p.wlds) spconv_fwd2_kernel<NT, true, false, 4, true><<<p.grid, 256, p.lds, s>>>(a);
-    else spconv_fwd2_kernel<NT, false, false, 4, true><<<p.grid, 256, p.lds, s>>>(a);
+// one launch of an instance: its dynamic-LDS limit, the launch, the launch check
+template <auto Kernel>
+static int c2_launch(const Conv2Args &a, dim3 grid, int threads, size_t lds, int lds_limit, hipStream_t s) {
+    if (const int rc = d3_allow_lds<Kernel>(lds_limit)) return rc;
+    Kernel<<<grid, threads, lds, s>>>(a);
     D3_LAUNCH_CHECK();
     return 0;
+}
+template <int NT>
+static int launch_fwd2_f32(const Conv2Args &a, const Conv2Plan &p, int *inst, hipStream_t s) {
+    if constexpr (NT <= C2_NW16_MAXNT) {
+        if (p.nw == 16) {
+            c2_inst(inst, NT, 1, 0, 16, 1, 0, 0);
+            return c2_launch<spconv_fwd2_kernel<NT, true, false, 16, true>>(a, p.grid, 1024, p.lds, 160 * 1024, s);
+        }
+    }
+    c2_inst(inst, NT, p.wlds ? 1 : 0, 0, 4, 1, 0, 0);
+    return d3_with_bools([&](auto wlds) { return c2_launch<spconv_fwd2_kernel<NT, wlds.value, false, 4, true>>(a, p.grid, 256, p.lds, 96 * 1024, s); },
+                         p.wlds != 0);
 }
 // the statically shaped instances (K = 27, bf16 rows, weights in LDS)
 template <int NT, int NW, int ST>
 static int launch_fwd2_static(const Conv2Args &a, const Conv2Plan &p, int *inst, hipStream_t s) {
-    static bool attr_done_dev[64] = {false};
-    if (d3_once_per_device(attr_done_dev))
-        D3_CHECK(hipFuncSetAttribute((const void *)spconv_fwd2_kernel<NT, true, true, NW, false, 27, ST>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     // the stem (136 -> 16: five products per offset) drops the offsets no row of a 16-row tile has before its reduction loop
     // (spconv_fwd2_c_kernel: 266 -> 231 us at 649 k rows; for the 16 / 32-channel instances the mask pass cost more than the dropped
     // steps saved -- measured in round 5 -- and they run spconv_fwd3_kernel on the lane table since round 6 anyway)
     if constexpr (ST == 17) {
-        static bool attrc_done_dev[64] = {false};
-        if (d3_once_per_device(attrc_done_dev)) {
-            D3_CHECK(hipFuncSetAttribute((const void *)spconv_fwd2_c_kernel<NT, NW, ST, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            D3_CHECK(hipFuncSetAttribute((const void *)spconv_fwd2_c_kernel<NT, NW, ST, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        }
+        // (the plain instance of the stem's shape stays in the code object: its limit is raised as before, nothing launches it)
+        if (const int rc = d3_allow_lds<spconv_fwd2_kernel<NT, true, true, NW, false, 27, ST>>(160 * 1024)) return rc;
         c2_inst(inst, NT, 1, 1, NW, 0, 27, ST + (a.tbl16 ? 1000 : 0) + 4000);     // (+ 4000: spconv_fwd2_c_kernel, see bench.py's kernel naming)
-        if (a.tbl16) { spconv_fwd2_c_kernel<NT, NW, ST, true><<<p.grid, 64 * NW, p.lds, s>>>(a); g_t16_launches++; }
-        else spconv_fwd2_c_kernel<NT, NW, ST, false><<<p.grid, 64 * NW, p.lds, s>>>(a);
-        D3_LAUNCH_CHECK();
-        return 0;
+        if (a.tbl16) g_t16_launches++;
+        return d3_with_bools([&](auto t16) { return c2_launch<spconv_fwd2_c_kernel<NT, NW, ST, t16.value>>(a, p.grid, 64 * NW, p.lds, 160 * 1024, s); },
+                             a.tbl16 != nullptr);
     }
     c2_inst(inst, NT, 1, 1, NW, 0, 27, ST);
-    spconv_fwd2_kernel<NT, true, true, NW, false, 27, ST><<<p.grid, 64 * NW, p.lds, s>>>(a);
-    D3_LAUNCH_CHECK();
-    return 0;
+    return c2_launch<spconv_fwd2_kernel<NT, true, true, NW, false, 27, ST>>(a, p.grid, 64 * NW, p.lds, 160 * 1024, s);
 }
 template <int NT>
 static int launch_fwd2(const Conv2Args &a, const Conv2Plan &p, int *inst, hipStream_t s) {
@@ -909,56 +902,24 @@ static int launch_fwd2(const Conv2Args &a, const Conv2Plan &p, int *inst, hipStr
         // (48 -> 48 with the offset loop rolled: measured no faster than the generic instance -- 36 k rows are one tile per wave)
         // (32 -> 64 spills at 128 registers even with the rolled loop: generic instance)
     }
-    static bool attr_done_dev[64] = {false};
-    if (d3_once_per_device(attr_done_dev)) {   // allow more than 64 KB of dynamic LDS
-        D3_CHECK(hipFuncSetAttribute((const void *)spconv_fwd2_kernel<NT, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-        D3_CHECK(hipFuncSetAttribute((const void *)spconv_fwd2_kernel<NT, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-        D3_CHECK(hipFuncSetAttribute((const void *)spconv_fwd2_kernel<NT, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-        D3_CHECK(hipFuncSetAttribute((const void *)spconv_fwd2_kernel<NT, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-    }
     if constexpr (NT <= C2_NW16_MAXNT) {
-        if (p.nw == 16) {
-            static bool attr16_done_dev[64] = {false};
-            if (d3_once_per_device(attr16_done_dev)) {
-                D3_CHECK(hipFuncSetAttribute((const void *)spconv_fwd2_kernel<NT, true, true, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                D3_CHECK(hipFuncSetAttribute((const void *)spconv_fwd2_kernel<NT, true, false, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            }
+        if (p.nw == 16) {      // (16 waves: the weights are in LDS always)
             c2_inst(inst, NT, 1, a.xbf16 ? 1 : 0, 16, 0, 0, 0);
-            if (a.xbf16) spconv_fwd2_kernel<NT, true, true, 16><<<p.grid, 1024, p.lds, s>>>(a);
-            else spconv_fwd2_kernel<NT, true, false, 16><<<p.grid, 1024, p.lds, s>>>(a);
-            D3_LAUNCH_CHECK();
-            return 0;
+            return d3_with_bools([&](auto xbf) { return c2_launch<spconv_fwd2_kernel<NT, true, xbf.value, 16>>(a, p.grid, 1024, p.lds, 160 * 1024, s); },
+                                 a.xbf16 != 0);
         }
     }
     c2_inst(inst, NT, p.wlds ? 1 : 0, a.xbf16 ? 1 : 0, 4, 0, 0, 0);
-    if (a.xbf16) {
-        if (p.wlds) spconv_fwd2_kernel<NT, true, true><<<p.grid, 256, p.lds, s>>>(a);
-        else spconv_fwd2_kernel<NT, false, true><<<p.grid, 256, p.lds, s>>>(a);
-    } else {
-        if (p.wlds) spconv_fwd2_kernel<NT, true, false><<<p.grid, 256, p.lds, s>>>(a);
-        else spconv_fwd2_kernel<NT, false, false><<<p.grid, 256, p.lds, s>>>(a);
-    }
-    D3_LAUNCH_CHECK();
-    return 0;
+    return d3_with_bools([&](auto wlds, auto xbf) { return c2_launch<spconv_fwd2_kernel<NT, wlds.value, xbf.value>>(a, p.grid, 256, p.lds, 96 * 1024, s); },
+                         p.wlds != 0, a.xbf16 != 0);
 }
 template <int NTW>
 static int launch_fwd2_split(const Conv2Args &a, const Conv2Plan &p, int *inst, hipStream_t s) {
-    static bool attr_done_dev[64] = {false};
-    if (d3_once_per_device(attr_done_dev)) {
-        D3_CHECK(hipFuncSetAttribute((const void *)spconv_fwd2_split_kernel<NTW, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-        D3_CHECK(hipFuncSetAttribute((const void *)spconv_fwd2_split_kernel<NTW, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-    }
     c2_inst(inst, NTW, a.f32 ? 0 : (a.xbf16 ? 1 : 0), a.f32 ? 1 : 0, -1, 0, 0, 0);
-    if (a.f32) {
-        static bool attr32_done_dev[64] = {false};
-        if (d3_once_per_device(attr32_done_dev))
-            D3_CHECK(hipFuncSetAttribute((const void *)spconv_fwd2_split_kernel<NTW, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-        spconv_fwd2_split_kernel<NTW, false, true><<<dim3(p.grid, p.gy), p.W * 64, p.lds, s>>>(a);
-    } else
-    if (a.xbf16) spconv_fwd2_split_kernel<NTW, true><<<dim3(p.grid, p.gy), p.W * 64, p.lds, s>>>(a);
-    else spconv_fwd2_split_kernel<NTW, false><<<dim3(p.grid, p.gy), p.W * 64, p.lds, s>>>(a);
-    D3_LAUNCH_CHECK();
-    return 0;
+    const dim3 grid(p.grid, p.gy);
+    if (a.f32) return c2_launch<spconv_fwd2_split_kernel<NTW, false, true>>(a, grid, p.W * 64, p.lds, 128 * 1024, s);      // (fp32 MFMA needs fp32 gathers)
+    return d3_with_bools([&](auto xbf) { return c2_launch<spconv_fwd2_split_kernel<NTW, xbf.value>>(a, grid, p.W * 64, p.lds, 128 * 1024, s); },
+                         a.xbf16 != 0);
 }
 
 // internal forward / data-gradient entry (conv.h)
@@ -999,12 +960,9 @@ int d3_conv2_run(const void *x, int ldx, const int *tbl, const void *Wp, float *
         const unsigned long long xb = Min > 0 ? ((unsigned long long)(Min - 1) * ldx + Cin) * elt : 0ull;
         a.xbytes = (Min > 0 && Min < (1 << 24) && rowb < (1ull << 24) && xb <= 0x7FFFFFFFull) ? (unsigned int)xb : 0u;   // (24-bit row x row-bytes multiply; absent rows address 2 GiB)
     }
-    a.bnx = nullptr; a.bn_mean = a.bn_var = a.bn_gamma = a.bn_beta = nullptr; a.ldbx = 0; a.bn_relu = 0; a.bn_eps = 0.f; a.bnx_bf16 = 0;
-    if (bn) {
-        if (bn->ldx & 3) return D3_ERR_ARG;
-        a.bnx = (const float *)bn->x; a.bn_mean = bn->mean; a.bn_var = bn->var; a.bn_gamma = bn->gamma; a.bn_beta = bn->beta;
-        a.ldbx = bn->ldx; a.bn_relu = bn->relu; a.bn_eps = bn->eps; a.bnx_bf16 = bn->xbf16;
-    }
+    if (bn && (bn->ldx & 3)) return D3_ERR_ARG;
+    d3_conv_bn_args(a, bn);
+    a.bnx_bf16 = bn ? bn->xbf16 : 0;
     const Conv2Plan p = conv2_plan(Mout, K, Cin, Cout, f32 != 0);
     *nparts = p.grid;
     if (!p.split && a.xbytes == 0u) return D3_ERR_RANGE;   // the wave-per-tile kernel addresses x through a raw buffer: <= 2 GiB, < 2^24 rows
@@ -1012,36 +970,15 @@ int d3_conv2_run(const void *x, int ldx, const int *tbl, const void *Wp, float *
                          (tbl ? 4.0 * (double)Mout * K : 0.0) + (res ? 4.0 * (double)Mout * Cout : 0.0);
     void *pr = d3_prof_begin(p.split ? 2 : 0, bytes, 0.0, s);
     int inst[7] = {0, 0, 0, 0, 0, 0, 0};      // filled by launch_fwd2*
-    auto tag_rec = [&]() {
-        if (!pr) return;
+    a.NT = (Cout + 15) / 16;
+    // workgroup-per-tile: column tiles per workgroup, more than 7 run the 7 instance; wave-per-tile: one instance per count of column tiles
+    const int rc = p.split ? d3_with_value<1, 2, 3, 4, 5, 6, 7>(p.ntw > 7 ? 7 : p.ntw, [&](auto ntw) { return launch_fwd2_split<ntw.value>(a, p, inst, s); })
+                           : d3_with_value<1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14>(a.NT, [&](auto nt) { return launch_fwd2<nt.value>(a, p, inst, s); });
+    if (pr) {
         const int dims[5] = {Min, Mout, K, Cin, Cout};
         for (int i = 0; i < 5; i++) d3_prof_tag(pr, i, dims[i]);
         for (int i = 0; i < 7; i++) d3_prof_tag(pr, 5 + i, inst[i]);
-    };
-    int rc;
-    a.NT = (Cout + 15) / 16;
-    if (p.split) {
-        switch (p.ntw) {
-            case 1: rc = launch_fwd2_split<1>(a, p, inst, s); break;
-            case 2: rc = launch_fwd2_split<2>(a, p, inst, s); break;
-            case 3: rc = launch_fwd2_split<3>(a, p, inst, s); break;
-            case 4: rc = launch_fwd2_split<4>(a, p, inst, s); break;
-            case 5: rc = launch_fwd2_split<5>(a, p, inst, s); break;
-            case 6: rc = launch_fwd2_split<6>(a, p, inst, s); break;
-            default: rc = launch_fwd2_split<7>(a, p, inst, s); break;
-        }
-        tag_rec();
-        d3_prof_end(pr, s);
-        return rc;
     }
-#define C2_CASE(NTV) case NTV: rc = launch_fwd2<NTV>(a, p, inst, s); break;
-    switch ((Cout + 15) / 16) {
-        C2_CASE(1) C2_CASE(2) C2_CASE(3) C2_CASE(4) C2_CASE(5) C2_CASE(6) C2_CASE(7) C2_CASE(8) C2_CASE(9)
-        C2_CASE(10) C2_CASE(11) C2_CASE(12) C2_CASE(13) C2_CASE(14)
-        default: rc = D3_ERR_ARG;
-    }
-#undef C2_CASE
-    tag_rec();
     d3_prof_end(pr, s);
     return rc;
 }

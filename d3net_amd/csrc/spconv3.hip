@@ -371,7 +371,7 @@ static int c3_launch_inst(const Conv3Args &a, const Conv3Plan &p, int *grid_out,
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
     if (!occ_dev[dev]) {
-        D3_CHECK(hipFuncSetAttribute((const void *)spconv_fwd3_kernel<ST, NT, EPI, OBF, BXBF, NW, QC>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        if (const int rc = d3_allow_lds<spconv_fwd3_kernel<ST, NT, EPI, OBF, BXBF, NW, QC>>(160 * 1024)) return rc;
         int nblk = 0;
         D3_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nblk, (const void *)spconv_fwd3_kernel<ST, NT, EPI, OBF, BXBF, NW, QC>, NW * 64, p.lds));
         occ_dev[dev] = nblk < 1 ? 1 : (nblk > 16 / NW ? 16 / NW : nblk);      // (measured: 16 -> 16 at five waves per SIMD runs no faster than at four -- 23.7 vs 23.5 us)
@@ -391,10 +391,14 @@ static int c3_launch_inst(const Conv3Args &a, const Conv3Plan &p, int *grid_out,
 }
 template <int ST, int NT, int NW, int QC>
 static int c3_launch_shape(const Conv3Args &a, const Conv3Plan &p, int epi, bool obf, bool bxbf, int *grid_out, hipStream_t s) {
-    if (epi == C3_EPI_PLAIN) return obf ? c3_launch_inst<ST, NT, C3_EPI_PLAIN, true, false, NW, QC>(a, p, grid_out, s) : c3_launch_inst<ST, NT, C3_EPI_PLAIN, false, false, NW, QC>(a, p, grid_out, s);
-    if (epi == C3_EPI_RES) return obf ? D3_ERR_ARG : c3_launch_inst<ST, NT, C3_EPI_RES, false, false, NW, QC>(a, p, grid_out, s);
-    if (obf) return bxbf ? c3_launch_inst<ST, NT, C3_EPI_BNBWD, true, true, NW, QC>(a, p, grid_out, s) : c3_launch_inst<ST, NT, C3_EPI_BNBWD, true, false, NW, QC>(a, p, grid_out, s);
-    return bxbf ? c3_launch_inst<ST, NT, C3_EPI_BNBWD, false, true, NW, QC>(a, p, grid_out, s) : c3_launch_inst<ST, NT, C3_EPI_BNBWD, false, false, NW, QC>(a, p, grid_out, s);
+    return d3_with_value<C3_EPI_PLAIN, C3_EPI_RES, C3_EPI_BNBWD>(epi, [&](auto e) {
+        constexpr int EPI = decltype(e)::value;
+        return d3_with_bools([&](auto o, auto bx) {
+            // no instances: a residual epilogue with a bf16 output; a bf16 BatchNorm input outside the BatchNorm-backward epilogue
+            if constexpr ((EPI == C3_EPI_RES && o.value) || (EPI != C3_EPI_BNBWD && bx.value)) return (int)D3_ERR_ARG;
+            else return c3_launch_inst<ST, NT, EPI, o.value, bx.value, NW, QC>(a, p, grid_out, s);
+        }, obf, epi == C3_EPI_BNBWD && bxbf);
+    });
 }
 
 // internal entry (conv.h: spconv2.hip's dispatcher and the C ABI below).  Returns D3_ERR_ARG for shapes without an instance.
@@ -412,8 +416,7 @@ int d3_conv3_run(const void *x, int ldx, const void *tq, const void *Wp, void *o
     a.x = x; a.tq = (const uint4 *)tq; a.rec = (const unsigned int *)((const char *)tq + (size_t)((Mout + 15) / 16) * 1024); a.Wp = (const uint4 *)Wp;
     a.out = out; a.res = res; a.part = part; a.part2 = part ? part2 : nullptr;
     a.ldx = ldx; a.ldo = ldo; a.ldr = ldr; a.Mout = Mout; a.ntiles = (Mout + 15) / 16; a.xbytes = xb;
-    a.bnx = nullptr; a.bn_mean = a.bn_var = a.bn_gamma = a.bn_beta = nullptr; a.ldbx = 0; a.bn_relu = 0; a.bn_eps = 0.f;
-    if (bn) { a.bnx = bn->x; a.bn_mean = bn->mean; a.bn_var = bn->var; a.bn_gamma = bn->gamma; a.bn_beta = bn->beta; a.ldbx = bn->ldx; a.bn_relu = bn->relu; a.bn_eps = bn->eps; }
+    d3_conv_bn_args(a, bn);
     const int epi = bn ? C3_EPI_BNBWD : (res ? C3_EPI_RES : C3_EPI_PLAIN);
     const bool obf = obf16 != 0, bxbf = bn && bn->xbf16;
     const int ST = Cin / 8, NT = Cout / 16;

@@ -22,7 +22,7 @@
 // library.  Results match the reference's own module to summation order (tests/test_speaker_gpu.py, golden vectors).
 // Roofline: launch / latency bound (0.3 GFLOP and ~20 MB of L2-resident weights per step); the measure is launches and
 // microseconds per step, reported by bench.py's profile.
-#include "common.h"
+#include "dispatch.h"
 #include "prof.h"
 #include <string.h>
 
@@ -1256,12 +1256,7 @@ extern "C" int d3_beam_select(const float *logits, const float *sums_in, int N, 
     if (live < 1 || live > b || b < 1 || b > 8 || V < 1 || t < 0 || t >= Tmax || (t > 0 && !seq_prev)) return D3_ERR_ARG;
     const size_t lds = (size_t)live * V * sizeof(float);
     if (lds > 60 * 1024) {        // (b = 8 beams over a 3004-word vocabulary: 94 KB)
-        static bool attr_done[64] = {false};
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64 || !attr_done[dev]) {
-            D3_CHECK(hipFuncSetAttribute((const void *)td_beam_select_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 8 * 1024));
-            if (dev >= 0 && dev < 64) attr_done[dev] = true;
-        }
+        if (const int rc = d3_allow_lds<td_beam_select_kernel>(160 * 1024 - 8 * 1024)) return rc;
         if (lds > 150 * 1024) return D3_ERR_ARG;
     }
     td_beam_select_kernel<<<N, BS_T, lds, d3_stream(stream)>>>(logits, sums_in, live, b, V, eos, last, t, Tmax, seq_prev, seq_out, tok_out, snap_out, ended_out,
@@ -1365,9 +1360,10 @@ extern "C" int d3_topdown_greedy(const d3_topdown_args *a, const float *fp, int 
 // instead of two of each: the recurrence is a chain of dependent ~7 us launches, so the step costs its length, not its rows.
 // Every row's arithmetic is that of the separate decodes (a row of the step never reads another row).  Beam outputs as
 // d3_topdown_beam; g_words / g_lps (glen, samples), glen >= max_len (the reference decodes max_spk_len + 1 greedy steps).
-static int td_beam_select_lds(size_t lds, const void *kernel) {
+template <auto Kernel>
+static int td_beam_select_lds(size_t lds) {
     if (lds > 150 * 1024) return D3_ERR_ARG;
-    if (lds > 60 * 1024) D3_CHECK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 8 * 1024));
+    if (lds > 60 * 1024) return d3_allow_lds<Kernel>(160 * 1024 - 8 * 1024);
     return 0;
 }
 extern "C" int d3_topdown_beam_greedy(const d3_topdown_args *a, const float *fp, int b, float *const *h1, float *const *h2, float *logits,
@@ -1378,7 +1374,7 @@ extern "C" int d3_topdown_beam_greedy(const d3_topdown_args *a, const float *fp,
     const int rs = b + 1, N = a->N / rs, H = a->H, V = a->V;
     const size_t per = (size_t)N * b;
     hipStream_t s = d3_stream(stream);
-    int rc = td_beam_select_lds((size_t)b * V * sizeof(float), (const void *)td_beam_greedy_select_kernel);
+    int rc = td_beam_select_lds<td_beam_greedy_select_kernel>((size_t)b * V * sizeof(float));
     if (rc) return rc;
     float *P1 = h1[1], *Q1 = h1[2], *R1 = h1[0], *P2 = h2[1], *Q2 = h2[2], *R2 = h2[0];
     rc = d3_topdown_step(a, first_word, fp, rs, R1, R2, P1, P2, logits, attn, ws, ws_bytes, stream);

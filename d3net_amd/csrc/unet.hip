@@ -1293,12 +1293,11 @@ static int net_forward_impl(const Net *n, NetRun &r, const void *const *params, 
                     // statistics + normalisation in one launch (un_bn_fused_small_kernel); big levels: up to 512 workgroups
                     int G, rows_pb; un_fs_grid(M, C, G, rows_pb, M <= fs_rows ? 32 : 512);
                     float *rm = o.rmean >= 0 ? (float *)params[o.rmean] : nullptr, *rv = o.rvar >= 0 ? (float *)params[o.rvar] : nullptr;
-#define UN_FSF(OBFV, XBFV)                                                                                                             \
-                    un_bn_fused_small_kernel<OBFV, XBFV><<<G, UN_FS_T, 0, s>>>(ss[0], ss[1], (const float *)tp(o.in), ti.ld, gamma, beta, \
-                                                                              tp(o.out), to.ld, M, C, o.eps, o.relu, mean, var, rm, rv, o.momentum, rows_pb)
-                    if (to.dtype == 1) { if (ti.dtype == 1) UN_FSF(true, true); else UN_FSF(true, false); }
-                    else { if (ti.dtype == 1) UN_FSF(false, true); else UN_FSF(false, false); }
-#undef UN_FSF
+                    d3_with_bools([&](auto obf, auto xbf) {
+                        un_bn_fused_small_kernel<obf.value, xbf.value><<<G, UN_FS_T, 0, s>>>(ss[0], ss[1], (const float *)tp(o.in), ti.ld, gamma, beta, tp(o.out),
+                                                                                             to.ld, M, C, o.eps, o.relu, mean, var, rm, rv, o.momentum, rows_pb);
+                        return 0;
+                    }, to.dtype == 1, ti.dtype == 1);
                     continue;
                 }
                 if (M > 0)
@@ -1311,12 +1310,11 @@ static int net_forward_impl(const Net *n, NetRun &r, const void *const *params, 
             }
             const long long total = (long long)M * (C / 4);
             if (total > 0) {
-                if (to.dtype == 1)
-                    un_bn_apply_kernel<true><<<un_ap_grid(M, C, 8), 256, 0, s>>>((const float *)tp(o.in), ti.ld, use_mean, use_var, gamma, beta,
-                                                                                     tp(o.out), to.ld, M, C, o.eps, o.relu, ti.dtype == 1 ? 1 : 0);
-                else
-                    un_bn_apply_kernel<false><<<un_ap_grid(M, C, 8), 256, 0, s>>>((const float *)tp(o.in), ti.ld, use_mean, use_var, gamma, beta,
-                                                                                      tp(o.out), to.ld, M, C, o.eps, o.relu, ti.dtype == 1 ? 1 : 0);
+                d3_with_bools([&](auto obf) {
+                    un_bn_apply_kernel<obf.value><<<un_ap_grid(M, C, 8), 256, 0, s>>>((const float *)tp(o.in), ti.ld, use_mean, use_var, gamma, beta, tp(o.out),
+                                                                                      to.ld, M, C, o.eps, o.relu, ti.dtype == 1 ? 1 : 0);
+                    return 0;
+                }, to.dtype == 1);
             }
         }
     }
@@ -1538,17 +1536,15 @@ static int net_backward_impl(const Net *n, NetRun &r, const void *const *params,
                     if (root_i >= 0) wait_pending(root_i);
                 }
                 if (!o.in_grad_mode) G = 1;
-#define UN_FSB2(OBFV, GBFV, XBFV, RELU_, ACC_, SH_)                                                                                   \
-                un_bn_bwd_fused_small_kernel<OBFV, GBFV, XBFV><<<G, UN_FS_T, 0, s>>>((const float *)(garena + o.bpart.off), bparts[i], x, ti.ld, go, ldgo, mean, \
-                                                                              var, gamma, beta, sums, pgrads[o.gamma], pgrads[o.beta], paccum[o.gamma], gi, \
-                                                                              ldgi, M, C, o.eps, RELU_, ACC_, SH_, rows_pb, \
-                                                                              use_p2 ? (const double *)(garena + o.bpart2.off) : nullptr)
-#define UN_FSB(OBFV, GBFV, RELU_, ACC_, SH_) do { if (ti.dtype == 1) UN_FSB2(OBFV, GBFV, true, RELU_, ACC_, SH_); else UN_FSB2(OBFV, GBFV, false, RELU_, ACC_, SH_); } while (0)
-                if (gibf) { if (gobf) UN_FSB(true, true, 0, 0, nullptr); else UN_FSB(true, false, 0, 0, nullptr); }
-                else if (gobf) UN_FSB(false, true, 0, o.in_grad_mode == 2 ? 1 : 0, sh);
-                else UN_FSB(false, false, 0, o.in_grad_mode == 2 ? 1 : 0, sh);
-#undef UN_FSB2
-#undef UN_FSB
+                // a bf16 input gradient never accumulates and never writes a shadow; the ReLU mask was the consumer's (relu 0)
+                const int acc = (!gibf && o.in_grad_mode == 2) ? 1 : 0;
+                unsigned short *const shw = gibf ? nullptr : sh;
+                d3_with_bools([&](auto obf, auto gbf, auto xbf) {
+                    un_bn_bwd_fused_small_kernel<obf.value, gbf.value, xbf.value><<<G, UN_FS_T, 0, s>>>(
+                        (const float *)(garena + o.bpart.off), bparts[i], x, ti.ld, go, ldgo, mean, var, gamma, beta, sums, pgrads[o.gamma], pgrads[o.beta],
+                        paccum[o.gamma], gi, ldgi, M, C, o.eps, 0, acc, shw, rows_pb, use_p2 ? (const double *)(garena + o.bpart2.off) : nullptr);
+                    return 0;
+                }, gibf != 0, gobf != 0, ti.dtype == 1);
                 continue;
             }
             if (o.fused_by >= 0) {   // reductions (and the ReLU mask) done by the consumer conv's data gradient
@@ -1564,13 +1560,14 @@ static int net_backward_impl(const Net *n, NetRun &r, const void *const *params,
                 float *gi = gp(vi); const int ldgi = vi.ld;
                 if (root_i >= 0) wait_pending(root_i);
                 const long long total = (long long)M * (C / 4);
-#define UN_APB(OBFV, GBFV, ACC_, SH_)                                                                                                     \
-                un_bn_bwd_apply_kernel<OBFV, GBFV><<<un_ap_grid(M, C, UN_AP_U * 2), 256, 0, s>>>(x, ti.ld, go, ldgo, mean, var, gamma, beta, sums, gi, ldgi, M, C, \
-                                                                                              o.eps, relu, ACC_, SH_, ti.dtype == 1 ? 1 : 0)
-                if (gibf) { if (gobf) UN_APB(true, true, 0, nullptr); else UN_APB(true, false, 0, nullptr); }
-                else if (gobf) UN_APB(false, true, o.in_grad_mode == 2 ? 1 : 0, sh);
-                else UN_APB(false, false, o.in_grad_mode == 2 ? 1 : 0, sh);
-#undef UN_APB
+                // a bf16 input gradient never accumulates and never writes a shadow
+                const int acc = (!gibf && o.in_grad_mode == 2) ? 1 : 0;
+                unsigned short *const shw = gibf ? nullptr : sh;
+                d3_with_bools([&](auto obf, auto gbf) {
+                    un_bn_bwd_apply_kernel<obf.value, gbf.value><<<un_ap_grid(M, C, UN_AP_U * 2), 256, 0, s>>>(x, ti.ld, go, ldgo, mean, var, gamma, beta, sums, gi, ldgi,
+                                                                                                               M, C, o.eps, relu, acc, shw, ti.dtype == 1 ? 1 : 0);
+                    return 0;
+                }, gibf != 0, gobf != 0);
             }
         }
     }

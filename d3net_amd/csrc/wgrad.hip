@@ -865,52 +865,44 @@ extern "C" int d3_spconv_wgrad2_splits(int Min, int Mout, int K, int Cin, int Co
     return wg2_plan_flags(Min, Mout, K, Cin, Cout, flags).R;
 }
 
-template <int MT, int NT, int KV, int NW, int OW, int KG, int S, bool GX, bool DYBF, bool T16>
-static int launch_wg3_i(const Wg3Args &a, const Wg2Plan &p, hipStream_t s) {
-    static bool attr_done_dev[64] = {false};
-    if (d3_once_per_device(attr_done_dev))
-        D3_CHECK(hipFuncSetAttribute((const void *)spconv_wgrad3_kernel<MT, NT, KV, NW, OW, KG, S, GX, DYBF, T16>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-    spconv_wgrad3_kernel<MT, NT, KV, NW, OW, KG, S, GX, DYBF, T16><<<dim3(p.R, KG), NW * 64, p.lds, s>>>(a);
-    return 0;
-}
 template <int MT, int NT, int KV, int NW, int OW, int KG, int S, bool GX>
 static int launch_wg3(const Wg3Args &a, const Wg2Plan &p, bool dybf, hipStream_t s) {
     static_assert(NW * OW * KG >= KV, "offsets not covered");
-    int rc;
-    if constexpr (KV == 27) {
-        if (a.tbl16) rc = dybf ? launch_wg3_i<MT, NT, KV, NW, OW, KG, S, GX, true, true>(a, p, s) : launch_wg3_i<MT, NT, KV, NW, OW, KG, S, GX, false, true>(a, p, s);
-        else rc = dybf ? launch_wg3_i<MT, NT, KV, NW, OW, KG, S, GX, true, false>(a, p, s) : launch_wg3_i<MT, NT, KV, NW, OW, KG, S, GX, false, false>(a, p, s);
-    } else {
-        rc = dybf ? launch_wg3_i<MT, NT, KV, NW, OW, KG, S, GX, true, false>(a, p, s) : launch_wg3_i<MT, NT, KV, NW, OW, KG, S, GX, false, false>(a, p, s);
-    }
-    if (rc) return rc;
-    D3_LAUNCH_CHECK();
-    return 0;
-}
-
-template <int TPO, int NU>
-static int launch_wg2(const Wg2Args &a, const Wg2Plan &p, hipStream_t s) {
-    static bool attr_done_dev[64] = {false};
-    if (d3_once_per_device(attr_done_dev))
-        D3_CHECK(hipFuncSetAttribute((const void *)spconv_wgrad2_kernel<TPO, NU>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-    spconv_wgrad2_kernel<TPO, NU><<<dim3(p.R, p.kg, p.passes), 256, p.lds, s>>>(a);
-    D3_LAUNCH_CHECK();
-    return 0;
+    return d3_with_bools([&](auto dy16, auto t16) {
+        if constexpr (KV != 27 && t16.value) return (int)D3_ERR_ARG;      // the 16-bit kernel map is K = 27's: no other instances
+        else {
+            constexpr auto kernel = spconv_wgrad3_kernel<MT, NT, KV, NW, OW, KG, S, GX, dy16.value, t16.value>;
+            if (const int rc = d3_allow_lds<kernel>(128 * 1024)) return rc;
+            kernel<<<dim3(p.R, KG), NW * 64, p.lds, s>>>(a);
+            D3_LAUNCH_CHECK();
+            return 0;
+        }
+    }, dybf, KV == 27 && a.tbl16 != nullptr);
 }
 
 // the one 16-wave workgroup per row split that holds all K x nt tiles (wg2_plan: p.wide)
 static int launch_wgw(const Wg2Args &a, const Wg2Plan &p, hipStream_t s) {
-    static bool wide_attr[64] = {false};
-    const bool set = d3_once_per_device(wide_attr);
-#define WGW_CASE(NTV)                                                                                                              \
-    case NTV:                                                                                                                      \
-        if (set) D3_CHECK(hipFuncSetAttribute((const void *)spconv_wgrad2_wide_kernel<NTV>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024)); \
-        spconv_wgrad2_wide_kernel<NTV><<<p.R, WGW_WAVES * 64, p.lds, s>>>(a);                                                      \
-        break;
-    switch (a.nt) { WGW_CASE(5) WGW_CASE(6) WGW_CASE(7) WGW_CASE(8) WGW_CASE(9) default: return D3_ERR_ARG; }
-#undef WGW_CASE
-    D3_LAUNCH_CHECK();
-    return 0;
+    return d3_with_value<5, 6, 7, 8, 9>(a.nt, [&](auto nt) {
+        if (const int rc = d3_allow_lds<spconv_wgrad2_wide_kernel<nt.value>>(128 * 1024)) return rc;
+        spconv_wgrad2_wide_kernel<nt.value><<<p.R, WGW_WAVES * 64, p.lds, s>>>(a);
+        D3_LAUNCH_CHECK();
+        return 0;
+    });
+}
+
+// tiles per offset group: 1, 2, 4, 8, anything else runs 16; 16-byte units per lane per offset: the first of 1, 2, 4, 7, 14 that holds p.nu
+static int launch_wg2(const Wg2Args &a, const Wg2Plan &p, hipStream_t s) {
+    const int tpo = (p.tpo == 1 || p.tpo == 2 || p.tpo == 4 || p.tpo == 8) ? p.tpo : 16;
+    const int nu = p.nu <= 1 ? 1 : p.nu <= 2 ? 2 : p.nu <= 4 ? 4 : p.nu <= 7 ? 7 : 14;
+    return d3_with_value<1, 2, 4, 8, 16>(tpo, [&](auto t) {
+        constexpr int TPO = decltype(t)::value;
+        return d3_with_value<1, 2, 4, 7, 14>(nu, [&](auto u) {
+            if (const int rc = d3_allow_lds<spconv_wgrad2_kernel<TPO, u.value>>(128 * 1024)) return rc;
+            spconv_wgrad2_kernel<TPO, u.value><<<dim3(p.R, p.kg, p.passes), 256, p.lds, s>>>(a);
+            D3_LAUNCH_CHECK();
+            return 0;
+        });
+    });
 }
 
 // x (Min, ldx) and dy (Mout, ldy), each fp32 or bf16 (D3_CONV_XBF16 / D3_CONV_DYBF16); tbl as for d3_spconv_wgrad
@@ -987,18 +979,7 @@ int d3_conv2_wgrad(const void *x, int ldx, const int *tbl, const void *tbl16, co
         } else if (p.wide) {
             rc = launch_wgw(a, p, s);
         } else {
-#define WG2_NU(TPOV)                                                                          \
-            (p.nu <= 1 ? launch_wg2<TPOV, 1>(a, p, s) : p.nu <= 2 ? launch_wg2<TPOV, 2>(a, p, s)          \
-             : p.nu <= 4 ? launch_wg2<TPOV, 4>(a, p, s) : p.nu <= 7 ? launch_wg2<TPOV, 7>(a, p, s)        \
-                                                                    : launch_wg2<TPOV, 14>(a, p, s))
-            switch (p.tpo) {
-                case 1: rc = WG2_NU(1); break;
-                case 2: rc = WG2_NU(2); break;
-                case 4: rc = WG2_NU(4); break;
-                case 8: rc = WG2_NU(8); break;
-                default: rc = WG2_NU(16); break;
-            }
-#undef WG2_NU
+            rc = launch_wg2(a, p, s);
         }
     }
     // the closing block: the partials' reduction when it is due, the profiling record's end

@@ -221,6 +221,32 @@ def test_executor_ops_teacher_forced_at_canonical_rows(dev, stem):
     assert e_in < 2e-2, e_in
 
 
+def test_executor_ops_teacher_forced_with_fp32_gradient_storage(dev):
+    """D3_GRAD_BF16=0 keeps every gradient buffer in fp32.  The plan then holds two launch arms no other test reaches: the one-launch
+    BatchNorm backward with a bf16 BatchNorm input and a bf16 shadow as dy but an fp32 input gradient
+    (un_bn_bwd_fused_small_kernel<false, true, true>), and the K = 27 weight gradients with an fp32 dy on the 16-bit kernel map
+    (spconv_wgrad3_kernel<..., DYBF false, T16 true>).  Same program, same oracle, same bounds as above."""
+    from d3net_amd import _lib, minkowski as ME, common, netexec
+    from d3net_amd.netexec import OP_CONV, OP_BNACT
+    DYBF16 = 64
+    L = _lib.lib()
+    with _lib.tuning(D3_GRAD_BF16=0):
+        norm = functools.partial(ME.MinkowskiBatchNorm, eps=1e-4, momentum=0.1)
+        net = torch.nn.Sequential(common.UBlock([16, 32, 48], norm, 2, common.ResidualBlock), norm(16), ME.MinkowskiReLU(inplace=True))
+        ME.fuse_bn_relu(net)
+        ex = netexec.NativeUNet(None, net[0], net[1], 16, True)
+        d = ex.describe([142920, 35127, 8282])      # (the plan is host code)
+        bn_arms = {(d["tensors"][raw[1]]["bf16"] if op["in_grad_mode"] else 0, d["tensors"][raw[2]]["bf16"], int(ex.b.tensors[raw[1]][4] == 1))
+                   for op, raw in zip(d["ops"], ex.b.ops) if op["type"] == OP_BNACT and op["fused_by"] >= 0}
+        assert (0, 1, 1) in bn_arms, bn_arms
+        k27 = [op for op, raw in zip(d["ops"], ex.b.ops) if op["type"] == OP_CONV and raw[7] == 27]
+        assert k27 and all(op["k3_tables"] == 1 and not (op["wgrad_flags"] & DYBF16) for op in k27), [(op["k3_tables"], op["wgrad_flags"]) for op in k27]
+        n0 = L.d3_spconv_t16_launches()
+        test_executor_ops_teacher_forced_at_canonical_rows(dev, False)
+        n_big = sum(1 for op, raw in zip(d["ops"], ex.b.ops) if op["type"] == OP_CONV and raw[7] == 27 and ex.b.tensors[raw[1]][0] <= 1)
+        assert n_big == 16 and L.d3_spconv_t16_launches() - n0 >= n_big      # one weight gradient on the 16-bit map per K = 27 layer of levels 0 and 1
+
+
 def _detector_step(dev, scene, seed=0):
     """one bf16 detector step on `scene` -> (loss, flat backbone gradient, backbone output checksum)"""
     from d3net_amd import synthetic as S

@@ -125,6 +125,114 @@ def test_conv_fwd_bwd_vs_oracle(dev, kind, cin, cout, exact):
         so.set_precision("fp32")
 
 
+# A layer whose input channels are no multiple of 8 runs the first-generation kernel (csrc/spconv.hip: spconv_fwd_mfma_kernel<NT, TRANSW>),
+# forward with NT = Cout / 16 column tiles, data gradient with NT = ceil(Cin / 16) and the transposed weight layout.  CONV_CASES'
+# stem (134 -> 16) is NT = 1 forward and 9 backward; these cases run 2..14 forward and 1..14 backward.
+FIRST_GEN_CASES = [(16 * a - 2, 16 * (a + 1)) for a in range(1, 14)] + [(222, 16)]
+
+
+@pytest.mark.parametrize("cin,cout", FIRST_GEN_CASES)
+def test_first_generation_conv_instances_vs_oracle(dev, cin, cout):
+    test_conv_fwd_bwd_vs_oracle(dev, "k3", cin, cout, False)
+
+
+@functools.lru_cache(maxsize=None)
+def _random_k3_table(M):
+    """an (M, 27) kernel map with 40 % absent neighbours (the kernels and the oracle take any table)"""
+    rng = np.random.default_rng(M)
+    tbl = rng.integers(0, M, (M, 27)).astype(np.int32)
+    tbl[rng.random((M, 27)) < 0.4] = -1
+    return tbl
+
+
+# Instances of the forward kernels that no layer shape of the networks selects (csrc/spconv2.hip: conv2_plan, d3_conv2_run):
+# (rows, Cout, bf16 rows, the plan the case is meant for).  Cin = 8, K = 27: the lane-table kernel has no instance for it.
+# 4,096 rows = 256 16-row tiles: workgroup-per-tile with 6 / 7 column tiles per workgroup; 16,400 rows = 1,025 tiles: wave-per-tile,
+# one instance per count of column tiles, weights in LDS up to 8 column tiles and read from memory from 9 on.
+FWD2_INSTANCE_CASES = [(4096, 176, False, dict(split=1, ntw=6)), (4096, 208, True, dict(split=1, ntw=7))] + \
+                      [(16400, 16 * nt, nt % 2 == 1, dict(split=0, waves=4, ntw=nt, wlds=1 if nt <= 8 else 0)) for nt in (5, 6, 7, 8, 9, 10, 11, 12, 13, 14)]
+
+
+@pytest.mark.parametrize("M,cout,xbf,want", FWD2_INSTANCE_CASES)
+def test_fwd2_instances_beyond_the_network_shapes(dev, M, cout, xbf, want):
+    import ctypes as C
+    from d3net_amd import _lib
+    from d3net_amd.pointgroup_ops import _ptr, _stream
+    L = _lib.lib()
+    K, cin, XBF16 = 27, 8, 32
+    plan = (C.c_int * 6)()
+    assert L.d3_spconv_fwd2_plan(M, K, cin, cout, plan) == 0
+    got_plan = dict(split=plan[0], waves=plan[1], grid=plan[2], wlds=plan[3], ntw=plan[4], gy=plan[5])
+    assert {k: got_plan[k] for k in want} == want, got_plan
+    assert L.d3_spconv_fwd3_nparts(M, cin, cout) == 0
+    rng = np.random.default_rng(M + cout)
+    tbl = _random_k3_table(M)
+    x = torch.from_numpy(rng.standard_normal((M, cin)).astype(np.float32))
+    W = torch.from_numpy((rng.standard_normal((K, cin, cout)) / np.sqrt(K * cin)).astype(np.float32))
+    with torch.no_grad():
+        ref32 = so.conv_k3(x, W, tbl)
+        so.set_precision("bf16")
+        try:
+            refb = so.conv_k3(x, W, tbl)
+        finally:
+            so.set_precision("fp32")
+    Wd = W.to(dev).contiguous()
+    wp = torch.empty(L.d3_spconv_pack_bytes(K, cin, cout), dtype=torch.uint8, device=dev)
+    assert L.d3_spconv_pack(_ptr(Wd), _ptr(wp), K, cin, cout, 0, _stream()) == 0
+    xd = x.to(dev).bfloat16() if xbf else x.to(dev)
+    td = torch.from_numpy(tbl).to(dev)
+    out = torch.full((M, cout), float("nan"), device=dev)
+    rc = L.d3_spconv_fwd2(_ptr(xd), cin, _ptr(td), _ptr(wp), _ptr(out), cout, None, 0, None, M, M, K, cin, cout, XBF16 if xbf else 0, _stream())
+    assert rc == 0, rc
+    assert relerr(out, refb) < 1e-4, relerr(out, refb)      # the kernels' arithmetic restated
+    assert relerr(out, ref32) < 2e-2, relerr(out, ref32)
+
+
+# Instances of the second-generation weight gradient that no layer shape of the networks selects (csrc/wgrad.hip: wg2_plan,
+# launch_wgw, launch_wg2), dy-stationary (gathered operand x: mt = Cin / 16 row tiles, stationary dy: nt = Cout / 16 column tiles):
+# (rows, Cin, Cout, the row splits the plan must report).  4,100 rows with mt = 1 and nt = 5..8: the wide kernel, one 16-wave
+# workgroup per split, min(256, ceil(129 chunks / 4)) = 33 splits (the tiled kernel would take 17).  600 rows (no wide kernel, no
+# third-generation kernel): spconv_wgrad2_kernel<TPO, NU>, TPO from mt * nt, NU from mt; 19 chunks of 32 rows -> 3 splits.
+WGRAD2_INSTANCE_CASES = [(4100, 16, 80, 33), (4100, 16, 96, 33), (4100, 16, 112, 33), (4100, 16, 128, 33),
+                         (600, 32, 16, 3),     # <2, 2>
+                         (600, 16, 48, 3),     # <4, 1>
+                         (600, 64, 16, 3),     # <4, 4>
+                         (600, 64, 32, 3),     # <8, 4>
+                         (600, 112, 16, 3),    # <8, 7>
+                         (600, 128, 16, 3),    # <8, 14>
+                         (600, 32, 80, 3),     # <16, 2>
+                         (600, 128, 32, 3)]    # <16, 14>
+
+
+@pytest.mark.parametrize("M,cin,cout,splits", WGRAD2_INSTANCE_CASES)
+def test_wgrad2_instances_beyond_the_network_shapes(dev, M, cin, cout, splits):
+    from d3net_amd import _lib
+    from d3net_amd.pointgroup_ops import _ptr, _stream
+    L = _lib.lib()
+    K = 27
+    assert L.d3_spconv_wgrad2_splits(M, M, K, cin, cout, 0) == splits
+    rng = np.random.default_rng(M + 1000 * cin + cout)
+    tbl = _random_k3_table(M)
+    x = torch.from_numpy(rng.standard_normal((M, cin)).astype(np.float32))
+    dy = torch.from_numpy(rng.standard_normal((M, cout)).astype(np.float32))
+    refs = {}
+    try:
+        for prec in ("fp32", "bf16"):
+            so.set_precision(prec)
+            Wo = torch.zeros((K, cin, cout), requires_grad=True)
+            so.conv_k3(x, Wo, tbl).backward(dy)
+            refs[prec] = Wo.grad
+    finally:
+        so.set_precision("fp32")
+    xd, dyd, td = x.to(dev), dy.to(dev), torch.from_numpy(tbl).to(dev)
+    ws = torch.empty(max(L.d3_spconv_wgrad2_ws_bytes(M, M, K, cin, cout, 0), 16), dtype=torch.uint8, device=dev)
+    dW = torch.full((K, cin, cout), float("nan"), device=dev)
+    rc = L.d3_spconv_wgrad2(_ptr(xd), cin, _ptr(td), _ptr(dyd), cout, _ptr(dW), M, M, K, cin, cout, cin, 0, _ptr(ws), ws.numel(), _stream())
+    assert rc == 0, rc
+    assert relerr(dW, refs["bf16"]) < 1e-4, relerr(dW, refs["bf16"])      # the kernels' arithmetic restated
+    assert relerr(dW, refs["fp32"]) < 2e-2, relerr(dW, refs["fp32"])
+
+
 @pytest.mark.parametrize("C,relu", [(16, True), (48, False), (112, True)])
 def test_batchnorm_relu_fwd_bwd(dev, C, relu):
     from d3net_amd import minkowski as ME
