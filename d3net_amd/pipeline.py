@@ -297,6 +297,40 @@ class PipelineNet(nn.Module):
         return {"bleu-1": bleu[0][0], "bleu-2": bleu[0][1], "bleu-3": bleu[0][2], "bleu-4": bleu[0][3], "cider": cider[0],
                 "meteor": meteor[0], "rouge": rouge[0]}
 
+    def evaluate_grounding(self, batches, evaluator=None, seeds=None):
+        """Acc@kIoU / ref_acc table and language accuracy of the listener over `batches`, scored on the device
+        (scripts/eval.py:168-426 eval_grounding): per seed `begin_repeat`, per batch the detector, the listener, `_ground` and
+        GroundingEvaluator.add_batch (no read-back), one compute at the end -> its dict (grounding_eval.py).  Modes 2 and 3.
+        seeds default to eval.py:170's list, cfg.eval.repeat long; with more than one, `batches` is walked once per seed and must be
+        re-iterable (anything but a one-shot iterator) or a zero-argument callable that returns a fresh iterator."""
+        import collections.abc
+        from .grounding_eval import GroundingEvaluator
+        if self.mode not in (2, 3):
+            raise NotImplementedError("evaluate_grounding needs the detector and the listener (modes 2 and 3), this is mode %d" % self.mode)
+        if seeds is None:
+            seeds = [self.cfg.general.manual_seed] + [2 * i for i in range(self.cfg.eval.repeat - 1)]
+        seeds = list(seeds)
+        one_shot = isinstance(batches, collections.abc.Iterator) or not isinstance(batches, collections.abc.Iterable)
+        if len(seeds) > 1 and not callable(batches) and one_shot:
+            raise TypeError("evaluate_grounding: %d seeds walk `batches` %d times; pass a sequence or a callable returning an iterator, "
+                            "not a one-shot iterator" % (len(seeds), len(seeds)))
+        ev = evaluator
+        if ev is None:
+            ev = GroundingEvaluator(use_lang_classifier=self.use_lang_classifier, device=next(self.parameters()).device)
+        was_training = self.training
+        self.eval()
+        try:
+            with torch.no_grad():
+                for seed in seeds:
+                    torch.manual_seed(seed); np.random.seed(seed)
+                    ev.begin_repeat()
+                    for batch in (batches() if callable(batches) else batches):
+                        self._lazy_proposals = False
+                        ev.add_batch(self._ground(self.listener(self._detect(dict(batch))), False))
+        finally:
+            self.train(was_training)
+        return ev.compute()
+
     def forward(self, data_dict):
         """inference entry point (model/pipeline.py:894-925): detector -> speaker -> listener, whichever exist"""
         if not self.no_detection:

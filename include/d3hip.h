@@ -859,6 +859,32 @@ int d3_caption_collect(const int *per_gt, const float *pred_boxes, const float *
 int d3_caption_stats(const int *cand, int ldc, const int *clen, const int *tokens, int ldt, const int *lens,
                      const int *slot_row, const int *u_off, int E, int *stats, int *lcs, void *stream);
 
+/* ---- grounding validation (csrc/grounding_eval.hip, driven by d3net_amd.grounding_eval.GroundingEvaluator) ------------------
+ * d3_ground_eval_batch: per validation batch, one launch, one wave per description row, in place of lib/grounding/eval_helper.py:28-137
+ *   (get_eval) and the per-batch appends of scripts/eval.py:197-262 (eval_grounding).  All pointers are device memory.  N = B * C rows,
+ *   scene of row n = n / C.  cluster_ref, cluster_labels (N,K) float32; proposal_mask (B,K) float32 (valid: truncates to 1, the
+ *   reference's `.long() == 1`); proposal_boxes (B,K,8,3), ref_boxes (N,8,3) float32 corners; unique_multiple, object_cat (N) int64;
+ *   lang_scores: NULL, or (N,n_lang) float32 with lang_correct non-NULL; scene_ids (B), chunk_ids (N) int64, read only when rec_ids
+ *   is given.  Per row: top = argmax(cluster_ref[n]), pred_ref = argmax(cluster_ref[n] * valid[b]) with the product formed in
+ *   float32, gt_ref = argmax(cluster_labels[n]), ref_acc = cluster_labels[n, top] == 1, iou / best_iou = lib/utils/bbox.py:221-244
+ *   get_aabb3d_iou of proposal pred_ref / gt_ref of scene b with ref_boxes[n] in float32, the reference's operation order.
+ *   Ties: the arg-max is torch.argmax on the CPU -- the lowest index wins among equal values, +0 == -0 (a row whose valid scores are
+ *   all negative scores its lowest invalid slot, as the reference does), a NaN ranks above every number and the lowest NaN wins.
+ *   table (3,2,4) int64 += per row, cell [m][o] with m = unique_multiple (0, 1, anything else -> 2), o = object_cat == 17:
+ *   {rows, ref_acc, iou >= 0.25f, iou >= 0.5f}; a NaN IoU compares false.  *lang_correct (int64) += argmax(lang_scores[n]) ==
+ *   object_cat[n].  Integer atomics only, at most 25 per workgroup: the sums do not depend on the order.  The caller zeroes table,
+ *   lang_correct and status.  Records, each NULL or written at row row0 + n: rec_iou, rec_best_iou float32; rec_pred_ref, rec_gt_ref,
+ *   rec_ref_acc int32; rec_pred_box, rec_gt_box (8,3) float32; rec_ids (2) int64 = scene_ids[b], chunk_ids[n].
+ *   *status (device int32) is OR-ed with 1 when the box at pred_ref, the box at gt_ref or the GT box holds a non-finite coordinate.
+ *   B < 1, C < 1, B * C >= 2^31, K outside [1, 4096] or, with lang_scores, n_lang outside [1, 64]: D3_ERR_RANGE before any launch.
+ *   No workspace. */
+int d3_ground_eval_batch(const float *cluster_ref, const float *cluster_labels, const float *proposal_mask,
+                         const float *proposal_boxes, const float *ref_boxes, const long long *unique_multiple,
+                         const long long *object_cat, const float *lang_scores, int n_lang, const long long *scene_ids,
+                         const long long *chunk_ids, int B, int C, int K, long long row0, long long *table, long long *lang_correct,
+                         float *rec_iou, float *rec_best_iou, int *rec_pred_ref, int *rec_gt_ref, int *rec_ref_acc,
+                         float *rec_pred_box, float *rec_gt_box, long long *rec_ids, int *status, void *stream);
+
 /* ---- PointGroup scene preparation (csrc/scene_prep.hip, driven by d3net_amd/scene_prep.py) ----------------------------------
  * One scene of n points: xyz (n,3) float32, ids / sem (n) int32 (ids -1 = none).  Coordinates are fp64 (numpy's float32 @ float64
  * promotion) unless fp32 != 0 (the validation path, float32 throughout like the reference's `points.copy() * scale`).
