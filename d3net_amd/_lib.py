@@ -164,6 +164,9 @@ SIGNATURES = {
     "d3_caption_stats": (i32, [vp, i32, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp]),
     "d3_ground_eval_batch": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, i32, i32, i32, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                    vp, vp, vp]),
+    "d3_caption_submit_batch": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i64, i32, i32, i32, vp, vp, vp, vp, vp,
+                                      vp, vp, vp, vp]),
+    "d3_ground_submit_batch": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "d3_scene_limits": (i32, [pi, pi, pi]),
     "d3_scene_transform": (i32, [vp, i32, vp, f64, i32, vp, vp, vp]),
     "d3_scene_reduce": (i32, [vp, vp, i32, vp, vp]),

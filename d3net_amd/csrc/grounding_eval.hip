@@ -19,35 +19,16 @@
 //                        int table in LDS, then at most 24 + 1 integer atomicAdd per workgroup reach the int64 table and the batch's
 //                        language counter: order-free, bit-reproducible.  A NaN IoU compares false.
 #include "common.h"
+#include "torch_argmax.h"       // ge_beats, ge_wave_argmax, GE_NONE: the arg-max rule, shared with submission.hip
 
 #define GE_THREADS 256
 #define GE_WAVES (GE_THREADS / 64)
 #define GE_MAX_K 4096
 #define GE_MAX_LANG 64
-#define GE_NONE 0x7fffffff      // index of a lane that holds no element: loses every draw
 
 // numpy's min / max / np.minimum / np.maximum: a NaN propagates
 __device__ __forceinline__ float ge_min(float a, float b) { return a != a ? a : (b != b ? b : fminf(a, b)); }
 __device__ __forceinline__ float ge_max(float a, float b) { return a != a ? a : (b != b ? b : fmaxf(a, b)); }
-
-// does (v, i) beat (bv, bi) under torch.argmax's CPU rule
-__device__ __forceinline__ bool ge_beats(float v, int i, float bv, int bi) {
-    if (i == GE_NONE) return false;
-    if (bi == GE_NONE) return true;
-    const bool vn = v != v, bn = bv != bv;
-    if (vn || bn) return vn && (!bn || i < bi);
-    return v > bv || (v == bv && i < bi);
-}
-
-__device__ __forceinline__ int ge_wave_argmax(float v, int i) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        const float ov = __shfl_xor(v, m, 64);
-        const int oi = __shfl_xor(i, m, 64);
-        if (ge_beats(ov, oi, v, i)) { v = ov; i = oi; }
-    }
-    return i;
-}
 
 // get_aabb3d_iou (bbox.py:221-244) of two boxes of 8 corners each, float32
 __device__ __forceinline__ float ge_iou(const float *c1, const float *c2) {

@@ -331,6 +331,62 @@ class PipelineNet(nn.Module):
             self.train(was_training)
         return ev.compute()
 
+    # --------------------------------------------------------------------------------------------- leaderboard writers
+    def _feed_only(self, data_dict):
+        """`detector.feed` alone, as the benchmark writers call it (benchmark_captioning.py:148, benchmark_grounding.py:119): no
+        parse_feed_ret, no loss -- a test split has no ground truth.  The batched-proposal step assigns every proposal its nearest
+        GT centre unless cfg.general.task == "test"; a batch without `center_label` is fed under that task, for this call only."""
+        keep, task = self.detector.compact_proposals, self.cfg.general.task
+        self.detector.compact_proposals = keep and not self.__dict__.get("_lazy_proposals", False)
+        if "center_label" not in data_dict:
+            self.cfg.general.task = "test"
+        try:
+            return self.detector.feed(data_dict, self.current_epoch)
+        finally:
+            self.detector.compact_proposals, self.cfg.general.task = keep, task
+
+    def _description_store(self, who):
+        store = getattr(self, "dataset_chunk_data", None)
+        if store is None:
+            raise ValueError("%s: the model was built without a description store (dataset.chunked_data); pass a submission" % who)
+        return store
+
+    def _predict(self, batches, submission, head):
+        was_training = self.training
+        self.eval()
+        try:
+            with torch.no_grad():
+                for batch in batches:
+                    self._lazy_proposals = False
+                    submission.add_batch(head(self._feed_only(dict(batch))))
+        finally:
+            self.train(was_training)
+        return submission
+
+    def predict_captioning(self, batches, submission=None):
+        """the Scan2Cap submission of `batches` (benchmark/benchmark_captioning.py:121-196 predict): per batch the detector's feed,
+        the speaker's evaluation decode and CaptionSubmission.add_batch (NMS + collect launch, no read-back) -> the submission;
+        `.results()` reads it back once, `.write(path)` dumps the file.  Batches need no ground-truth key.  Modes 1 and 3."""
+        from .submission import CaptionSubmission
+        if self.mode not in (1, 3):
+            raise NotImplementedError("predict_captioning needs the detector and the speaker (modes 1 and 3), this is mode %d" % self.mode)
+        sub = submission
+        if sub is None:
+            sub = CaptionSubmission(self._description_store("predict_captioning"), self.vocabulary, max_proposals=self.cfg.model.max_num_proposal,
+                                    max_len=self.cfg.data.max_spk_len + 1, device=next(self.parameters()).device)
+        return self._predict(batches, sub, lambda d: self.speaker(d, use_tf=False, use_rl=False, is_eval=True, beam_opt=self.beam_opt))
+
+    def predict_grounding(self, batches, submission=None):
+        """the ScanRefer submission of `batches` (benchmark/benchmark_grounding.py:110-186 predict): per batch the detector's feed,
+        the listener and GroundingSubmission.add_batch (one launch, no read-back) -> the submission.  Modes 2 and 3."""
+        from .submission import GroundingSubmission
+        if self.mode not in (2, 3):
+            raise NotImplementedError("predict_grounding needs the detector and the listener (modes 2 and 3), this is mode %d" % self.mode)
+        sub = submission
+        if sub is None:
+            sub = GroundingSubmission(self._description_store("predict_grounding"), device=next(self.parameters()).device)
+        return self._predict(batches, sub, self.listener)
+
     def forward(self, data_dict):
         """inference entry point (model/pipeline.py:894-925): detector -> speaker -> listener, whichever exist"""
         if not self.no_detection:

@@ -885,6 +885,44 @@ int d3_ground_eval_batch(const float *cluster_ref, const float *cluster_labels, 
                          float *rec_iou, float *rec_best_iou, int *rec_pred_ref, int *rec_gt_ref, int *rec_ref_acc,
                          float *rec_pred_box, float *rec_gt_box, long long *rec_ids, int *status, void *stream);
 
+/* ---- leaderboard prediction writers (csrc/submission.hip, driven by d3net_amd.submission) -----------------------------------
+ * All pointers are device memory; both are one launch, read nothing back and OR bits into *status (device int32, zeroed by the
+ * caller), on which the host raises when it reads the records.
+ * d3_caption_submit_batch: per test batch, after d3_nms3d_samecls, in place of the scene x proposal loop of
+ *   benchmark/benchmark_captioning.py:151-188 (predict).  corners (B,K,8,3), sem_cls (B,K), scores (B,K), pick (B,K) float32 (pick
+ *   == 1: kept by the NMS; no confidence threshold, as the reference); lang_cap (B,K,T) int64; ids (B) int64 dataset indices;
+ *   scene_of_id (D) int32: the scene slot of chunked_data[id][0]["scene_id"], -1: none.  State of S scene slots with room for Kcap
+ *   records of Tcap tokens each: rec_box (S,Kcap,8,3) float32, rec_cls (S,Kcap) int32 = the one-hot position of sem_prob (sem - 2,
+ *   negative -> 17, truncated), rec_score (S,Kcap) float32, rec_ntok (S,Kcap) int32, rec_tok (S,Kcap,Tcap) int32, count (S) int32
+ *   records of the scene, first_seen (S) int64 = batch_seq * 2^20 + row of the scene's first appearance, negative: never seen (the
+ *   caller fills it with -1).  One workgroup per row compacts the kept slots in slot order; rec_ntok = position of the first eos
+ *   + 1, or T without one (decode_caption's cut; "sos" and a missing "eos" are the host's).  Of several rows of one batch that
+ *   name the same scene the LAST writes the records and the count (`results[scene_id] = ...`), first_seen is the first such row's
+ *   and is written only while unset, the others return; stream order serialises the batches.
+ *   *status |= 1: a token outside [0, V) before a kept caption's cut; 2: a kept slot's class outside [0, 18); 4: an id outside
+ *   [0, D) or without a scene slot in [0, S) (that row writes nothing).
+ *   B outside [1, 2^20], K outside [1, 256], T outside [1, 62], Kcap < K, Tcap < T or batch_seq outside [0, 2^43): D3_ERR_RANGE
+ *   before any launch.
+ * d3_ground_submit_batch: per test batch, one wave per description row, in place of benchmark/benchmark_grounding.py:122-180
+ *   (predict).  N = B * C rows, scene of row n = n / C.  cluster_ref (N,K) float32; proposal_boxes (B,K,8,3) float32;
+ *   unique_multiple, object_cat, chunk_ids (N) int64; ids (B) int64; key_of (D,Cmax) int32: the number of the annotation's
+ *   "scene-object-ann" string (equal strings, equal numbers), -1: no such annotation.  pred_ref = argmax(cluster_ref[n]) over ALL
+ *   slots, torch.argmax's CPU rule (d3_ground_eval_batch's `top`): the reference does not mask invalid slots here.  Record at row
+ *   row0 + n: rec_box (8,3) float32 the box at pred_ref of scene n / C, rec_pred_ref int32, rec_unique_multiple int64, rec_others
+ *   int32 = object_cat == 17, rec_key int32, rec_keep int32 = 0 when an earlier row of THIS batch has the same key (or the key is
+ *   -1), rec_ids (2) int64 = ids[n / C], chunk_ids[n].  *status |= 1: an id / chunk id outside the table or a -1 entry.
+ *   B < 1, C < 1, B * C >= 2^31 or K outside [1, 4096]: D3_ERR_RANGE before any launch.  No workspace. */
+int d3_caption_submit_batch(const float *corners, const float *sem_cls, const float *scores, const float *pick,
+                            const long long *lang_cap, const long long *ids, const int *scene_of_id, int D, int B, int K, int T,
+                            int V, int eos, long long batch_seq, int S, int Kcap, int Tcap, float *rec_box, int *rec_cls,
+                            float *rec_score, int *rec_ntok, int *rec_tok, int *count, long long *first_seen, int *status,
+                            void *stream);
+int d3_ground_submit_batch(const float *cluster_ref, const float *proposal_boxes, const long long *unique_multiple,
+                           const long long *object_cat, const long long *ids, const long long *chunk_ids, const int *key_of, int D,
+                           int Cmax, int B, int C, int K, long long row0, float *rec_box, int *rec_pred_ref,
+                           long long *rec_unique_multiple, int *rec_others, int *rec_key, int *rec_keep, long long *rec_ids,
+                           int *status, void *stream);
+
 /* ---- PointGroup scene preparation (csrc/scene_prep.hip, driven by d3net_amd/scene_prep.py) ----------------------------------
  * One scene of n points: xyz (n,3) float32, ids / sem (n) int32 (ids -1 = none).  Coordinates are fp64 (numpy's float32 @ float64
  * promotion) unless fp32 != 0 (the validation path, float32 throughout like the reference's `points.copy() * scale`).
