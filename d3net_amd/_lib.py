@@ -167,6 +167,10 @@ SIGNATURES = {
     "d3_caption_submit_batch": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i64, i32, i32, i32, vp, vp, vp, vp, vp,
                                       vp, vp, vp, vp]),
     "d3_ground_submit_batch": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "d3_box_wire_limits": (i32, [pi, pi, pi]),
+    "d3_box_wire_verts": (i32, [vp, i32, C.POINTER(f64), vp, vp, vp]),
+    "d3_box_wire_text": (i32, [vp, vp, i32, C.POINTER(f64), vp, vp, vp, vp]),
+    "d3_format_f6": (i32, [vp, i64, vp, vp, vp, vp]),
     "d3_scene_limits": (i32, [pi, pi, pi]),
     "d3_scene_transform": (i32, [vp, i32, vp, f64, i32, vp, vp, vp]),
     "d3_scene_reduce": (i32, [vp, vp, i32, vp, vp]),

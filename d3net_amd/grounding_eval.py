@@ -248,6 +248,20 @@ class GroundingEvaluator:
             raise ValueError("GroundingEvaluator: no batch was added")
         return {k: t[:self._rows].cpu().numpy() for k, t in self._rec.items()}
 
+    def device_predictions(self, chunked_data):
+        """`predictions` for the box writer (d3net_amd.visualize.visualize_grounding): the same tree, but "pred_bbox" / "gt_bbox" are
+        rows of the device records (views, (8,3) float32) and there is no "iou"; only the (rows, 2) ids are read back"""
+        if not self.keep_predictions:
+            raise ValueError("GroundingEvaluator: constructed without keep_predictions")
+        if self._rec is None:
+            raise ValueError("GroundingEvaluator: no batch was added")
+        pred, gt = self._rec["pred_bbox"][:self._rows], self._rec["gt_bbox"][:self._rows]
+        out = {}
+        for i, (scene, chunk) in enumerate(self._rec["ids"][:self._rows].cpu().tolist()):
+            ann = chunked_data[scene][chunk]
+            out.setdefault(ann["scene_id"], {}).setdefault(ann["object_id"], {})[ann["ann_id"]] = {"pred_bbox": pred[i], "gt_bbox": gt[i]}
+        return out
+
     def predictions(self, chunked_data):
         """{scene_id: {object_id: {ann_id: {"pred_bbox", "gt_bbox", "iou"}}}} of the last repeat as scripts/eval.py:243-266 leaves it:
         `chunked_data[id][chunk_id]` names a row's annotation, later rows overwrite earlier ones"""

@@ -331,6 +331,26 @@ class PipelineNet(nn.Module):
             self.train(was_training)
         return ev.compute()
 
+    def visualize_grounding(self, batches, root, evaluator=None, seeds=None, per_annotation_boxes=False, on_degenerate="raise"):
+        """`evaluate_grounding` with an evaluator that keeps the per-description boxes, then the box files of
+        scripts/visualize_grounding.py under `root` (d3net_amd.visualize.visualize_grounding: <root>/<scene>/gt-<object>.ply and
+        pred-<object>-<ann>.ply; the boxes go from the evaluator's device records to the writer without a read-back).  The boxes
+        are the last seed's; on_degenerate="skip" drops a box with a zero extent or a non-finite corner (an untrained listener can
+        pick an empty proposal slot) instead of raising.  Modes 2 and 3.  -> (the evaluation's dict, the list of paths written)."""
+        from .grounding_eval import GroundingEvaluator
+        from .visualize import visualize_grounding
+        if self.mode not in (2, 3):
+            raise NotImplementedError("visualize_grounding needs the detector and the listener (modes 2 and 3), this is mode %d" % self.mode)
+        store = self._description_store("visualize_grounding")
+        ev = evaluator
+        if ev is None:
+            ev = GroundingEvaluator(use_lang_classifier=self.use_lang_classifier, keep_predictions=True, device=next(self.parameters()).device)
+        elif not ev.keep_predictions:
+            raise ValueError("visualize_grounding: the evaluator must be constructed with keep_predictions=True")
+        result = self.evaluate_grounding(batches, evaluator=ev, seeds=seeds)
+        return result, visualize_grounding(ev.device_predictions(store), root, per_annotation_boxes=per_annotation_boxes,
+                                           on_degenerate=on_degenerate)
+
     # --------------------------------------------------------------------------------------------- leaderboard writers
     def _feed_only(self, data_dict):
         """`detector.feed` alone, as the benchmark writers call it (benchmark_captioning.py:148, benchmark_grounding.py:119): no

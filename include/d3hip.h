@@ -1125,6 +1125,30 @@ int d3_caption_inputs_fwd(const float *base, const float *edge, const float *adj
 int d3_caption_inputs_bwd(const float *g_obj, const float *g_target, const long long *target_ids, const int *nbr, int N, int per_scene,
                           int K, int L, int F, float *d_base, float *d_edge, void *stream);
 
+/* ---- box wireframes as PLY text (csrc/visualize.hip, driven by d3net_amd.visualize) ---------------------------------------
+ * In place of write_bbox / write_ply of scripts/visualize_grounding.py:20-168 (scripts/visualize_captioning.py:20-168 is the same
+ * code): per box the 12 x 11 x 10 = 1320 vertices of the twelve-cylinder wireframe, in the reference's order (edge, stack, slice),
+ * and their text lines.  All pointers but ring20 are device memory; ring20 is HOST memory, 20 doubles: 0.03 * cos(i2 * 2 pi / 10)
+ * for i2 = 0 .. 9, then the sines, from the host's libm (create_cylinder_mesh, :81-82), so that the bytes do not depend on the
+ * device's trigonometry.  corners (M,8,3) float64 (a float32 box widened); min / max over the 8 corners is taken first, as :150-151.
+ * Limits: every coordinate finite with |c| < 1e5, every extent's float32 square a normal positive number (the reference divides by
+ * its root: a zero extent makes it print `nan nan nan`).  A box outside them is not written: status[0] |= 1 (coordinate) or 2
+ * (extent) or 4 (mode outside {0, 1}), status[1] = min(status[1], box index); the caller sets status to {0, INT_MAX}.
+ * d3_box_wire_limits: vertices per box (1320), the byte stride of a box's text (73920), the byte stride of a d3_format_f6 value (24).
+ * d3_box_wire_verts : verts (M,1320,3) float64, one thread per vertex (create_cylinder_mesh, :75-106, for the 12 edges of :126-141).
+ * d3_box_wire_text  : modes (M) int32, 0 = GT (colour `0 255 0`), 1 = prediction (`0 0 255`), :152-156.  text + b * stride receives
+ *   box b's 1320 lines "{:f} {:f} {:f} r g b\n" (:39-40) back to back, nbytes[b] their length (0 for a refused box); the bytes of
+ *   the slot behind nbytes[b], up to the next multiple of 4, are zeroed, the rest is left as it was.  One workgroup per box.
+ * d3_format_f6      : the formatter alone: text + i * 24 receives "{:f}".format(values[i]) -- the exact binary value rounded
+ *   half-to-even at six decimals, `-0.000000` for negatives that round to zero, nan / inf / -inf -- and lens[i] its length;
+ *   a finite |value| >= 1e15 is refused: lens[i] = -1, *status |= 1 (status: one device int32).
+ * M outside [1, 2^20], n outside [1, 2^30]: D3_ERR_RANGE before any launch.  No workspace. */
+int d3_box_wire_limits(int *verts_per_box, int *text_stride, int *f6_stride);
+int d3_box_wire_verts(const double *corners, int M, const double *ring20, double *verts, int *status, void *stream);
+int d3_box_wire_text(const double *corners, const int *modes, int M, const double *ring20, char *text, int *nbytes, int *status,
+                     void *stream);
+int d3_format_f6(const double *values, long long n, char *text, int *lens, int *status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
