@@ -1,9 +1,12 @@
-"""AdamW over every parameter tensor of a group in ONE launch (csrc/heads.hip: adamw_kernel).
+"""AdamW, Adam and SGD over every parameter tensor of a group in ONE launch (csrc/heads.hip: adamw_kernel; csrc/optim.hip:
+adam_kernel, sgd_kernel).
 
-Same update as `torch.optim.AdamW` (decoupled weight decay, bias-corrected moments, no amsgrad / maximize), which the
-reference configures through Lightning (model/pipeline.py:738-757); `torch.optim.AdamW(fused=True)` issues one
-multi-tensor launch per ~30 tensors (8 launches, 0.27 ms for the detector's ~300 tensors), this one issues one.
-A device table of (param, grad, exp_avg, exp_avg_sq) pointers is kept per group.  Per step the host only collects the
+Same updates as `torch.optim.AdamW` (decoupled weight decay, bias-corrected moments, no amsgrad / maximize), `torch.optim.Adam`
+(the same moments, L2 weight decay added to the gradient) and `torch.optim.SGD` (momentum, L2 weight decay, no dampening /
+nesterov / maximize), which the reference builds by `train.optim.classname` and configures through Lightning
+(model/pipeline.py:738-757, model/pointgroup.py:372-384); `torch.optim.AdamW(fused=True)` issues one multi-tensor launch per ~30
+tensors (8 launches, 0.27 ms for the detector's ~300 tensors), these issue one.
+A device table of (param, grad, state, state) pointers is kept per group.  Per step the host only collects the
 gradient addresses (the native U-Net executor keeps its flat gradient buffer, the few head gradients are re-allocated by
 `zero_grad(set_to_none=True)`); when any of them moved, the address column is refreshed through a pinned staging buffer
 (one asynchronous 10 KB copy, no synchronisation).
@@ -13,7 +16,11 @@ tensor has received): ScoreNet / `score_linear` only start receiving gradients o
 (`epoch > prepare_epochs`, model/pointgroup.py:332) and must then start at t = 1, not at the backbone's t.  The tensors of a
 table are ordered by their step count, so tensors with equal counts ("cohorts") own a contiguous range of the block map and
 get one launch with their own bias corrections -- one launch in the steady state.  `state_dict()` carries
-`state[p]["step"]`, so checkpoints move to and from `torch.optim.AdamW` in both directions."""
+`state[p]["step"]`, so checkpoints move to and from `torch.optim.AdamW` / `torch.optim.Adam` in both directions.
+
+SGD keeps no step count: its cohorts are "owns a momentum buffer" and "first update" (`buf = g'`, as the library clones the
+gradient into the new buffer) -- two launches on the step where late tensors join, after which the two ranges are one cohort
+again; without momentum there is no buffer, no state and one cohort."""
 import math
 import operator
 
@@ -28,93 +35,76 @@ _DATA_PTR = operator.methodcaller("data_ptr")
 _GRAD = operator.attrgetter("grad")
 
 
-class FusedAdamW(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
-        self._tables = {}
+class _FusedTable(torch.optim.Optimizer):
+    """The table machinery the three optimizers share: the pointer table and block map of a group (`_build`), its reuse and the
+    refresh of moved gradient addresses through a ring of pinned buffers (`_table`), cohort ordering, `_flush_steps`.
+    A subclass names its state tensors (`_slots`: table columns 2..), the cohort a tensor belongs to (`_key`) and launches."""
 
     RING = 4   # pinned staging slots per group: an address refresh never rewrites a buffer whose copy may still be queued
 
+    def __init__(self, params, defaults):
+        super().__init__(params, defaults)
+        self._tables = {}
+
+    def _slots(self, group):
+        """names of the per-parameter state tensors whose addresses fill table columns 2.."""
+        raise NotImplementedError
+
+    def _key(self, p, slots):
+        """cohort of a tensor (an int; larger first): tensors with equal keys share a launch"""
+        raise NotImplementedError
+
     def _flush_steps(self):
         """cohort step counters of the cached tables -> state[p]["step"] (python ints)"""
-        for tb in self._tables.values():
-            for t, lo, hi, _b0, _nb in tb.get("cohorts", ()):
-                for p in tb["plist"][lo:hi]:
-                    self.state[p]["step"] = t
-
-    def state_dict(self):
-        """torch.optim.AdamW's layout: per-parameter `step` (a float32 scalar tensor), `exp_avg`, `exp_avg_sq`.  The returned
-        per-parameter dicts are COPIES: `Optimizer.state_dict()` hands out the live `self.state[p]` objects, and this class keeps
-        python-int step counts there (ADVICE r3: converting in place also rewrote the dict already returned)."""
-        self._flush_steps()
-        sd = super().state_dict()
-        sd["state"] = {k: (dict(st, step=torch.tensor(float(st["step"]))) if "step" in st and not torch.is_tensor(st["step"]) else dict(st))
-                       for k, st in sd["state"].items()}
-        return sd
-
-    def load_state_dict(self, state_dict):
-        """moments are replaced: the cached device tables (which hold their addresses) are dropped; the step counts come from
-        the checkpoint: torch.optim.AdamW's per-parameter `state[p]["step"]`, or -- checkpoints written by the first
-        version of this class -- one per-group `step` applied to every tensor that has moments"""
-        super().load_state_dict(state_dict)
-        self._tables = {}
-        for group in self.param_groups:
-            legacy = group.pop("step", None)
-            for p in group["params"]:
-                st = self.state.get(p)
-                if st is None or "exp_avg" not in st:
-                    continue
-                if "step" in st:
-                    st["step"] = int(st["step"])
-                elif legacy is not None:
-                    st["step"] = int(legacy)
 
     def __setstate__(self, state):
         super().__setstate__(state)
         self._tables = {}
 
-    @staticmethod
-    def _validate(p):
+    @classmethod
+    def _validate(cls, p):
         g = p.grad
         if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() and g.is_contiguous()
                 and g.dtype == torch.float32 and not g.is_sparse and g.device == p.device):
-            raise RuntimeError("FusedAdamW: contiguous fp32 device parameters and gradients only")
+            raise RuntimeError("%s: contiguous fp32 device parameters and gradients only" % cls.__name__)
 
-    def _build(self, gi, plist):
+    def _build(self, gi, group, plist):
         for p in plist:
             self._validate(p)
+        slots = self._slots(group)
+        key = {p: self._key(p, slots) for p in plist}
         # equal step counts adjacent (most-stepped first; stable): one contiguous block-map range, one launch per cohort
-        plist.sort(key=lambda p: -int(self.state[p].get("step", 0)))
+        plist.sort(key=lambda p: -key[p])
         dev = plist[0].device
-        fresh = [p for p in plist if "exp_avg" not in self.state[p]]
+        fresh = [p for p in plist if slots and self.state[p].get(slots[0]) is None]
         if fresh:   # moments of the tensors seen for the first time: one flat buffer
-            flat = torch.zeros(2 * sum(p.numel() for p in fresh), dtype=torch.float32, device=dev)
+            flat = torch.zeros(len(slots) * sum(p.numel() for p in fresh), dtype=torch.float32, device=dev)
             o = 0
             for p in fresh:
                 n = p.numel()
-                self.state[p]["exp_avg"] = flat[o:o + n].view_as(p)
-                self.state[p]["exp_avg_sq"] = flat[o + n:o + 2 * n].view_as(p)
-                o += 2 * n
+                for s in slots:
+                    self.state[p][s] = flat[o:o + n].view_as(p)
+                    o += n
         chunk = _lib.lib().d3_adamw_chunk()
         ring = [torch.empty((len(plist), 4), dtype=torch.int64).pin_memory() for _ in range(self.RING)]
         host = ring[0]
         hv = host.numpy()
         hv[:, 0] = [p.data_ptr() for p in plist]
         hv[:, 1] = [p.grad.data_ptr() for p in plist]
-        hv[:, 2] = [self.state[p]["exp_avg"].data_ptr() for p in plist]
-        hv[:, 3] = [self.state[p]["exp_avg_sq"].data_ptr() for p in plist]
+        hv[:, 2:] = 0
+        for k, s in enumerate(slots):
+            hv[:, 2 + k] = [self.state[p][s].data_ptr() for p in plist]
         numel = np.array([p.numel() for p in plist], dtype=np.int32)
         blocks = np.array([(t, c) for t, n in enumerate(numel) for c in range((int(n) + chunk - 1) // chunk)], dtype=np.int32)
         nblk = [(int(n) + chunk - 1) // chunk for n in numel]
         cohorts, lo, b0 = [], 0, 0      # [step count, first tensor, end tensor, first block, blocks]
         for i in range(1, len(plist) + 1):
-            if i == len(plist) or int(self.state[plist[i]].get("step", 0)) != int(self.state[plist[lo]].get("step", 0)):
+            if i == len(plist) or key[plist[i]] != key[plist[lo]]:
                 nb = sum(nblk[lo:i])
-                cohorts.append([int(self.state[plist[lo]].get("step", 0)), lo, i, b0, nb])
+                cohorts.append([key[plist[lo]], lo, i, b0, nb])
                 lo, b0 = i, b0 + nb
         tb = {"pptr": [p.data_ptr() for p in plist], "gptr": hv[:, 1].tolist(), "host": host, "ring": ring, "slot": 0, "cohorts": cohorts,
-              "mptr": [self.state[p]["exp_avg"].data_ptr() for p in plist],
-              "nblocks": int(blocks.shape[0]), "ptrs": host.to(dev), "numel": torch.from_numpy(numel).to(dev),
+              "slots": slots, "nblocks": int(blocks.shape[0]), "ptrs": host.to(dev), "numel": torch.from_numpy(numel).to(dev),
               "blocks": torch.from_numpy(blocks.reshape(-1)).to(dev), "device": dev}
         self._tables[gi] = tb
         return tb
@@ -147,10 +137,60 @@ class FusedAdamW(torch.optim.Optimizer):
             return {"nblocks": 0, "plist": [], "ngrad": -1}
         self._flush_steps()            # the table being replaced owns the current counts
         self._tables.pop(gi, None)
-        tb = self._build(gi, plist)
+        tb = self._build(gi, group, plist)
         tb["plist"] = plist
         tb["ngrad"] = len(plist)
         return tb
+
+
+def _refuse(cls, unsupported):
+    if unsupported:
+        raise ValueError("%s: %s not supported (the single-launch kernels implement the library's defaults only)"
+                         % (cls.__name__, ", ".join(sorted(unsupported))))
+
+
+class _FusedMoments(_FusedTable):
+    """Adam-family state: exp_avg, exp_avg_sq and a per-parameter step count; `_ENTRY` is the library call of the rule."""
+    _ENTRY = None
+
+    def _slots(self, group):
+        return ("exp_avg", "exp_avg_sq")
+
+    def _key(self, p, slots):
+        return int(self.state[p].get("step", 0))
+
+    def _flush_steps(self):
+        for tb in self._tables.values():
+            for t, lo, hi, _b0, _nb in tb.get("cohorts", ()):
+                for p in tb["plist"][lo:hi]:
+                    self.state[p]["step"] = t
+
+    def state_dict(self):
+        """torch.optim.AdamW's layout: per-parameter `step` (a float32 scalar tensor), `exp_avg`, `exp_avg_sq`.  The returned
+        per-parameter dicts are COPIES: `Optimizer.state_dict()` hands out the live `self.state[p]` objects, and this class keeps
+        python-int step counts there (ADVICE r3: converting in place also rewrote the dict already returned)."""
+        self._flush_steps()
+        sd = super().state_dict()
+        sd["state"] = {k: (dict(st, step=torch.tensor(float(st["step"]))) if "step" in st and not torch.is_tensor(st["step"]) else dict(st))
+                       for k, st in sd["state"].items()}
+        return sd
+
+    def load_state_dict(self, state_dict):
+        """moments are replaced: the cached device tables (which hold their addresses) are dropped; the step counts come from
+        the checkpoint: torch.optim.AdamW's per-parameter `state[p]["step"]`, or -- checkpoints written by the first
+        version of this class -- one per-group `step` applied to every tensor that has moments"""
+        super().load_state_dict(state_dict)
+        self._tables = {}
+        for group in self.param_groups:
+            legacy = group.pop("step", None)
+            for p in group["params"]:
+                st = self.state.get(p)
+                if st is None or "exp_avg" not in st:
+                    continue
+                if "step" in st:
+                    st["step"] = int(st["step"])
+                elif legacy is not None:
+                    st["step"] = int(legacy)
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -158,7 +198,7 @@ class FusedAdamW(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        L = _lib.lib()
+        entry = getattr(_lib.lib(), self._ENTRY)
         for gi, group in enumerate(self.param_groups):
             tb = self._table(gi, group)
             if tb["nblocks"] == 0:
@@ -168,7 +208,100 @@ class FusedAdamW(torch.optim.Optimizer):
                 st = torch.cuda.current_stream().cuda_stream
                 for co in tb["cohorts"]:       # tensors with the same number of updates behind them: one launch
                     co[0] = t = co[0] + 1
-                    check(L.d3_adamw(tb["ptrs"].data_ptr(), tb["numel"].data_ptr(), tb["blocks"].data_ptr() + 8 * co[3], co[4],
-                                     float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]),
-                                     1.0 - b1 ** t, math.sqrt(1.0 - b2 ** t), st), "adamw")
+                    check(entry(tb["ptrs"].data_ptr(), tb["numel"].data_ptr(), tb["blocks"].data_ptr() + 8 * co[3], co[4],
+                                float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]),
+                                1.0 - b1 ** t, math.sqrt(1.0 - b2 ** t), st), self._ENTRY[3:])
         return loss
+
+
+class FusedAdamW(_FusedMoments):
+    _ENTRY = "d3_adamw"
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+
+
+class FusedAdam(_FusedMoments):
+    """torch.optim.Adam (amsgrad = maximize = False) in one launch: FusedAdamW's state and step counts, L2 weight decay
+    (`g + weight_decay * p` enters both moments) instead of the decoupled one.  Checkpoints interchange with torch.optim.Adam."""
+    _ENTRY = "d3_adam"
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, **unsupported):
+        _refuse(type(self), unsupported)      # amsgrad, maximize, ...: refused whatever their value
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+
+    def load_state_dict(self, state_dict):
+        for g in state_dict["param_groups"]:
+            _refuse(type(self), [k for k in ("amsgrad", "maximize", "decoupled_weight_decay") if g.get(k)])
+        super().load_state_dict(state_dict)
+
+
+class FusedSGD(_FusedTable):
+    """torch.optim.SGD (dampening = 0, nesterov = maximize = False) in one launch.  State is `momentum_buffer` alone, as in the
+    library (none at all with momentum 0); a tensor without a buffer -- new, or loaded as `momentum_buffer: None` -- receives
+    the first-update rule `buf = g + weight_decay * p`.  Checkpoints interchange with torch.optim.SGD."""
+
+    def __init__(self, params, lr=1e-3, momentum=0, weight_decay=0, **unsupported):
+        _refuse(type(self), unsupported)      # dampening, nesterov, maximize, amsgrad, ...: refused whatever their value
+        if lr < 0.0 or momentum < 0.0 or weight_decay < 0.0:
+            raise ValueError("FusedSGD: negative lr, momentum or weight_decay")
+        # the three constants are what torch.optim.SGD expects to find in a checkpoint's param_groups
+        super().__init__(params, dict(lr=lr, momentum=momentum, dampening=0, weight_decay=weight_decay, nesterov=False,
+                                      maximize=False))
+
+    def _slots(self, group):
+        return ("momentum_buffer",) if group["momentum"] != 0 else ()
+
+    def _key(self, p, slots):
+        return 0 if slots and self.state[p].get(slots[0]) is None else 1     # 0: first update still to come
+
+    def load_state_dict(self, state_dict):
+        """buffers are replaced: the cached device tables are dropped"""
+        for g in state_dict["param_groups"]:
+            _refuse(type(self), [k for k in ("dampening", "nesterov", "maximize") if g.get(k)])
+        super().load_state_dict(state_dict)
+        self._tables = {}
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        L = _lib.lib()
+        for gi, group in enumerate(self.param_groups):
+            tb = self._tables.get(gi)
+            if tb is not None and tb["slots"] != self._slots(group):      # momentum switched on or off: other table columns
+                del self._tables[gi]
+            tb = self._table(gi, group)
+            if tb["nblocks"] == 0:
+                continue
+            with torch.cuda.device(tb["device"]):
+                st = torch.cuda.current_stream().cuda_stream
+                for co in tb["cohorts"]:       # buffer owners, then the tensors updated for the first time
+                    check(L.d3_sgd(tb["ptrs"].data_ptr(), tb["numel"].data_ptr(), tb["blocks"].data_ptr() + 8 * co[3], co[4],
+                                   float(group["lr"]), float(group["momentum"]), float(group["weight_decay"]), int(co[0] == 0), st),
+                          "sgd")
+            if len(tb["cohorts"]) > 1 or tb["cohorts"][0][0] == 0:      # every tensor owns a buffer now: one cohort, one launch
+                tb["cohorts"] = [[1, 0, len(tb["plist"]), 0, tb["nblocks"]]]
+        return loss
+
+
+_FUSED = {"Adam": FusedAdam, "AdamW": FusedAdamW, "SGD": FusedSGD}
+
+
+def from_config(optim_cfg, params, keys, drop_stale_grads):
+    """The optimizer `train.optim.classname` names (AdamW when the key is absent), as the reference builds it by name
+    (model/pipeline.py:741-748, model/pointgroup.py:375-382).  keys: {classname: the `train.optim` keys that class receives}.
+    Device parameters get the single-launch class, with `drop_stale_grads` as a step pre-hook (the executors' flat gradient
+    buffers outlive zero_grad()); host parameters get the torch.optim class of that name."""
+    name = optim_cfg.get("classname", "AdamW")
+    if name not in keys:
+        raise ValueError("train.optim.classname: %r is not one of %s" % (name, ", ".join(sorted(keys))))
+    kw = {k: optim_cfg[k] for k in keys[name]}
+    if params[0].is_cuda:   # one launch for all tensors (csrc/heads.hip, csrc/optim.hip); same update rule
+        opt = _FUSED[name](params, **kw)
+        opt.register_step_pre_hook(lambda *a: drop_stale_grads())
+    else:
+        opt = getattr(torch.optim, name)(params, **kw)
+    return opt

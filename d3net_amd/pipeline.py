@@ -480,12 +480,11 @@ class PipelineNet(nn.Module):
         return data_dict
 
     def configure_optimizers(self):
-        """AdamW + StepLR(10, 0.8) over the trainable parameters (model/pipeline.py:738-757)"""
+        """`train.optim.classname` (Adam, AdamW -- also when the key is absent -- or SGD) + StepLR(10, 0.8) over the trainable
+        parameters (model/pipeline.py:738-757): Adam / AdamW take lr and weight_decay, SGD lr, momentum and weight_decay"""
+        from .optim import from_config
         params = [p for p in self.parameters() if p.requires_grad]
-        if params[0].is_cuda:   # one launch for all tensors (csrc/heads.hip); same update rule
-            from .optim import FusedAdamW
-            opt = FusedAdamW(params, lr=self.cfg.train.optim.lr, weight_decay=self.cfg.train.optim.weight_decay)
-            opt.register_step_pre_hook(lambda *a: self.detector.drop_stale_grads())
-        else:
-            opt = torch.optim.AdamW(params, lr=self.cfg.train.optim.lr, weight_decay=self.cfg.train.optim.weight_decay)
+        opt = from_config(self.cfg.train.optim, params, {"Adam": ("lr", "weight_decay"), "AdamW": ("lr", "weight_decay"),
+                                                         "SGD": ("lr", "momentum", "weight_decay")},
+                          lambda: self.detector.drop_stale_grads())
         return [opt], [torch.optim.lr_scheduler.StepLR(opt, step_size=10, gamma=0.8)]

@@ -411,6 +411,16 @@ class PointGroup(nn.Module):
             if ex is not None:
                 ex.drop_stale_grads()
 
+    def configure_optimizers(self):
+        """[optimizer], no scheduler (model/pointgroup.py:372-384): `train.optim.classname` Adam takes lr alone, SGD takes lr,
+        momentum and weight_decay.  AdamW (lr, weight_decay; also when the key is absent) is accepted as well: the reference
+        raises for it here although its own conf/pointgroup.yaml names it.  Device parameters get the single-launch classes
+        of d3net_amd.optim with drop_stale_grads() as their step pre-hook."""
+        from .optim import from_config
+        params = [p for p in self.parameters() if p.requires_grad]
+        return [from_config(self.cfg.train.optim, params, {"Adam": ("lr",), "AdamW": ("lr", "weight_decay"),
+                                                           "SGD": ("lr", "momentum", "weight_decay")}, self.drop_stale_grads)]
+
     def zero_grad(self, set_to_none=True):
         """nn.Module.zero_grad; gradients owned by the native executors are marked stale instead of being detached
         one by one (the next backward overwrites them)."""

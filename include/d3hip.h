@@ -507,6 +507,18 @@ int d3_stack_to_batch(const float *feats, const float *crop, const float *scores
 int d3_adamw_chunk(void);
 int d3_adamw(const long long *ptrs, const int *numel, const void *blocks, int nblocks, double lr, double beta1, double beta2,
              double eps, double weight_decay, double bias_correction1, double bias_correction2_sqrt, void *stream);
+/* Adam and SGD steps with the tables of d3_adamw (csrc/optim.hip), one launch per call: the other two optimizers that
+ * `train.optim.classname` names (model/pipeline.py:738-757 for the pipeline, model/pointgroup.py:372-384 for the detector).
+ * d3_adam: torch.optim.Adam with amsgrad = maximize = False; weight decay is L2, added to the gradient (g' = g + wd p)
+ * before the moments; table columns (param, grad, exp_avg, exp_avg_sq).
+ * d3_sgd: torch.optim.SGD with dampening = 0, nesterov = maximize = False; table columns (param, grad, momentum_buffer,
+ * unused).  momentum == 0: no buffer is read or written.  first != 0: the launched range receives its first update,
+ * buf = g' (the buffer is written, never read); first == 0: buf = momentum buf + g'.  first != 0 with momentum == 0:
+ * D3_ERR_ARG. */
+int d3_adam(const long long *ptrs, const int *numel, const void *blocks, int nblocks, double lr, double beta1, double beta2,
+            double eps, double weight_decay, double bias_correction1, double bias_correction2_sqrt, void *stream);
+int d3_sgd(const long long *ptrs, const int *numel, const void *blocks, int nblocks, double lr, double momentum,
+           double weight_decay, int first, void *stream);
 /* out[idx[s], :] += g[s, :] (out zero-filled by the caller): backward of the cluster feature gather
  * (model/pointgroup.py:130); deterministic when every output row receives at most two addends, as it does there */
 int d3_scatter_add_rows(const float *g, const int64_t *idx, float *out, long long S, int C, void *stream);
