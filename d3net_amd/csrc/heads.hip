@@ -949,9 +949,20 @@ extern "C" int d3_stack_to_batch(const float *feats, const float *crop, const fl
 // a device table holds (param, grad, exp_avg, exp_avg_sq) pointers per tensor and a block map (tensor, chunk) per
 // workgroup; HBM bound: 4 reads + 3 writes of 4 B per element.
 #define ADAMW_CHUNK 4096
+// CTL: the step runs behind d3_grad_clip_finish (optim.hip), as torch.nn.utils.clip_grad_norm_ runs before the library's
+// step: every workgroup returns before its first store when the record says skip (a uniform branch), otherwise each
+// gradient element is used as g * coef -- one fp32 multiply, what clip_grad_norm_'s in-place mul_ would have left in
+// memory (the build runs with -ffp-contract=off); the gradient in memory is not rewritten.  CTL = false never reads ctl.
+template <bool CTL>
 __global__ __launch_bounds__(256) void adamw_kernel(const long long *__restrict__ ptrs, const int *__restrict__ numel,
                                                    const int2 *__restrict__ blocks, float step_size, float beta2, float omb1,
-                                                   float omb2, float eps, float lr_wd, float bc2_sqrt) {
+                                                   float omb2, float eps, float lr_wd, float bc2_sqrt,
+                                                   const d3_clip_ctl *__restrict__ ctl) {
+    float coef = 1.f;
+    if (CTL) {
+        if (ctl->skip & ctl->enforce) return;
+        coef = ctl->coef;
+    }
     const int2 bm = blocks[blockIdx.x];
     float *p = (float *)ptrs[bm.x * 4 + 0];
     const float *g = (const float *)ptrs[bm.x * 4 + 1];
@@ -968,26 +979,42 @@ __global__ __launch_bounds__(256) void adamw_kernel(const long long *__restrict_
     for (int j = 0; j < 16; j++) {
         const int i = base + j * 256 + threadIdx.x;
         if (i < n) {
+            const float gc = CTL ? gv[j] * coef : gv[j];
             float pp = pv[j] - lr_wd * pv[j];
-            const float mm = mv[j] + omb1 * (gv[j] - mv[j]);
-            const float v2 = beta2 * vv[j] + omb2 * gv[j] * gv[j];
+            const float mm = mv[j] + omb1 * (gc - mv[j]);
+            const float v2 = beta2 * vv[j] + omb2 * gc * gc;
             const float denom = sqrtf(v2) / bc2_sqrt + eps;
             pp -= step_size * mm / denom;
             p[i] = pp; m[i] = mm; v[i] = v2;
         }
     }
 }
+template <bool CTL>
+static int adamw_launch(const long long *ptrs, const int *numel, const void *blocks, int nblocks, double lr, double beta1,
+                        double beta2, double eps, double weight_decay, double bias_correction1, double bias_correction2_sqrt,
+                        const void *ctl, void *stream) {
+    D3_CLEAR();
+    if (nblocks <= 0) return 0;
+    if (CTL && !ctl) return D3_ERR_ARG;
+    // scalars derived in double, as the library does before it narrows them
+    adamw_kernel<CTL><<<nblocks, 256, 0, d3_stream(stream)>>>(ptrs, numel, (const int2 *)blocks, (float)(lr / bias_correction1),
+                                                             (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps,
+                                                             (float)(lr * weight_decay), (float)bias_correction2_sqrt,
+                                                             (const d3_clip_ctl *)ctl);
+    D3_LAUNCH_CHECK();
+    return 0;
+}
 extern "C" int d3_adamw(const long long *ptrs, const int *numel, const void *blocks, int nblocks, double lr, double beta1,
                         double beta2, double eps, double weight_decay, double bias_correction1, double bias_correction2_sqrt,
                         void *stream) {
-    D3_CLEAR();
-    if (nblocks <= 0) return 0;
-    // scalars derived in double, as the library does before it narrows them
-    adamw_kernel<<<nblocks, 256, 0, d3_stream(stream)>>>(ptrs, numel, (const int2 *)blocks, (float)(lr / bias_correction1),
-                                                        (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps,
-                                                        (float)(lr * weight_decay), (float)bias_correction2_sqrt);
-    D3_LAUNCH_CHECK();
-    return 0;
+    return adamw_launch<false>(ptrs, numel, blocks, nblocks, lr, beta1, beta2, eps, weight_decay, bias_correction1,
+                               bias_correction2_sqrt, nullptr, stream);
+}
+extern "C" int d3_adamw_clipped(const long long *ptrs, const int *numel, const void *blocks, int nblocks, double lr, double beta1,
+                                double beta2, double eps, double weight_decay, double bias_correction1,
+                                double bias_correction2_sqrt, const void *ctl, void *stream) {
+    return adamw_launch<true>(ptrs, numel, blocks, nblocks, lr, beta1, beta2, eps, weight_decay, bias_correction1,
+                              bias_correction2_sqrt, ctl, stream);
 }
 extern "C" int d3_adamw_chunk(void) { return ADAMW_CHUNK; }
 

@@ -20,7 +20,22 @@ get one launch with their own bias corrections -- one launch in the steady state
 
 SGD keeps no step count: its cohorts are "owns a momentum buffer" and "first update" (`buf = g'`, as the library clones the
 gradient into the new buffer) -- two launches on the step where late tensors join, after which the two ranges are one cohort
-again; without momentum there is no buffer, no state and one cohort."""
+again; without momentum there is no buffer, no state and one cohort.
+
+Gradient clipping (`max_grad_norm=`; None: off, and the step calls exactly what it called before the option existed).  What
+`torch.nn.utils.clip_grad_norm_` -- Lightning's `Trainer(gradient_clip_val=...)` for the reference -- does in front of the step
+happens inside it: one `d3_grad_sumsq` launch per group over the group's table, one `d3_grad_clip_finish` launch that leaves
+(norm, coef, skip, nskipped) in a 32-byte device record, and the `_clipped` update entries, which use `g * coef`.  The norm is
+global over all groups, over the tensors that have a gradient this step (after the `drop_stale_grads` pre-hook), accumulated in
+double in a fixed order; `math.inf` measures without clipping.  Differences from torch, both deliberate:
+* `p.grad` is NOT rewritten: it keeps its unclipped value after `step()` (the write pass is what the native path saves);
+* `skip_nonfinite=True` (default): when the norm is inf or NaN the update kernels store nothing -- parameters and every state
+  tensor stay bit-unchanged -- and no value is read back to the host.  THE PER-PARAMETER STEP COUNTS STILL ADVANCE on such a
+  step (they live on the host): the next finite step is `torch.optim`'s update with `state[p]["step"]` one higher, and an SGD
+  tensor whose first update was skipped owns a zero momentum buffer, which gives the first-update rule anyway.
+  `skip_nonfinite=False` lets the NaN propagate as it does through torch.
+Neither option is a `param_groups` entry or part of `state_dict()`: checkpoints interchange with `torch.optim.*` as before.
+With several ranks the gradients are identical after the all-reduce, so each rank's norm is the global one: no collective."""
 import math
 import operator
 
@@ -38,13 +53,79 @@ _GRAD = operator.attrgetter("grad")
 class _FusedTable(torch.optim.Optimizer):
     """The table machinery the three optimizers share: the pointer table and block map of a group (`_build`), its reuse and the
     refresh of moved gradient addresses through a ring of pinned buffers (`_table`), cohort ordering, `_flush_steps`.
-    A subclass names its state tensors (`_slots`: table columns 2..), the cohort a tensor belongs to (`_key`) and launches."""
+    A subclass names its state tensors (`_slots`: table columns 2..), the cohort a tensor belongs to (`_key`) and launches.
+
+    `max_grad_norm` (None: off; a positive float or math.inf) and `skip_nonfinite` are attributes, not `param_groups` entries
+    and not in `state_dict()`.  With `max_grad_norm` set, `_measure` puts the global gradient norm, the clipping coefficient
+    and the skip flag into a device record that the `_clipped` update entries read; `p.grad` keeps its unclipped value.
+    A step skipped for a non-finite norm leaves parameters and state tensors bit-unchanged BUT STILL ADVANCES THE
+    PER-PARAMETER STEP COUNTS: they live on the host and nothing is read back.  The next finite step is therefore
+    `torch.optim`'s update with `state[p]["step"]` one higher."""
 
     RING = 4   # pinned staging slots per group: an address refresh never rewrites a buffer whose copy may still be queued
 
-    def __init__(self, params, defaults):
+    def __init__(self, params, defaults, max_grad_norm=None, skip_nonfinite=True):
+        if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
+            raise ValueError("%s: max_grad_norm is None (off), a positive float or math.inf" % type(self).__name__)
         super().__init__(params, defaults)
         self._tables = {}
+        # attributes, not param_groups entries: state_dict() stays the torch.optim layout
+        self.max_grad_norm = max_grad_norm
+        self.skip_nonfinite = skip_nonfinite
+        self._ctl = self._partials = None
+
+    def __getstate__(self):
+        return dict(super().__getstate__(), max_grad_norm=self.max_grad_norm, skip_nonfinite=self.skip_nonfinite)
+
+    def _record(self):
+        """the d3_clip_ctl record (include/d3hip.h) as 8 int32 words on the parameters' device; `enforce` follows `skip_nonfinite`"""
+        enforce = int(bool(self.skip_nonfinite))
+        if self._ctl is None:
+            dev = self.param_groups[0]["params"][0].device
+            self._ctl = torch.tensor([0, 0, 0, 0, enforce, 0, 0, 0], dtype=torch.int32, device=dev)
+            self._enforce = enforce
+        elif self._enforce != enforce:
+            self._ctl[4] = enforce
+            self._enforce = enforce
+        return self._ctl
+
+    def last_grad_norm(self):
+        """0-d float32 device tensor ALIASING the record's `norm`: the total gradient 2-norm the last clipped step()
+        measured, before clipping (0 before the first).  No synchronisation; every step() rewrites it in place."""
+        return self._record()[0:1].view(torch.float32).reshape(())
+
+    def nonfinite_steps(self):
+        """number of steps whose gradient norm was not finite, over the optimizer's life (one small read-back)"""
+        return 0 if self._ctl is None else int(self._ctl[3].item())
+
+    def _resolve(self):
+        """every group's table, after the step pre-hooks: [(group, table)] of the groups that have gradients"""
+        tables = [(group, self._table(gi, group)) for gi, group in enumerate(self.param_groups)]
+        return [(group, tb) for group, tb in tables if tb["nblocks"]]
+
+    def _measure(self, tables):
+        """torch.nn.utils.clip_grad_norm_ over every tensor of `tables`: one d3_grad_sumsq per group into one partials
+        buffer, one d3_grad_clip_finish; -> the record's address for the _clipped entries (None: clipping is off)"""
+        if self.max_grad_norm is None or not tables:
+            return None
+        L = _lib.lib()
+        ctl = self._record()
+        dev = ctl.device
+        total = sum(tb["nblocks"] for _g, tb in tables)
+        if self._partials is None or self._partials.numel() < total:
+            self._partials = torch.empty(total, dtype=torch.float64, device=dev)
+        with torch.cuda.device(dev):
+            st = torch.cuda.current_stream().cuda_stream
+            o = 0
+            for _g, tb in tables:
+                if tb["device"] != dev:
+                    raise RuntimeError("%s: max_grad_norm needs every group on one device" % type(self).__name__)
+                check(L.d3_grad_sumsq(tb["ptrs"].data_ptr(), tb["numel"].data_ptr(), tb["blocks"].data_ptr(), tb["nblocks"],
+                                      self._partials.data_ptr() + 8 * o, st), "grad_sumsq")
+                o += tb["nblocks"]
+            check(L.d3_grad_clip_finish(self._partials.data_ptr(), total, float(self.max_grad_norm), ctl.data_ptr(), st),
+                  "grad_clip_finish")
+        return ctl.data_ptr()
 
     def _slots(self, group):
         """names of the per-parameter state tensors whose addresses fill table columns 2.."""
@@ -60,6 +141,9 @@ class _FusedTable(torch.optim.Optimizer):
     def __setstate__(self, state):
         super().__setstate__(state)
         self._tables = {}
+        self.__dict__.setdefault("max_grad_norm", None)
+        self.__dict__.setdefault("skip_nonfinite", True)
+        self._ctl = self._partials = None
 
     @classmethod
     def _validate(cls, p):
@@ -198,27 +282,27 @@ class _FusedMoments(_FusedTable):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        entry = getattr(_lib.lib(), self._ENTRY)
-        for gi, group in enumerate(self.param_groups):
-            tb = self._table(gi, group)
-            if tb["nblocks"] == 0:
-                continue
+        tables = self._resolve()
+        ctl = self._measure(tables)
+        name = self._ENTRY if ctl is None else self._ENTRY + "_clipped"
+        entry, tail = getattr(_lib.lib(), name), (() if ctl is None else (ctl,))
+        for group, tb in tables:
             b1, b2 = group["betas"]
             with torch.cuda.device(tb["device"]):
                 st = torch.cuda.current_stream().cuda_stream
                 for co in tb["cohorts"]:       # tensors with the same number of updates behind them: one launch
-                    co[0] = t = co[0] + 1
+                    co[0] = t = co[0] + 1      # also on a step the record makes the kernels skip: nothing is read back
                     check(entry(tb["ptrs"].data_ptr(), tb["numel"].data_ptr(), tb["blocks"].data_ptr() + 8 * co[3], co[4],
                                 float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]),
-                                1.0 - b1 ** t, math.sqrt(1.0 - b2 ** t), st), self._ENTRY[3:])
+                                1.0 - b1 ** t, math.sqrt(1.0 - b2 ** t), *tail, st), name[3:])
         return loss
 
 
 class FusedAdamW(_FusedMoments):
     _ENTRY = "d3_adamw"
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=None, skip_nonfinite=True):
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay), max_grad_norm, skip_nonfinite)
 
 
 class FusedAdam(_FusedMoments):
@@ -226,9 +310,10 @@ class FusedAdam(_FusedMoments):
     (`g + weight_decay * p` enters both moments) instead of the decoupled one.  Checkpoints interchange with torch.optim.Adam."""
     _ENTRY = "d3_adam"
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, **unsupported):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, max_grad_norm=None, skip_nonfinite=True,
+                 **unsupported):
         _refuse(type(self), unsupported)      # amsgrad, maximize, ...: refused whatever their value
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay), max_grad_norm, skip_nonfinite)
 
     def load_state_dict(self, state_dict):
         for g in state_dict["param_groups"]:
@@ -241,13 +326,13 @@ class FusedSGD(_FusedTable):
     library (none at all with momentum 0); a tensor without a buffer -- new, or loaded as `momentum_buffer: None` -- receives
     the first-update rule `buf = g + weight_decay * p`.  Checkpoints interchange with torch.optim.SGD."""
 
-    def __init__(self, params, lr=1e-3, momentum=0, weight_decay=0, **unsupported):
+    def __init__(self, params, lr=1e-3, momentum=0, weight_decay=0, max_grad_norm=None, skip_nonfinite=True, **unsupported):
         _refuse(type(self), unsupported)      # dampening, nesterov, maximize, amsgrad, ...: refused whatever their value
         if lr < 0.0 or momentum < 0.0 or weight_decay < 0.0:
             raise ValueError("FusedSGD: negative lr, momentum or weight_decay")
         # the three constants are what torch.optim.SGD expects to find in a checkpoint's param_groups
         super().__init__(params, dict(lr=lr, momentum=momentum, dampening=0, weight_decay=weight_decay, nesterov=False,
-                                      maximize=False))
+                                      maximize=False), max_grad_norm, skip_nonfinite)
 
     def _slots(self, group):
         return ("momentum_buffer",) if group["momentum"] != 0 else ()
@@ -268,20 +353,21 @@ class FusedSGD(_FusedTable):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        L = _lib.lib()
         for gi, group in enumerate(self.param_groups):
             tb = self._tables.get(gi)
             if tb is not None and tb["slots"] != self._slots(group):      # momentum switched on or off: other table columns
                 del self._tables[gi]
-            tb = self._table(gi, group)
-            if tb["nblocks"] == 0:
-                continue
+        tables = self._resolve()
+        ctl = self._measure(tables)
+        name = "d3_sgd" if ctl is None else "d3_sgd_clipped"
+        entry, tail = getattr(_lib.lib(), name), (() if ctl is None else (ctl,))
+        for group, tb in tables:
             with torch.cuda.device(tb["device"]):
                 st = torch.cuda.current_stream().cuda_stream
                 for co in tb["cohorts"]:       # buffer owners, then the tensors updated for the first time
-                    check(L.d3_sgd(tb["ptrs"].data_ptr(), tb["numel"].data_ptr(), tb["blocks"].data_ptr() + 8 * co[3], co[4],
-                                   float(group["lr"]), float(group["momentum"]), float(group["weight_decay"]), int(co[0] == 0), st),
-                          "sgd")
+                    check(entry(tb["ptrs"].data_ptr(), tb["numel"].data_ptr(), tb["blocks"].data_ptr() + 8 * co[3], co[4],
+                                float(group["lr"]), float(group["momentum"]), float(group["weight_decay"]), int(co[0] == 0),
+                                *tail, st), name[3:])
             if len(tb["cohorts"]) > 1 or tb["cohorts"][0][0] == 0:      # every tensor owns a buffer now: one cohort, one launch
                 tb["cohorts"] = [[1, 0, len(tb["plist"]), 0, tb["nblocks"]]]
         return loss
@@ -294,14 +380,25 @@ def from_config(optim_cfg, params, keys, drop_stale_grads):
     """The optimizer `train.optim.classname` names (AdamW when the key is absent), as the reference builds it by name
     (model/pipeline.py:741-748, model/pointgroup.py:375-382).  keys: {classname: the `train.optim` keys that class receives}.
     Device parameters get the single-launch class, with `drop_stale_grads` as a step pre-hook (the executors' flat gradient
-    buffers outlive zero_grad()); host parameters get the torch.optim class of that name."""
+    buffers outlive zero_grad()); host parameters get the torch.optim class of that name.
+    `train.optim.max_grad_norm` (absent, None or 0: off) is what Lightning's `Trainer(gradient_clip_val=...)` is to the reference:
+    the global 2-norm of all gradients is clipped to it -- inside the single-launch step on the device (with
+    `train.optim.skip_nonfinite`, default true: a step whose norm is not finite is dropped), by a step pre-hook calling
+    `torch.nn.utils.clip_grad_norm_` on the host."""
     name = optim_cfg.get("classname", "AdamW")
     if name not in keys:
         raise ValueError("train.optim.classname: %r is not one of %s" % (name, ", ".join(sorted(keys))))
     kw = {k: optim_cfg[k] for k in keys[name]}
+    clip = optim_cfg.get("max_grad_norm") or None
     if params[0].is_cuda:   # one launch for all tensors (csrc/heads.hip, csrc/optim.hip); same update rule
+        if clip is not None:
+            kw.update(max_grad_norm=float(clip), skip_nonfinite=bool(optim_cfg.get("skip_nonfinite", True)))
         opt = _FUSED[name](params, **kw)
         opt.register_step_pre_hook(lambda *a: drop_stale_grads())
     else:
         opt = getattr(torch.optim, name)(params, **kw)
+        if clip is not None:
+            def clip_hook(*_a):     # a step pre-hook returns None (or new arguments), never the norm
+                torch.nn.utils.clip_grad_norm_(params, float(clip))
+            opt.register_step_pre_hook(clip_hook)
     return opt

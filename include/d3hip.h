@@ -519,6 +519,46 @@ int d3_adam(const long long *ptrs, const int *numel, const void *blocks, int nbl
             double eps, double weight_decay, double bias_correction1, double bias_correction2_sqrt, void *stream);
 int d3_sgd(const long long *ptrs, const int *numel, const void *blocks, int nblocks, double lr, double momentum,
            double weight_decay, int first, void *stream);
+/* Global gradient-norm clipping and the non-finite skip for the three steps above, over their own tables: what
+ * torch.nn.utils.clip_grad_norm_ does in front of a torch.optim step, and what Lightning's `gradient_clip_val` switches on
+ * for the reference.  Two launches produce the control record; the _clipped steps read it and leave the gradients in
+ * memory as they are.
+ * The record (32 bytes of device memory, zero-filled by the caller before its first use):
+ *   norm      the total 2-norm of the gradients before clipping (double accumulation, narrowed once)
+ *   coef      torch.nn.utils.clip_grad_norm_'s coefficient in fp32: min(1.0f, max_norm / (norm + 1e-6f)); exactly 1 for
+ *             max_norm = +inf and a finite norm (measure only); NaN when norm is NaN
+ *   skip      1 when norm is not finite, else 0
+ *   nskipped  incremented by every d3_grad_clip_finish whose skip is 1: cumulative
+ *   enforce   written by the HOST alone: non-zero makes the _clipped steps return before their first store while skip
+ *             is 1; zero makes them ignore skip (the non-finite coefficient then propagates, as it does through torch) */
+typedef struct d3_clip_ctl {
+    float norm;
+    float coef;
+    int skip;
+    int nskipped;
+    int enforce;
+    int reserved[3];
+} d3_clip_ctl;
+/* d3_grad_sumsq: the first half of torch.nn.utils.clip_grad_norm_'s norm.  partials[b] = sum of grad^2 (table column 1)
+ * over block b of the map, b in [0, nblocks), accumulated in double in a fixed order; no atomics.
+ * d3_grad_clip_finish: sums partials[0..n) in double in a fixed order (n spans every group of the optimizer, one
+ * contiguous segment per d3_grad_sumsq call; n == 0: norm 0), takes the square root and writes norm, coef, skip and
+ * nskipped of the record as torch.nn.utils.clip_grad_norm_(max_norm) defines them.  max_norm > 0, +inf allowed.
+ * The record is bit-identical from run to run for the same gradients. */
+int d3_grad_sumsq(const long long *ptrs, const int *numel, const void *blocks, int nblocks, double *partials, void *stream);
+int d3_grad_clip_finish(const double *partials, int n, double max_norm, void *ctl, void *stream);
+/* d3_adamw / d3_adam / d3_sgd behind torch.nn.utils.clip_grad_norm_: each element uses g * ctl->coef (one fp32 multiply,
+ * what clip_grad_norm_'s in-place mul_ would have left in memory; the gradient itself is NOT rewritten), and the launch
+ * stores nothing while ctl->skip and ctl->enforce are set.  ctl: the device record d3_grad_clip_finish wrote on the
+ * same stream. */
+int d3_adamw_clipped(const long long *ptrs, const int *numel, const void *blocks, int nblocks, double lr, double beta1,
+                     double beta2, double eps, double weight_decay, double bias_correction1, double bias_correction2_sqrt,
+                     const void *ctl, void *stream);
+int d3_adam_clipped(const long long *ptrs, const int *numel, const void *blocks, int nblocks, double lr, double beta1,
+                    double beta2, double eps, double weight_decay, double bias_correction1, double bias_correction2_sqrt,
+                    const void *ctl, void *stream);
+int d3_sgd_clipped(const long long *ptrs, const int *numel, const void *blocks, int nblocks, double lr, double momentum,
+                   double weight_decay, int first, const void *ctl, void *stream);
 /* out[idx[s], :] += g[s, :] (out zero-filled by the caller): backward of the cluster feature gather
  * (model/pointgroup.py:130); deterministic when every output row receives at most two addends, as it does there */
 int d3_scatter_add_rows(const float *g, const int64_t *idx, float *out, long long S, int C, void *stream);
