@@ -110,6 +110,9 @@ SIGNATURES = {
     "d3_adamw_clipped": (i32, [vp, vp, vp, i32, f64, f64, f64, f64, f64, f64, f64, vp, vp]),
     "d3_adam_clipped": (i32, [vp, vp, vp, i32, f64, f64, f64, f64, f64, f64, f64, vp, vp]),
     "d3_sgd_clipped": (i32, [vp, vp, vp, i32, f64, f64, f64, i32, vp, vp]),
+    "d3_metric_capacity": (i32, []),
+    "d3_metric_accumulate": (i32, [vp, i32, vp, vp]),
+    "d3_metric_reset": (i32, [vp, i32, i32, vp]),
     "d3_gather_rows_pad": (i32, [vp, i64, vp, vp, i64, i32, i32, vp]),
     "d3_point_heads_dy": (i32, [vp, vp, vp, i64, vp, vp]),
     "d3_point_heads_dx": (i32, [vp, vp, vp, vp, i64, i32, vp, vp]),

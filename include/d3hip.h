@@ -1201,6 +1201,43 @@ int d3_box_wire_text(const double *corners, const int *modes, int M, const doubl
                      void *stream);
 int d3_format_f6(const double *values, long long n, char *text, int *lens, int *status, void *stream);
 
+/* ---- running records of logged scalars (csrc/metric_log.hip, driven by d3net_amd.metric_log.MetricLog) --------------------
+ * In place of Lightning's `self.log(..., on_epoch=True)` (model/pipeline.py:149,182,...): one launch per step folds every
+ * scalar logged in that step into its slot's record; nothing is read back.
+ * A table row names one slot's value of this step: the address of a 0-d device value (NULL: the key was not logged this
+ * step, its record stays bit-unchanged), the value's type and a float64 weight.  A record is
+ *   sum        sum of weight * value in float64: one multiplication and one addition per step, in step order, unfused
+ *   wsum       sum of the weights
+ *   last       the last value
+ *   count      values folded in
+ *   nonfinite  how many of them were inf or NaN (they propagate into sum as they do through a mean)
+ * One thread per slot, one writer per record, no atomics: a record equals a sequential host sum bit for bit.
+ * d3_metric_capacity  : slots one launch or one reset range covers (1024).
+ * d3_metric_accumulate: table (nslots rows), records (nslots records), both device memory.  nslots outside
+ *   [0, d3_metric_capacity()]: D3_ERR_RANGE before any launch -- never truncated.  A row whose dtype is none of the four codes is
+ *   treated as not logged.
+ * d3_metric_reset     : zeroes records[offset .. offset + count) (one asynchronous memset), so that several tables -- training
+ *   and validation -- live in one buffer.  offset < 0 or count outside [0, d3_metric_capacity()]: D3_ERR_RANGE. */
+#define D3_METRIC_F32 0
+#define D3_METRIC_F64 1
+#define D3_METRIC_I32 2
+#define D3_METRIC_I64 3
+typedef struct d3_metric_row {
+    const void *value;
+    long long dtype;
+    double weight;
+} d3_metric_row;
+typedef struct d3_metric_rec {
+    double sum;
+    double wsum;
+    double last;
+    long long count;
+    long long nonfinite;
+} d3_metric_rec;
+int d3_metric_capacity(void);
+int d3_metric_accumulate(const void *table, int nslots, void *records, void *stream);
+int d3_metric_reset(void *records, int offset, int count, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
