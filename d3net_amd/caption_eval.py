@@ -29,7 +29,10 @@ import numpy as np
 import torch
 from scipy.optimize import linear_sum_assignment
 
+from . import _lib
+from ._call import call, on, ptr, stream
 from .cider import cider_scores
+from .devstate import FLAGS, FLOATS, INTS, check_batch, read_back
 
 _EPS = 1e-8
 
@@ -96,8 +99,6 @@ def _center_cost(pred_boxes, gt_boxes):
 
 def _assign_launch(pred_boxes, gt_boxes, nactual, strategy, return_cost):
     """-> per_gt (B, G) int32, status (B) int32, cost (B, K, G) or None; stream-ordered, nothing read back"""
-    import ctypes as C
-    from . import _lib
     if strategy not in ("giou", "center"):
         raise ValueError("invalid strategy.")
     if not pred_boxes.is_cuda:
@@ -111,17 +112,14 @@ def _assign_launch(pred_boxes, gt_boxes, nactual, strategy, return_cost):
     if B == 0 or K == 0 or G == 0:
         return per_gt.zero_(), status.zero_(), (torch.zeros((B, K, G), device=dev) if return_cost else None)
     na = nactual.to(device=dev, dtype=torch.int32).contiguous()
-    p = lambda t: C.c_void_p(t.data_ptr())
-    with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    with on(dev):
         if strategy == "giou":
             pb, gb = pred_boxes.detach().float().contiguous(), gt_boxes.detach().float().contiguous()
             cost = torch.empty((B, K, G), dtype=torch.float32, device=dev) if return_cost else None
-            _lib.check(_lib.lib().d3_dense_caption_assign(p(pb), p(gb), p(na), B, K, G, p(per_gt), p(status),
-                                                          p(cost) if cost is not None else None, stream), "dense_caption_assign")
+            call("dense_caption_assign", ptr(pb), ptr(gb), ptr(na), B, K, G, ptr(per_gt), ptr(status), ptr(cost), stream())
         else:
             cost = _center_cost(pred_boxes.detach(), gt_boxes.detach()).contiguous()
-            _lib.check(_lib.lib().d3_lsap_batched(p(cost), p(na), B, K, G, p(per_gt), p(status), stream), "lsap_batched")
+            call("lsap_batched", ptr(cost), ptr(na), B, K, G, ptr(per_gt), ptr(status), stream())
     return per_gt, status, (cost if return_cost else None)
 
 
@@ -318,7 +316,8 @@ class EvalCorpus:
         return " ".join(self.words[int(i)] for i in ids)
 
 
-_CAP_KEYS = ("lang_cap", "proposal_bbox_batched", "gt_bbox", "gt_bbox_object_id", "gt_bbox_label", "scene_id")
+_CAP_TABLE = {"lang_cap": ((torch.int64,), (("B", "K", "T"),)), "proposal_bbox_batched": (FLOATS, None), "gt_bbox": (FLOATS, None),
+              "gt_bbox_object_id": (INTS, (("B", "G"),)), "gt_bbox_label": (FLAGS, (("B", "G"),)), "scene_id": None}
 
 
 class CaptionEvaluator:
@@ -346,44 +345,32 @@ class CaptionEvaluator:
         self._status = torch.zeros(1, dtype=torch.int32, device=dev)
         self._seq, self._entries = 0, {}
 
-    def _checked(self, data_dict):
-        missing = [k for k in _CAP_KEYS if k not in data_dict]
-        if missing:
-            raise ValueError("CaptionEvaluator.add_batch: missing %s" % missing)
-        caps, pb, gb, ids, mask, scenes = (data_dict[k] for k in _CAP_KEYS)
-        dev = self.corpus.device
-        for k in _CAP_KEYS[:5]:
-            t = data_dict[k]
-            if not torch.is_tensor(t) or not t.is_cuda or t.device != dev:
-                raise ValueError("CaptionEvaluator.add_batch: %s must be a tensor on the corpus's GPU (%s)" % (k, dev))
+    @staticmethod
+    def _geometry(d):
+        name = "CaptionEvaluator.add_batch"
+        caps, pb, gb = d["lang_cap"], d["proposal_bbox_batched"], d["gt_bbox"]
         if pb.dim() != 4 or tuple(pb.shape[2:]) != (8, 3) or gb.dim() != 4 or tuple(gb.shape[2:]) != (8, 3) or gb.shape[0] != pb.shape[0]:
-            raise ValueError("CaptionEvaluator.add_batch: corners (B,K,8,3) and (B,G,8,3) expected")
+            raise ValueError("%s: corners (B,K,8,3) and (B,G,8,3) expected" % name)
         B, K, G = pb.shape[0], pb.shape[1], gb.shape[1]
         if B < 1 or K < 1 or G < 1 or K > DEVICE_ASSIGN_MAX or G > DEVICE_ASSIGN_MAX:
-            raise ValueError("CaptionEvaluator.add_batch: B >= 1, 1 <= K, G <= %d (got B %d, K %d, G %d)" % (DEVICE_ASSIGN_MAX, B, K, G))
+            raise ValueError("%s: B >= 1, 1 <= K, G <= %d (got B %d, K %d, G %d)" % (name, DEVICE_ASSIGN_MAX, B, K, G))
         if B * G > EVAL_MAX_SLOTS_PER_BATCH:
-            raise ValueError("CaptionEvaluator.add_batch: B * G = %d exceeds %d" % (B * G, EVAL_MAX_SLOTS_PER_BATCH))
-        if caps.dim() != 3 or tuple(caps.shape[:2]) != (B, K):
-            raise ValueError("CaptionEvaluator.add_batch: lang_cap must be (%d, %d, T)" % (B, K))
+            raise ValueError("%s: B * G = %d exceeds %d" % (name, B * G, EVAL_MAX_SLOTS_PER_BATCH))
+        if caps.dim() != 3:
+            raise ValueError("%s: lang_cap must be (%d, %d, T)" % (name, B, K))
         T = caps.shape[2]
         if T > EVAL_MAX_TOKENS - 2:
-            raise ValueError("CaptionEvaluator.add_batch: captions of T = %d tokens, the kernel holds %d" % (T, EVAL_MAX_TOKENS - 2))
-        for k, t in ((_CAP_KEYS[3], ids), (_CAP_KEYS[4], mask)):
-            if tuple(t.shape) != (B, G):
-                raise ValueError("CaptionEvaluator.add_batch: %s must be (%d, %d)" % (k, B, G))
-        ints = (torch.int32, torch.int64)
-        for k, t, ok in ((_CAP_KEYS[0], caps, (torch.int64,)), (_CAP_KEYS[1], pb, (torch.float32,)), (_CAP_KEYS[2], gb, (torch.float32,)),
-                         (_CAP_KEYS[3], ids, ints), (_CAP_KEYS[4], mask, (torch.float32, torch.bool, torch.uint8) + ints)):
-            if t.dtype not in ok:
-                raise ValueError("CaptionEvaluator.add_batch: %s has dtype %s, expected one of %s" % (k, t.dtype, ok))
-        if len(scenes) != B:
-            raise ValueError("CaptionEvaluator.add_batch: scene_id must name the %d scenes" % B)
-        return caps, pb, gb, ids, mask, scenes, B, K, G, T
+            raise ValueError("%s: captions of T = %d tokens, the kernel holds %d" % (name, T, EVAL_MAX_TOKENS - 2))
+        if len(d["scene_id"]) != B:
+            raise ValueError("%s: scene_id must name the %d scenes" % (name, B))
+        return dict(B=B, K=K, G=G, T=T)
+
+    def _checked(self, d):
+        dims = check_batch("CaptionEvaluator.add_batch", d, _CAP_TABLE, self._geometry, self.corpus.device, self._status)
+        return tuple(d[k] for k in _CAP_TABLE) + tuple(dims[k] for k in "BKGT")
 
     def add_batch(self, data_dict):
         """the six keys eval_caption_step reads, tensors on the GPU; returns nothing and reads nothing back"""
-        import ctypes as C
-        from . import _lib
         caps, pb, gb, ids, mask, scenes, B, K, G, T = self._checked(data_dict)
         c, dev = self.corpus, self.corpus.device
         nactual = mask.sum(1).long()
@@ -391,13 +378,10 @@ class CaptionEvaluator:
         per_gt, astatus, _ = _assign_launch(pb, gb, nactual, self.strategy, False)
         scene_idx = torch.tensor([c.scene_index.get(s, -1) for s in scenes], dtype=torch.int32).to(dev, non_blocking=True)
         m32, ids64, caps = (mask != 0).to(torch.int32).contiguous(), ids.long().contiguous(), caps.detach().contiguous()
-        p = lambda t: C.c_void_p(t.data_ptr())
-        with torch.cuda.device(dev):
-            _lib.check(_lib.lib().d3_caption_collect(p(per_gt), p(pb), p(gb), p(m32), p(ids64), p(caps) if T else None, p(c.lut), p(scene_idx),
-                                                     p(c.slot_of), p(astatus), B, K, G, T, c.V, c.n_scenes, c.n_obj, len(c.keys), c.sos,
-                                                     c.eos, self._seq, p(self._owner), p(self._cap), p(self._cap_len), p(self._iou),
-                                                     p(self._seen), p(self._status), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
-                       "caption_collect")
+        with on(dev):
+            call("caption_collect", ptr(per_gt), ptr(pb), ptr(gb), ptr(m32), ptr(ids64), ptr(caps) if T else None, ptr(c.lut), ptr(scene_idx),
+                 ptr(c.slot_of), ptr(astatus), B, K, G, T, c.V, c.n_scenes, c.n_obj, len(c.keys), c.sos, c.eos, self._seq, ptr(self._owner),
+                 ptr(self._cap), ptr(self._cap_len), ptr(self._iou), ptr(self._seen), ptr(self._status), stream())
         self._seq += 1
 
     def _entry_tables(self, seen):
@@ -422,8 +406,6 @@ class CaptionEvaluator:
 
     def compute(self, min_iou=None):
         """-> (bleu, cider, rouge, meteor) as eval_caption_epoch returns them for the epoch's merged candidates; sets self.keys"""
-        import ctypes as C
-        from . import _lib
         from .caption_metrics import bleu_from_counts, rouge_from_lcs
         min_iou = self.min_iou if min_iou is None else float(min_iou)
         c, dev = self.corpus, self.corpus.device
@@ -441,27 +423,21 @@ class CaptionEvaluator:
         empty[0], empty[1] = c.sos, c.eos
         cand = torch.where(keep[:, None], self._cap[sel], empty[None]).contiguous()
         clen = torch.where(keep, self._cap_len[sel], torch.full_like(self._cap_len[sel], 2)).contiguous()
-        L = _lib.lib()
-        ws = torch.empty(L.d3_cider_ws_bytes(SR, E, hash_slots), dtype=torch.uint8, device=dev)
+        ws = torch.empty(_lib.lib().d3_cider_ws_bytes(SR, E, hash_slots), dtype=torch.uint8, device=dev)
         scores = torch.empty(E, dtype=torch.float64, device=dev)
         flag = torch.empty(1, dtype=torch.int32, device=dev)
         stats = torch.empty((E, 6), dtype=torch.int32, device=dev)
         lcs = torch.empty(SR, dtype=torch.int32, device=dev)
-        p = lambda t: C.c_void_p(t.data_ptr())
-        with torch.cuda.device(dev):
-            stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-            _lib.check(L.d3_cider_scores(p(c.tokens), c.ldt, p(c.lens), p(d_rows), p(d_uoff), p(d_mult), p(d_ent), E, SR, p(cand),
-                                         EVAL_MAX_TOKENS, p(clen), E, c.eos, 6.0, hash_slots, p(scores), p(flag), p(ws), ws.numel(), stream),
-                       "cider_scores")
-            _lib.check(L.d3_caption_stats(p(cand), EVAL_MAX_TOKENS, p(clen), p(c.tokens), c.ldt, p(c.lens), p(d_rows), p(d_uoff), E, p(stats),
-                                          p(lcs), stream), "caption_stats")
-        host = torch.cat([stats.view(-1).double(), lcs.double(), scores, flag.double(), self._status.double()]).cpu().numpy()   # read-back 2
-        if int(host[-2]):
+        with on(dev):
+            call("cider_scores", ptr(c.tokens), c.ldt, ptr(c.lens), ptr(d_rows), ptr(d_uoff), ptr(d_mult), ptr(d_ent), E, SR, ptr(cand),
+                 EVAL_MAX_TOKENS, ptr(clen), E, c.eos, 6.0, hash_slots, ptr(scores), ptr(flag), ptr(ws), ws.numel(), stream())
+            call("caption_stats", ptr(cand), EVAL_MAX_TOKENS, ptr(clen), ptr(c.tokens), c.ldt, ptr(c.lens), ptr(d_rows), ptr(d_uoff), E, ptr(stats),
+                 ptr(lcs), stream())
+        counts, lcs_h, cider, flag, status = read_back([stats, lcs, scores, flag, self._status])                      # read-back 2
+        if int(flag[0]):
             raise _lib.D3Error("CaptionEvaluator: a CIDEr hash table overflowed")
-        self._raise_on(int(host[-1]))
-        counts = host[:6 * E].astype(np.int64).reshape(E, 6).tolist()
-        lcs_h = host[6 * E:6 * E + SR].astype(np.int64).tolist()
-        cider = host[6 * E + SR:6 * E + SR + E].copy()
+        self._raise_on(int(status[0]))
+        counts, lcs_h, cider = counts.tolist(), lcs_h.tolist(), cider.copy()
         bleu = bleu_from_counts(counts, 4)
         rouge = rouge_from_lcs([(counts[e][4], [c.row_len[r] for r in slot_row[u_off[e]:u_off[e + 1]]], lcs_h[u_off[e]:u_off[e + 1]])
                                 for e in range(E)])
@@ -469,7 +445,6 @@ class CaptionEvaluator:
 
     @staticmethod
     def _raise_on(status):
-        from . import _lib
         if status & 1:
             raise _lib.D3Error("CaptionEvaluator: a matched caption holds a token outside the vocabulary")
         if status & 6:

@@ -65,7 +65,7 @@ def _cider_device(corpus, entry_sets, cands, sample_topn):
     """entry_sets: per valid description its (first row, #rows) in the corpus; cands: E = len(entry_sets) * sample_topn device
     token tensors -> (E,) float64 device scores, or None when the batch does not fit the kernels' fixed tables."""
     from . import _lib
-    from ._lib import check
+    from ._call import call, on, ptr, stream
     E = len(cands)
     uniq, u_of = {}, []
     for fs in entry_sets:
@@ -102,15 +102,12 @@ def _cider_device(corpus, entry_sets, cands, sample_topn):
         if corpus.lut is not None:
             flat = corpus.lut[flat.long()]
         cand.view(-1)[d_pos.long()] = flat.to(torch.int32)
-    L = _lib.lib()
-    ws = torch.empty(L.d3_cider_ws_bytes(SR, E, hash_slots), dtype=torch.uint8, device=dev)
+    ws = torch.empty(_lib.lib().d3_cider_ws_bytes(SR, E, hash_slots), dtype=torch.uint8, device=dev)
     out = torch.empty(E, dtype=torch.float64, device=dev)
     flag = torch.empty(1, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        check(L.d3_cider_scores(corpus.tokens.data_ptr(), corpus.ldt, corpus.lens.data_ptr(), d_slot.data_ptr(), d_uoff.data_ptr(),
-                                d_mult.data_ptr(), d_ent.data_ptr(), U, SR, cand.data_ptr(), ldc, d_clen.data_ptr(), E, corpus.eos, 6.0,
-                                hash_slots, out.data_ptr(), flag.data_ptr(), ws.data_ptr(), ws.numel(),
-                                torch.cuda.current_stream().cuda_stream), "cider_scores")
+    with on(dev):
+        call("cider_scores", ptr(corpus.tokens), corpus.ldt, ptr(corpus.lens), ptr(d_slot), ptr(d_uoff), ptr(d_mult), ptr(d_ent), U, SR,
+             ptr(cand), ldc, ptr(d_clen), E, corpus.eos, 6.0, hash_slots, ptr(out), ptr(flag), ptr(ws), ws.numel(), stream())
     return out
 
 
@@ -216,7 +213,7 @@ class _MaskedXE(torch.autograd.Function):
     def forward(ctx, pred, target, good):
         from . import _lib
         from ._lib import check
-        from .pointgroup_ops import _on, _ptr, _stream
+        from ._call import _on, _ptr, _stream
         N, S, V = pred.shape
         dev = pred.device
         pred = pred.contiguous()
@@ -288,7 +285,7 @@ class _OrientationLoss(torch.autograd.Function):
         import ctypes as C
         from . import _lib
         from ._lib import check
-        from .pointgroup_ops import _on, _ptr, _stream
+        from ._call import _on, _ptr, _stream
         B, E, nb = preds.shape
         assert nb == num_bins and preds.stride(2) == 1
         bounds = torch.arange(np.pi / num_bins, np.pi - 1e-8, np.pi / num_bins).float().tolist()   # `radian_to_label`

@@ -9,14 +9,10 @@ which are resized exactly as the reference natives do (src/voxelize/voxelize.cpp
 src/bfs_cluster/bfs_cluster.cpp:103-106)."""
 import ctypes as C
 
-import torch
-
 from .. import _lib
 from .. import pointgroup_ops as _ops
+from .._call import ptr as _P, stream as _S, workspace
 from .._lib import check
-
-_P = lambda t: C.c_void_p(t.data_ptr())
-_S = lambda: C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def voxelize_idx(coords, output_coords, input_map, output_map, batchSize, mode):
@@ -50,7 +46,7 @@ def ballquery_batch_p(xyz, batch_idxs, batch_offsets, idx, start_len, n, meanAct
     """returns the total hit count; > n*meanActive makes the reference wrapper retry with a bigger `idx`
     (functions/pointgroup_ops.py:135-142); hits beyond idx's capacity are dropped as in bfs_cluster.cu:51-59."""
     L = _lib.lib()
-    ws = _ops._workspace(L.d3_ballquery_ws_bytes(n), xyz.device, "bq")
+    ws = workspace(L.d3_ballquery_ws_bytes(n), xyz.device, "bq")
     tot = C.c_int(0)
     check(L.d3_ballquery_count(_P(xyz), _P(batch_idxs), _P(batch_offsets), n, float(radius), _P(start_len), _P(ws),
                                ws.numel(), C.byref(tot), _S()), "ballquery_count")

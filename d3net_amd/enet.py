@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib, multiview
-from .pointgroup_ops import _ptr, _stream
+from ._call import _ptr, _stream
 
 IMAGE_DIMS = (328, 256)                      # (W, H): compute_multiview_features.py:30
 MEAN = (0.496342, 0.466664, 0.440796)       # :70

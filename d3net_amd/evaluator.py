@@ -6,7 +6,14 @@ over boxes instead of the reference's per-box python loops, float64 arithmetic a
 the reference's own numbers and the one the mAP@0.5 parity report uses (HIP detector vs CPU oracle on identical weights and
 scenes).  DetectionEvaluator below them is the same metric on the device (csrc/nms.hip + csrc/det_eval.hip): nothing is read
 back per batch, one small table at the end."""
+import ctypes as C
+
 import numpy as np
+import torch
+
+from . import _lib
+from ._call import call, on, ptr, stream
+from .devstate import FLAGS, FLOATS, INTS, check_batch, read_back
 
 POST_DICT = {"remove_empty_box": False, "use_3d_nms": True, "nms_iou": 0.25, "use_old_type_nms": False, "cls_nms": True,
              "per_class_proposal": True, "conf_thresh": 0.09}   # scripts/eval.py:132-143, model/pipeline.py:75-87
@@ -37,9 +44,6 @@ def nms_pred_mask_device(data_dict, nms_iou=0.25, old_type=False, numpy_tie_orde
     same picks as the host loop below (float64 arithmetic).  Exactly tied scores: numpy's argsort (the reference's visiting
     order) leaves their order to its sort implementation; `numpy_tie_order` computes that order on the host and hands it to
     the kernel, otherwise ties go to the later proposal first."""
-    import ctypes as C
-    import torch
-    from . import _lib
     boxes = data_dict["proposal_bbox_batched"].detach().float()
     B, K = boxes.shape[:2]
     cls = data_dict["proposal_sem_cls_batched"].detach().float() - 2
@@ -57,10 +61,8 @@ def nms_pred_mask_device(data_dict, nms_iou=0.25, old_type=False, numpy_tie_orde
             o = inds[np.argsort(sc[i][va[i]])[::-1]]          # nms.py:122: I = np.argsort(score), visited from the end
             vis[i, :len(o)] = o
         visit = torch.from_numpy(vis).to(boxes.device)
-    with torch.cuda.device(boxes.device):
-        _lib.check(_lib.lib().d3_nms3d_samecls(C.c_void_p(b8.data_ptr()), C.c_void_p(valid.data_ptr()),
-                                               C.c_void_p(visit.data_ptr()) if visit is not None else None, B, K, float(nms_iou), int(old_type),
-                                               C.c_void_p(pick.data_ptr()), C.c_void_p(torch.cuda.current_stream().cuda_stream)), "nms3d_samecls")
+    with on(boxes.device):
+        call("nms3d_samecls", ptr(b8), ptr(valid), ptr(visit), B, K, float(nms_iou), int(old_type), ptr(pick), stream())
     return pick
 
 
@@ -215,14 +217,14 @@ class APCalculator:
 
 # ------------------------------------------------------------------------------------------------- device path (csrc/det_eval.hip)
 DET_MAX_BOXES, DET_MAX_THRESHOLDS = 256, 4
-_DET_KEYS = ("proposal_bbox_batched", "proposal_sem_cls_batched", "proposal_batch_mask", "proposal_scores_batched",
-             "gt_bbox", "gt_bbox_label", "sem_cls_label")
+_DET_TABLE = {"proposal_bbox_batched": (FLOATS, None), "proposal_sem_cls_batched": (FLOATS + INTS, (("B", "K"),)),
+              "proposal_batch_mask": (FLAGS, (("B", "K"),)), "proposal_scores_batched": (FLOATS, (("B", "K"),)),
+              "gt_bbox": (FLOATS, None), "gt_bbox_label": (FLAGS, (("B", "G"),)), "sem_cls_label": (INTS, (("B", "G"),))}
 
 
 def map_pred_classes(sem):
     """proposal_sem_cls_batched -> int32 evaluation classes as parse_predictions maps them (sem - 2, negative -> 17); a value that
     is no integer matches no class there and becomes -1"""
-    import torch
     cls = sem.detach().float() - 2
     cls = torch.where(cls < 0, torch.full_like(cls, 17.0), cls)
     ci = cls.to(torch.int32)
@@ -234,9 +236,6 @@ def det_match_device(boxes, cls, scores, pick, conf_thresh, gt_boxes, gt_mask, g
     (B,G,8,3) f32, gt_mask (B,G) f32, gt_cls (B,G) i32, all contiguous on one GPU -> dict of device tensors: kept, cls, score,
     ovmax (f64), jmax, tp (bit q: true positive at thresholds[q]) (B,K); gt_count (B,num_class); status (1,) int32, OR-ed into
     when given.  Nothing is read back."""
-    import ctypes as C
-    import torch
-    from . import _lib
     B, K = scores.shape
     G = gt_mask.shape[1]
     dev = scores.device
@@ -245,12 +244,9 @@ def det_match_device(boxes, cls, scores, pick, conf_thresh, gt_boxes, gt_mask, g
                ovmax=torch.empty((B, K), dtype=torch.float64, device=dev), jmax=i32(B, K), tp=i32(B, K), gt_count=i32(B, num_class),
                status=status if status is not None else torch.zeros(1, dtype=torch.int32, device=dev))
     thr = (C.c_double * len(thresholds))(*[float(t) for t in thresholds])
-    p = lambda t: C.c_void_p(t.data_ptr())
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().d3_det_match(p(boxes), p(cls), p(scores), p(pick), float(conf_thresh), p(gt_boxes), p(gt_mask), p(gt_cls),
-                                           B, K, G, num_class, thr, len(thresholds), p(out["kept"]), p(out["cls"]), p(out["score"]),
-                                           p(out["ovmax"]), p(out["jmax"]), p(out["tp"]), p(out["gt_count"]), p(out["status"]),
-                                           C.c_void_p(torch.cuda.current_stream().cuda_stream)), "det_match")
+    with on(dev):
+        call("det_match", ptr(boxes), ptr(cls), ptr(scores), ptr(pick), float(conf_thresh), ptr(gt_boxes), ptr(gt_mask), ptr(gt_cls), B, K, G,
+             num_class, thr, len(thresholds), *[ptr(out[k]) for k in ("kept", "cls", "score", "ovmax", "jmax", "tp", "gt_count", "status")], stream())
     return out
 
 
@@ -258,9 +254,6 @@ def det_ap_device(kept, cls, score, tp, gt_count, num_thresholds, num_class=18):
     """flat record tensors (n,) in record order (scene sequence number, then proposal index) and gt_count (S,num_class) -> table
     (T,num_class,4) float64 on the device = [AP, last recall, detections, present].  One stable sort on the key (class, descending
     score) -- equal scores keep their record order -- and one d3_det_ap launch; nothing is read back."""
-    import ctypes as C
-    import torch
-    from . import _lib
     dev = gt_count.device
     b = score.view(torch.int32).to(torch.int64)
     asc = torch.where(b >= 0, b + (1 << 31), -1 - b)                     # float32 order as an unsigned 32-bit key
@@ -269,10 +262,9 @@ def det_ap_device(kept, cls, score, tp, gt_count, num_thresholds, num_class=18):
     tp_sorted = tp[order].contiguous()
     bounds = torch.searchsorted(skey, torch.arange(num_class + 1, device=dev, dtype=torch.int64) * (1 << 32)).to(torch.int32).contiguous()
     table = torch.empty((num_thresholds, num_class, 4), dtype=torch.float64, device=dev)
-    p = lambda t: C.c_void_p(t.data_ptr()) if t.numel() else None
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().d3_det_ap(p(tp_sorted), p(bounds), p(gt_count), gt_count.shape[0], tp_sorted.numel(), num_class,
-                                        num_thresholds, p(table), C.c_void_p(torch.cuda.current_stream().cuda_stream)), "det_ap")
+    p = lambda t: ptr(t) if t.numel() else None                          # an empty tensor goes as NULL
+    with on(dev):
+        call("det_ap", p(tp_sorted), p(bounds), p(gt_count), gt_count.shape[0], tp_sorted.numel(), num_class, num_thresholds, p(table), stream())
     return table
 
 
@@ -298,36 +290,23 @@ class DetectionEvaluator:
     def reset(self):
         self._records, self._status, self.table = [], None, None
 
-    def _checked(self, data_dict):
-        import torch
-        missing = [k for k in _DET_KEYS if k not in data_dict]
-        if missing:
-            raise ValueError("DetectionEvaluator.add_batch: missing %s" % missing)
-        boxes, sem, mask, scores, gtb, gtm, gtc = (data_dict[k] for k in _DET_KEYS)
-        for k in _DET_KEYS:
-            if not torch.is_tensor(data_dict[k]) or not data_dict[k].is_cuda or data_dict[k].device != boxes.device:
-                raise ValueError("DetectionEvaluator.add_batch: %s must be a tensor on the GPU of the proposals" % k)
-        if self._status is not None and self._status.device != boxes.device:
-            raise ValueError("DetectionEvaluator.add_batch: the batches of one evaluation live on one device")
+    @staticmethod
+    def _geometry(d):
+        boxes, gtb = d["proposal_bbox_batched"], d["gt_bbox"]
         if boxes.dim() != 4 or tuple(boxes.shape[2:]) != (8, 3) or gtb.dim() != 4 or tuple(gtb.shape[2:]) != (8, 3) or gtb.shape[0] != boxes.shape[0]:
             raise ValueError("DetectionEvaluator.add_batch: corners (B,K,8,3) and (B,G,8,3) expected")
         B, K, G = boxes.shape[0], boxes.shape[1], gtb.shape[1]
         if B < 1 or K > DET_MAX_BOXES or G > DET_MAX_BOXES:
             raise ValueError("DetectionEvaluator.add_batch: B >= 1, K <= %d and G <= %d (got B %d, K %d, G %d)" % (DET_MAX_BOXES, DET_MAX_BOXES, B, K, G))
-        for k, t, n in ((_DET_KEYS[1], sem, K), (_DET_KEYS[2], mask, K), (_DET_KEYS[3], scores, K), (_DET_KEYS[5], gtm, G), (_DET_KEYS[6], gtc, G)):
-            if tuple(t.shape) != (B, n):
-                raise ValueError("DetectionEvaluator.add_batch: %s must be (%d, %d)" % (k, B, n))
-        ints = (torch.int32, torch.int64)
-        for k, t, ok in ((_DET_KEYS[0], boxes, (torch.float32,)), (_DET_KEYS[3], scores, (torch.float32,)), (_DET_KEYS[4], gtb, (torch.float32,)),
-                         (_DET_KEYS[1], sem, (torch.float32,) + ints), (_DET_KEYS[2], mask, (torch.float32, torch.bool, torch.uint8) + ints),
-                         (_DET_KEYS[5], gtm, (torch.float32, torch.bool, torch.uint8) + ints), (_DET_KEYS[6], gtc, ints)):
-            if t.dtype not in ok:
-                raise ValueError("DetectionEvaluator.add_batch: %s has dtype %s, expected one of %s" % (k, t.dtype, ok))
-        return boxes, sem, scores, gtb, gtm, gtc, B, K
+        return dict(B=B, K=K, G=G)
+
+    def _checked(self, d):
+        dims = check_batch("DetectionEvaluator.add_batch", d, _DET_TABLE, self._geometry, None, self._status)
+        return tuple(d[k] for k in ("proposal_bbox_batched", "proposal_sem_cls_batched", "proposal_scores_batched", "gt_bbox", "gt_bbox_label",
+                                    "sem_cls_label")) + (dims["B"], dims["K"])
 
     def add_batch(self, data_dict):
         """the seven keys parse_predictions and parse_groundtruths read, as GPU tensors"""
-        import torch
         boxes, sem, scores, gtb, gtm, gtc, B, K = self._checked(data_dict)
         dev = boxes.device
         if self._status is None:
@@ -342,19 +321,17 @@ class DetectionEvaluator:
         self._records.append(tuple(r[k].view(-1) for k in ("kept", "cls", "score", "tp")) + (r["gt_count"],))
 
     def compute_metrics(self):
-        import torch
-        from . import _lib
         if not self._records:
             raise ValueError("DetectionEvaluator.compute_metrics: no batch was added")
         kept, cls, score, tp, gt_count = (torch.cat([r[i] for r in self._records]) for i in range(5))
         table = det_ap_device(kept, cls, score, tp, gt_count, len(self.thresholds), self.num_class)
-        host = torch.cat([table.view(-1), self._status.to(torch.float64)]).cpu().numpy()          # the one read-back
-        status = int(host[-1])
+        table, status = read_back([table, self._status])                                     # the one read-back
+        status = int(status[0])
         if status & 1:
             raise _lib.D3Error("DetectionEvaluator: a kept detection or a valid GT box holds a non-finite coordinate")
         if status & 2:
             raise _lib.D3Error("DetectionEvaluator: a valid GT box has a class outside [0, %d)" % self.num_class)
-        self.table = host[:-1].reshape(len(self.thresholds), self.num_class, 4)
+        self.table = table
         name = lambda k: self.class2type_map[k] if self.class2type_map else str(k)
         out = []
         for q in range(len(self.thresholds)):

@@ -14,6 +14,8 @@ reference's return keys.
 """
 import torch
 
+from ._call import call, on, ptr, stream
+from .devstate import FLAGS, FLOATS, GROUND_MAX_K, INTS, RecordStore, as_f32, as_i64, check_batch, read_back
 from .listener import aabb_iou_to_gt
 
 
@@ -64,13 +66,18 @@ def get_eval(data_dict, grounding=True, use_lang_classifier=False):
 
 
 # ---------------------------------------------------------------------------------------------------- the device form
-GROUND_MAX_K, GROUND_MAX_LANG = 4096, 64             # proposal slots per scene / language classes of csrc/grounding_eval.hip
+GROUND_MAX_LANG = 64                                  # language classes of csrc/grounding_eval.hip
 _MULTIPLE = (("unique", 0), ("multiple", 1))          # scripts/eval.py:305-312
 _OTHERS = (("not_in_others", 0), ("in_others", 1))
 _METRICS = ("ref_acc", "acc@0.25iou", "acc@0.5iou")
-_GROUND_KEYS = ("cluster_ref", "cluster_labels", "proposal_batch_mask", "proposal_bbox_batched", "ref_box_corner_label",
-                "unique_multiple", "object_cat")
-_INTS = (torch.int32, torch.int64)
+_ROWS = (("B", "C"), ("N",))                          # one value per description, batched or flat
+_TABLE = {"cluster_ref": (FLOATS, None), "cluster_labels": (FLAGS, (("N", "K"),)), "proposal_batch_mask": (FLAGS, (("B", "K"),)),
+          "proposal_bbox_batched": (FLOATS, (("B", "K", 8, 3),)), "ref_box_corner_label": (FLOATS, (("B", "C", 8, 3), ("N", 8, 3))),
+          "unique_multiple": (INTS, _ROWS), "object_cat": (INTS, _ROWS),
+          "lang_scores": (FLOATS, (("N", "L"),)),                             # use_lang_classifier
+          "id": (INTS, (("B",),)), "chunk_ids": (INTS, (("B", "C"),))}        # keep_predictions
+_REC = dict(iou=((), torch.float32), best_iou=((), torch.float32), pred_ref=((), torch.int32), gt_ref=((), torch.int32),
+            ref_acc=((), torch.int32), pred_bbox=((8, 3), torch.float32), gt_bbox=((8, 3), torch.float32), ids=((2,), torch.int64))
 
 
 def grounding_scores(tables, lang_correct=(), lang_rows=()):
@@ -119,71 +126,37 @@ class GroundingEvaluator:
 
     def reset(self):
         self._tables = self._lang = self._status = self._rec = None
-        self._repeat, self._lang_rows, self._rows, self.tables = -1, [], 0, None
+        self._repeat, self._lang_rows, self.tables = -1, [], None
 
     def begin_repeat(self):
         self._repeat += 1
-        self._rows = 0                                  # the records are the last repeat's (scripts/eval.py:196, 264-266)
+        if self._rec is not None:
+            self._rec.rows = 0                          # the records are the last repeat's (scripts/eval.py:196, 264-266)
 
-    def _checked(self, d):
+    def _geometry(self, d):
         name = "GroundingEvaluator.add_batch"
-        keys = _GROUND_KEYS + (("lang_scores",) if self.use_lang_classifier else ()) + (("id", "chunk_ids") if self.keep_predictions else ())
-        missing = [k for k in keys if k not in d]
-        if missing:
-            raise ValueError("%s: missing %s" % (name, missing))
-        for k in keys:
-            if not torch.is_tensor(d[k]):
-                raise ValueError("%s: %s must be a tensor" % (name, k))
-        ref, labels, mask, boxes, gt = (d[k] for k in _GROUND_KEYS[:5])
+        ref, mask, boxes = d["cluster_ref"], d["proposal_batch_mask"], d["proposal_bbox_batched"]
         if ref.dim() != 2 or boxes.dim() != 4 or tuple(boxes.shape[2:]) != (8, 3) or mask.dim() != 2:
             raise ValueError("%s: cluster_ref (N,K), proposal_batch_mask (B,K) and proposal_bbox_batched (B,K,8,3) expected" % name)
         (N, K), B = ref.shape, boxes.shape[0]
         if B < 1 or N < 1 or N % B or not 1 <= K <= GROUND_MAX_K:
             raise ValueError("%s: B >= 1, N = B * C >= 1 and 1 <= K <= %d (got B %d, N %d, K %d)" % (name, GROUND_MAX_K, B, N, K))
-        Cn = N // B
-        want = {"cluster_labels": ((N, K),), "proposal_batch_mask": ((B, K),), "proposal_bbox_batched": ((B, K, 8, 3),),
-                "ref_box_corner_label": ((B, Cn, 8, 3), (N, 8, 3)), "unique_multiple": ((B, Cn), (N,)), "object_cat": ((B, Cn), (N,)),
-                "id": ((B,),), "chunk_ids": ((B, Cn),)}
-        for k in keys:
-            if k in want and tuple(d[k].shape) not in want[k]:
-                raise ValueError("%s: %s has shape %s, expected %s" % (name, k, tuple(d[k].shape), " or ".join(map(str, want[k]))))
-        floats, flags = (torch.float32,), (torch.float32, torch.bool, torch.uint8) + _INTS
-        ok = {"cluster_ref": floats, "cluster_labels": flags, "proposal_batch_mask": flags, "proposal_bbox_batched": floats,
-              "ref_box_corner_label": floats, "unique_multiple": _INTS, "object_cat": _INTS, "lang_scores": floats, "id": _INTS,
-              "chunk_ids": _INTS}
-        for k in keys:
-            if d[k].dtype not in ok[k]:
-                raise ValueError("%s: %s has dtype %s, expected one of %s" % (name, k, d[k].dtype, ok[k]))
         L = 0
         if self.use_lang_classifier:
             ls = d["lang_scores"]
-            if ls.dim() != 2 or ls.shape[0] != N or not 1 <= ls.shape[1] <= GROUND_MAX_LANG:
+            if ls.dim() != 2 or not 1 <= ls.shape[1] <= GROUND_MAX_LANG:
                 raise ValueError("%s: lang_scores must be (%d, L) with 1 <= L <= %d, got %s" % (name, N, GROUND_MAX_LANG, tuple(ls.shape)))
             L = ls.shape[1]
-        for k in keys:
-            t = d[k]
-            if not t.is_cuda or (self.device.index is not None and t.device != self.device):
-                raise ValueError("%s: %s must be on the evaluator's GPU (%s), it is on %s" % (name, k, self.device, t.device))
-            if t.device != ref.device or (self._status is not None and t.device != self._status.device):
-                raise ValueError("%s: the batches of one evaluation live on one device" % name)
-        return B, Cn, K, N, L
+        return dict(B=B, C=N // B, K=K, N=N, L=L)
 
-    @staticmethod
-    def _grown(t, need):
-        """t with room for `need` leading entries: capacity doubles, the old entries are copied on the device, the rest is zero"""
-        if t.shape[0] >= need:
-            return t
-        cap = t.shape[0]
-        while cap < need:
-            cap *= 2
-        new = torch.zeros((cap,) + tuple(t.shape[1:]), dtype=t.dtype, device=t.device)
-        new[:t.shape[0]].copy_(t)
-        return new
+    def _checked(self, d):
+        skip = (() if self.use_lang_classifier else ("lang_scores",)) + (() if self.keep_predictions else ("id", "chunk_ids"))
+        dims = check_batch("GroundingEvaluator.add_batch", d, {k: v for k, v in _TABLE.items() if k not in skip}, self._geometry,
+                           self.device, self._status)
+        return tuple(dims[k] for k in "BCKNL")
 
     def add_batch(self, data_dict):
         """one launch, nothing read back; `data_dict` is left as it is"""
-        import ctypes as C
-        from . import _lib
         d = data_dict
         B, Cn, K, N, L = self._checked(d)
         dev = d["cluster_ref"].device
@@ -191,84 +164,74 @@ class GroundingEvaluator:
             self._repeat = 0
         if self._status is None:
             self._status = torch.zeros(1, dtype=torch.int32, device=dev)
-            self._tables = torch.zeros((2, 3, 2, 4), dtype=torch.int64, device=dev)
-            self._lang = torch.zeros(8, dtype=torch.int64, device=dev)
-        self._tables = self._grown(self._tables, self._repeat + 1)
+            self._tables = RecordStore(dev, 2, t=((3, 2, 4), torch.int64))
+            self._lang = RecordStore(dev, 8, n=((), torch.int64))
+        self._tables.reserve(self._repeat + 1)
         # the dtypes the dict leaves `_ground` with pass through untouched (float32 scores / labels / mask, int64 ids)
-        f32 = lambda t: t.detach().contiguous() if t.dtype == torch.float32 else t.detach().float().contiguous()
-        i64 = lambda t: t.detach().contiguous() if t.dtype == torch.int64 else t.detach().long().contiguous()
-        ref, labels, boxes, gt = f32(d["cluster_ref"]), f32(d["cluster_labels"]), f32(d["proposal_bbox_batched"]), f32(d["ref_box_corner_label"])
+        ref, labels, boxes, gt = (as_f32(d[k]) for k in ("cluster_ref", "cluster_labels", "proposal_bbox_batched", "ref_box_corner_label"))
         mask = d["proposal_batch_mask"]
         mask = mask.detach().contiguous() if mask.dtype == torch.float32 else (mask.detach().long() == 1).float().contiguous()
-        um, cat = i64(d["unique_multiple"]), i64(d["object_cat"])
+        um, cat = as_i64(d["unique_multiple"]), as_i64(d["object_cat"])
         slot = len(self._lang_rows)
-        lang = ids = chunks = None
+        lang = lang_out = ids = chunks = None
         if self.use_lang_classifier:
-            lang = f32(d["lang_scores"])
-            self._lang = self._grown(self._lang, slot + 1)
-        rec = None
+            lang = as_f32(d["lang_scores"])
+            self._lang.reserve(slot + 1)
+            lang_out = self._lang["n"][slot:]
+        rec = [None] * len(_REC)
         if self.keep_predictions:
-            ids, chunks = i64(d["id"]), i64(d["chunk_ids"])
+            ids, chunks = as_i64(d["id"]), as_i64(d["chunk_ids"])
             if self._rec is None:
-                z = lambda shape, dt: torch.zeros((1024,) + shape, dtype=dt, device=dev)
-                self._rec = dict(iou=z((), torch.float32), best_iou=z((), torch.float32), pred_ref=z((), torch.int32), gt_ref=z((), torch.int32),
-                                 ref_acc=z((), torch.int32), pred_bbox=z((8, 3), torch.float32), gt_bbox=z((8, 3), torch.float32),
-                                 ids=z((2,), torch.int64))
-            self._rec = {k: self._grown(t, self._rows + N) for k, t in self._rec.items()}
-            rec = self._rec
-        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        r = (lambda k: p(rec[k])) if rec is not None else (lambda k: None)
-        with torch.cuda.device(dev):
-            _lib.check(_lib.lib().d3_ground_eval_batch(
-                p(ref), p(labels), p(mask), p(boxes), p(gt), p(um), p(cat), p(lang), L, p(ids), p(chunks), B, Cn, K, self._rows,
-                p(self._tables[self._repeat]), p(self._lang[slot:]) if lang is not None else None, r("iou"), r("best_iou"), r("pred_ref"),
-                r("gt_ref"), r("ref_acc"), r("pred_bbox"), r("gt_bbox"), r("ids"), p(self._status),
-                C.c_void_p(torch.cuda.current_stream().cuda_stream)), "ground_eval_batch")
+                self._rec = RecordStore(dev, **_REC)
+            self._rec.reserve(self._rec.rows + N)
+            rec = [self._rec[k] for k in _REC]
+        with on(dev):
+            call("ground_eval_batch", ptr(ref), ptr(labels), ptr(mask), ptr(boxes), ptr(gt), ptr(um), ptr(cat), ptr(lang), L, ptr(ids),
+                 ptr(chunks), B, Cn, K, self._rec.rows if self.keep_predictions else 0, ptr(self._tables["t"][self._repeat]), ptr(lang_out),
+                 *[ptr(t) for t in rec], ptr(self._status), stream())
         self._lang_rows.append(N)
-        if rec is not None:
-            self._rows += N
+        if self.keep_predictions:
+            self._rec.rows += N
 
     def compute(self):
         """-> {"stats", "scores", "lang_acc", "status"} as scripts/eval.py:305-426 forms and prints them; sets self.tables (R,3,2,4)"""
         if self._status is None:
             raise ValueError("GroundingEvaluator.compute: no batch was added")
         R, nb = self._repeat + 1, len(self._lang_rows)
-        host = torch.cat([self._tables[:R].reshape(-1), self._lang[:nb], self._status.long()]).cpu().numpy()       # the one read-back
-        self.tables = host[:R * 24].reshape(R, 3, 2, 4).copy()
-        lang = host[R * 24:R * 24 + nb]
+        tables, lang, status = read_back([self._tables["t"][:R], self._lang["n"][:nb], self._status])       # the one read-back
+        self.tables = tables.copy()
         stats, scores, lang_acc = grounding_scores(self.tables, lang if self.use_lang_classifier else (),
                                                    self._lang_rows if self.use_lang_classifier else ())
-        return {"stats": stats, "scores": scores, "lang_acc": lang_acc, "status": int(host[-1])}
+        return {"stats": stats, "scores": scores, "lang_acc": lang_acc, "status": int(status[0])}
 
-    def records(self):
-        """the last repeat's per-description records read back once -> dict of numpy arrays (keep_predictions only)"""
+    def _filled(self):
         if not self.keep_predictions:
             raise ValueError("GroundingEvaluator: constructed without keep_predictions")
         if self._rec is None:
             raise ValueError("GroundingEvaluator: no batch was added")
-        return {k: t[:self._rows].cpu().numpy() for k, t in self._rec.items()}
+        return self._rec.filled()
+
+    def records(self):
+        """the last repeat's per-description records read back once -> dict of numpy arrays (keep_predictions only)"""
+        self._filled()
+        return self._rec.read_back()[0]
+
+    @staticmethod
+    def _tree(ids, chunked_data, entry):
+        out = {}
+        for i, (scene, chunk) in enumerate(ids):
+            ann = chunked_data[scene][chunk]
+            out.setdefault(ann["scene_id"], {}).setdefault(ann["object_id"], {})[ann["ann_id"]] = entry(i)
+        return out
 
     def device_predictions(self, chunked_data):
         """`predictions` for the box writer (d3net_amd.visualize.visualize_grounding): the same tree, but "pred_bbox" / "gt_bbox" are
         rows of the device records (views, (8,3) float32) and there is no "iou"; only the (rows, 2) ids are read back"""
-        if not self.keep_predictions:
-            raise ValueError("GroundingEvaluator: constructed without keep_predictions")
-        if self._rec is None:
-            raise ValueError("GroundingEvaluator: no batch was added")
-        pred, gt = self._rec["pred_bbox"][:self._rows], self._rec["gt_bbox"][:self._rows]
-        out = {}
-        for i, (scene, chunk) in enumerate(self._rec["ids"][:self._rows].cpu().tolist()):
-            ann = chunked_data[scene][chunk]
-            out.setdefault(ann["scene_id"], {}).setdefault(ann["object_id"], {})[ann["ann_id"]] = {"pred_bbox": pred[i], "gt_bbox": gt[i]}
-        return out
+        rec = self._filled()
+        return self._tree(rec["ids"].cpu().tolist(), chunked_data, lambda i: {"pred_bbox": rec["pred_bbox"][i], "gt_bbox": rec["gt_bbox"][i]})
 
     def predictions(self, chunked_data):
         """{scene_id: {object_id: {ann_id: {"pred_bbox", "gt_bbox", "iou"}}}} of the last repeat as scripts/eval.py:243-266 leaves it:
         `chunked_data[id][chunk_id]` names a row's annotation, later rows overwrite earlier ones"""
         rec = self.records()
-        out = {}
-        for i, (scene, chunk) in enumerate(rec["ids"].tolist()):
-            ann = chunked_data[scene][chunk]
-            out.setdefault(ann["scene_id"], {}).setdefault(ann["object_id"], {})[ann["ann_id"]] = {
-                "pred_bbox": rec["pred_bbox"][i], "gt_bbox": rec["gt_bbox"][i], "iou": rec["iou"][i]}
-        return out
+        return self._tree(rec["ids"].tolist(), chunked_data, lambda i: {k: rec[k][i] for k in ("pred_bbox", "gt_bbox", "iou")})

@@ -8,7 +8,7 @@ from torch.autograd import Function
 
 from . import _lib
 from ._lib import check
-from .pointgroup_ops import _on, _ptr, _stream, _workspace
+from ._call import _on, _ptr, _stream, _workspace
 
 TALL_ROWS = 8192   # below this the library GEMM is fine
 

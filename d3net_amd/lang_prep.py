@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib, scene_prep
-from .pointgroup_ops import _ptr, _stream
+from ._call import _ptr, _stream
 
 SCANNET_CLASSES = ("cabinet", "bed", "chair", "sofa", "table", "door", "window", "bookshelf", "picture", "counter", "desk", "curtain",
                    "refrigerator", "shower curtain", "toilet", "sink", "bathtub", "others")

@@ -23,7 +23,7 @@ from torch.nn.utils.rnn import pack_padded_sequence, pad_packed_sequence
 from . import _lib
 from . import nativelinear as NL
 from ._lib import check
-from .pointgroup_ops import _on, _ptr, _stream
+from ._call import _on, _ptr, _stream
 
 
 # ------------------------------------------------------------------------------------ attention core

@@ -25,6 +25,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._call import call, on, stream
 from ._lib import check
 
 _CODES = {torch.float32: 0, torch.float64: 1, torch.int32: 2, torch.int64: 3}   # D3_METRIC_* (include/d3hip.h)
@@ -143,11 +144,10 @@ class MetricLog:
         for i, ptr, code in rows:
             hv[i, 0] = ptr
             hv[i, 1] = code
-        with torch.cuda.device(self.device):
+        with on(self.device):
             self._table[:n].copy_(pin[:n], non_blocking=True)
             ev.record()
-            check(_lib.lib().d3_metric_accumulate(self._table.data_ptr(), n, self._rec_ptr(), torch.cuda.current_stream().cuda_stream),
-                  "metric_accumulate")
+            call("metric_accumulate", self._table.data_ptr(), n, self._rec_ptr(), stream())
         self._held = held        # alive until the launch that reads them is behind the next update's
 
     def _rec_ptr(self):
@@ -159,9 +159,8 @@ class MetricLog:
         self._host_newer = [False] * len(self._names)
         self._gen += 1
         if self._table is not None:
-            with torch.cuda.device(self.device):
-                check(_lib.lib().d3_metric_reset(self._records.data_ptr(), self._offset, self.capacity,
-                                                 torch.cuda.current_stream().cuda_stream), "metric_reset")
+            with on(self.device):
+                call("metric_reset", self._records.data_ptr(), self._offset, self.capacity, stream())
 
     # ------------------------------------------------------------------------------------------------- reading
     @staticmethod
@@ -234,7 +233,7 @@ class MetricLog:
                 self._snap_free = [torch.zeros((self.capacity, _FIELDS), dtype=torch.float64).pin_memory() for _ in range(self.SNAPSHOTS)]
             if self._snap_free:
                 pin = self._snap_free.pop()
-                with torch.cuda.device(self.device):
+                with on(self.device):
                     pin[:n].copy_(self._records[self._offset:self._offset + n], non_blocking=True)
                     ev = torch.cuda.Event()
                     ev.record()

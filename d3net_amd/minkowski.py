@@ -25,7 +25,7 @@ from torch.autograd import Function
 
 from . import _lib
 from ._lib import check
-from .pointgroup_ops import _on, _ptr, _stream, _workspace
+from ._call import _on, _ptr, _stream, _workspace
 
 D3_CONV_FLIPK, D3_CONV_TRANSW, D3_CONV_EXACT, D3_CONV_XSTAT, D3_CONV_ACCUM, D3_CONV_XBF16, D3_CONV_DYBF16 = 1, 2, 4, 8, 16, 32, 64
 D3_CONV_F32 = 256   # reference precision on the matrix cores: fp32 operands, v_mfma_f32_16x16x4_f32 (csrc/spconv2.hip)

@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .pointgroup_ops import _ptr, _stream
+from ._call import _ptr, _stream
 
 # project_multiview_features.py:22-23
 INTRINSICS = [[37.01983, 0, 20, 0], [0, 38.52470, 15.5, 0], [0, 0, 1, 0], [0, 0, 0, 1]]

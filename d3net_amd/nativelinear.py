@@ -14,7 +14,7 @@ from torch.autograd import Function
 
 from . import _lib
 from ._lib import GemmProb, GemmSeg, check
-from .pointgroup_ops import _on, _ptr, _stream, _workspace
+from ._call import _on, _ptr, _stream, _workspace
 
 
 def _seg(A, lda, a_km, B, ldb, b_km, K):

@@ -17,7 +17,7 @@ from torch.autograd import Function
 from . import _lib, common
 from . import minkowski as ME
 from ._lib import check
-from .pointgroup_ops import _on, _stream
+from ._call import _on, _stream
 
 OP_CONV, OP_BNACT, OP_PADCAST, OP_STATS = 1, 2, 3, 4
 MAP_K1, MAP_K3, MAP_DOWN, MAP_UP = 0, 1, 2, 3

@@ -43,7 +43,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import check
+from ._call import call, on, stream
 
 
 _DATA_PTR = operator.methodcaller("data_ptr")
@@ -108,23 +108,21 @@ class _FusedTable(torch.optim.Optimizer):
         buffer, one d3_grad_clip_finish; -> the record's address for the _clipped entries (None: clipping is off)"""
         if self.max_grad_norm is None or not tables:
             return None
-        L = _lib.lib()
         ctl = self._record()
         dev = ctl.device
         total = sum(tb["nblocks"] for _g, tb in tables)
         if self._partials is None or self._partials.numel() < total:
             self._partials = torch.empty(total, dtype=torch.float64, device=dev)
-        with torch.cuda.device(dev):
-            st = torch.cuda.current_stream().cuda_stream
+        with on(dev):
+            st = stream()
             o = 0
             for _g, tb in tables:
                 if tb["device"] != dev:
                     raise RuntimeError("%s: max_grad_norm needs every group on one device" % type(self).__name__)
-                check(L.d3_grad_sumsq(tb["ptrs"].data_ptr(), tb["numel"].data_ptr(), tb["blocks"].data_ptr(), tb["nblocks"],
-                                      self._partials.data_ptr() + 8 * o, st), "grad_sumsq")
+                call("grad_sumsq", tb["ptrs"].data_ptr(), tb["numel"].data_ptr(), tb["blocks"].data_ptr(), tb["nblocks"],
+                     self._partials.data_ptr() + 8 * o, st)
                 o += tb["nblocks"]
-            check(L.d3_grad_clip_finish(self._partials.data_ptr(), total, float(self.max_grad_norm), ctl.data_ptr(), st),
-                  "grad_clip_finish")
+            call("grad_clip_finish", self._partials.data_ptr(), total, float(self.max_grad_norm), ctl.data_ptr(), st)
         return ctl.data_ptr()
 
     def _slots(self, group):
@@ -285,21 +283,21 @@ class _FusedMoments(_FusedTable):
         tables = self._resolve()
         ctl = self._measure(tables)
         name = self._ENTRY if ctl is None else self._ENTRY + "_clipped"
-        entry, tail = getattr(_lib.lib(), name), (() if ctl is None else (ctl,))
+        tail = () if ctl is None else (ctl,)
         for group, tb in tables:
             b1, b2 = group["betas"]
-            with torch.cuda.device(tb["device"]):
-                st = torch.cuda.current_stream().cuda_stream
+            with on(tb["device"]):
+                st = stream()
                 for co in tb["cohorts"]:       # tensors with the same number of updates behind them: one launch
                     co[0] = t = co[0] + 1      # also on a step the record makes the kernels skip: nothing is read back
-                    check(entry(tb["ptrs"].data_ptr(), tb["numel"].data_ptr(), tb["blocks"].data_ptr() + 8 * co[3], co[4],
-                                float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]),
-                                1.0 - b1 ** t, math.sqrt(1.0 - b2 ** t), *tail, st), name[3:])
+                    call(name, tb["ptrs"].data_ptr(), tb["numel"].data_ptr(), tb["blocks"].data_ptr() + 8 * co[3], co[4],
+                         float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]),
+                         1.0 - b1 ** t, math.sqrt(1.0 - b2 ** t), *tail, st)
         return loss
 
 
 class FusedAdamW(_FusedMoments):
-    _ENTRY = "d3_adamw"
+    _ENTRY = "adamw"
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=None, skip_nonfinite=True):
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay), max_grad_norm, skip_nonfinite)
@@ -308,7 +306,7 @@ class FusedAdamW(_FusedMoments):
 class FusedAdam(_FusedMoments):
     """torch.optim.Adam (amsgrad = maximize = False) in one launch: FusedAdamW's state and step counts, L2 weight decay
     (`g + weight_decay * p` enters both moments) instead of the decoupled one.  Checkpoints interchange with torch.optim.Adam."""
-    _ENTRY = "d3_adam"
+    _ENTRY = "adam"
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, max_grad_norm=None, skip_nonfinite=True,
                  **unsupported):
@@ -359,15 +357,13 @@ class FusedSGD(_FusedTable):
                 del self._tables[gi]
         tables = self._resolve()
         ctl = self._measure(tables)
-        name = "d3_sgd" if ctl is None else "d3_sgd_clipped"
-        entry, tail = getattr(_lib.lib(), name), (() if ctl is None else (ctl,))
+        name, tail = ("sgd", ()) if ctl is None else ("sgd_clipped", (ctl,))
         for group, tb in tables:
-            with torch.cuda.device(tb["device"]):
-                st = torch.cuda.current_stream().cuda_stream
+            with on(tb["device"]):
+                st = stream()
                 for co in tb["cohorts"]:       # buffer owners, then the tensors updated for the first time
-                    check(entry(tb["ptrs"].data_ptr(), tb["numel"].data_ptr(), tb["blocks"].data_ptr() + 8 * co[3], co[4],
-                                float(group["lr"]), float(group["momentum"]), float(group["weight_decay"]), int(co[0] == 0),
-                                *tail, st), name[3:])
+                    call(name, tb["ptrs"].data_ptr(), tb["numel"].data_ptr(), tb["blocks"].data_ptr() + 8 * co[3], co[4],
+                         float(group["lr"]), float(group["momentum"]), float(group["weight_decay"]), int(co[0] == 0), *tail, st)
             if len(tb["cohorts"]) > 1 or tb["cohorts"][0][0] == 0:      # every tensor owns a buffer now: one cohort, one launch
                 tb["cohorts"] = [[1, 0, len(tb["plist"]), 0, tb["nblocks"]]]
         return loss

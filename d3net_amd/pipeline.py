@@ -11,6 +11,7 @@ import torch
 import torch.nn as nn
 
 from .captioning_loss import get_captioning_loss
+from .devstate import evaluating
 from .listener import ListenerNet, get_grounding_loss, get_lobjcls_loss
 from .pointgroup import PointGroup, _mark
 from .speaker import SpeakerNet
@@ -283,16 +284,11 @@ class PipelineNet(nn.Module):
         if ev is None:
             ev = CaptionEvaluator(self.val_raw_data or [], self.vocabulary, max_len=self.cfg.eval.max_des_len + 2,
                                   min_iou=self.cfg.eval.min_iou_threshold, device=next(self.parameters()).device)
-        was_training = self.training
-        self.eval()
-        try:
-            with torch.no_grad():
-                for batch in batches:
-                    self._lazy_proposals = False
-                    d = self.speaker(self._detect(batch), use_tf=False, use_rl=False, is_eval=True, beam_opt=self.beam_opt)
-                    ev.add_batch(d)
-        finally:
-            self.train(was_training)
+        with evaluating(self):
+            for batch in batches:
+                self._lazy_proposals = False
+                d = self.speaker(self._detect(batch), use_tf=False, use_rl=False, is_eval=True, beam_opt=self.beam_opt)
+                ev.add_batch(d)
         bleu, cider, rouge, meteor = ev.compute()
         return {"bleu-1": bleu[0][0], "bleu-2": bleu[0][1], "bleu-3": bleu[0][2], "bleu-4": bleu[0][3], "cider": cider[0],
                 "meteor": meteor[0], "rouge": rouge[0]}
@@ -317,18 +313,13 @@ class PipelineNet(nn.Module):
         ev = evaluator
         if ev is None:
             ev = GroundingEvaluator(use_lang_classifier=self.use_lang_classifier, device=next(self.parameters()).device)
-        was_training = self.training
-        self.eval()
-        try:
-            with torch.no_grad():
-                for seed in seeds:
-                    torch.manual_seed(seed); np.random.seed(seed)
-                    ev.begin_repeat()
-                    for batch in (batches() if callable(batches) else batches):
-                        self._lazy_proposals = False
-                        ev.add_batch(self._ground(self.listener(self._detect(dict(batch))), False))
-        finally:
-            self.train(was_training)
+        with evaluating(self):
+            for seed in seeds:
+                torch.manual_seed(seed); np.random.seed(seed)
+                ev.begin_repeat()
+                for batch in (batches() if callable(batches) else batches):
+                    self._lazy_proposals = False
+                    ev.add_batch(self._ground(self.listener(self._detect(dict(batch))), False))
         return ev.compute()
 
     def visualize_grounding(self, batches, root, evaluator=None, seeds=None, per_annotation_boxes=False, on_degenerate="raise"):
@@ -372,15 +363,10 @@ class PipelineNet(nn.Module):
         return store
 
     def _predict(self, batches, submission, head):
-        was_training = self.training
-        self.eval()
-        try:
-            with torch.no_grad():
-                for batch in batches:
-                    self._lazy_proposals = False
-                    submission.add_batch(head(self._feed_only(dict(batch))))
-        finally:
-            self.train(was_training)
+        with evaluating(self):
+            for batch in batches:
+                self._lazy_proposals = False
+                submission.add_batch(head(self._feed_only(dict(batch))))
         return submission
 
     def predict_captioning(self, batches, submission=None):

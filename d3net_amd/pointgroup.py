@@ -27,6 +27,7 @@ from . import minkowski as ME
 from . import nativelinear
 from . import netexec
 from . import pointgroup_ops
+from .devstate import evaluating
 
 
 class _HostStage:
@@ -893,8 +894,8 @@ class PointGroup(nn.Module):
         score / size thresholds, point-mask NMS (lib/utils/eval.py:75-97).  Device-side: the pairwise mask IoUs come from the
         (cluster, point) lists (csrc/nms.hip) instead of a dense (nProposal, N) mask product and a host copy.
         -> dict(pick (n,) indices into the proposals, scores (n,), proposals_idx, proposals_offset, semantic_pred (N,))"""
-        import ctypes as C
         from . import _lib
+        from ._call import call, on, ptr, stream
         data_dict = self.feed(data_dict, self.current_epoch)
         scores, proposals_idx, proposals_offset = data_dict["proposal_scores"][:3]
         sem_pred = data_dict["semantic_scores"].max(1)[1]
@@ -911,13 +912,11 @@ class PointGroup(nn.Module):
         flags = torch.zeros(2, dtype=torch.int32, device=dev)
         order = torch.empty(P, dtype=torch.int32, device=dev)
         picked = torch.empty(P, dtype=torch.int32, device=dev)
-        L = _lib.lib()
         cidx, off = proposals_idx.contiguous(), proposals_offset.contiguous()
-        p_, st = (lambda t: C.c_void_p(t.data_ptr())), C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        with torch.cuda.device(dev):
-            _lib.check(L.d3_instance_cross_iou(p_(cidx), p_(off), cidx.shape[0], P, N, p_(ious), p_(member), p_(flags), st), "instance_cross_iou")
-            _lib.check(L.d3_nms_matrix(p_(ious), p_(sig), p_(keep), P, float(self.cfg.test.TEST_NMS_THRESH), p_(order), p_(picked),
-                                       p_(flags[1:]), st), "nms_matrix")
+        with on(dev):
+            call("instance_cross_iou", ptr(cidx), ptr(off), cidx.shape[0], P, N, ptr(ious), ptr(member), ptr(flags), stream())
+            call("nms_matrix", ptr(ious), ptr(sig), ptr(keep), P, float(self.cfg.test.TEST_NMS_THRESH), ptr(order), ptr(picked),
+                 ptr(flags[1:]), stream())
         over, n = flags.tolist()
         if over:
             raise _lib.D3Error("predict_instances: a point belongs to more than two proposals")
@@ -931,14 +930,10 @@ class PointGroup(nn.Module):
         counting of each batch on the device (seg_eval.SegmentationEvaluator) -> (instance averages dict, semantic IoU dict)"""
         from .seg_eval import SegmentationEvaluator
         ev = evaluator if evaluator is not None else SegmentationEvaluator()
-        was_training = self.training
-        self.eval()
-        try:
+        with evaluating(self):
             for batch in batches:
                 gt = {k: batch[k] for k in ("sem_labels", "instance_ids", "batch_offsets", "instance_offsets") if k in batch}
                 ev.add_batch(self.predict_instances(batch), gt)
-        finally:
-            self.train(was_training)
         return ev.instance_results()[0], ev.semantic_results()[0]
 
     def evaluate_detection(self, batches, evaluator=None):
@@ -948,14 +943,9 @@ class PointGroup(nn.Module):
         -> one APCalculator-shaped dict per IoU threshold (0.25 and 0.5 by default)"""
         from .evaluator import DetectionEvaluator
         ev = evaluator if evaluator is not None else DetectionEvaluator()
-        was_training = self.training
-        self.eval()
-        try:
-            with torch.no_grad():
-                for batch in batches:
-                    ev.add_batch(self.feed(batch, self.current_epoch))
-        finally:
-            self.train(was_training)
+        with evaluating(self):
+            for batch in batches:
+                ev.add_batch(self.feed(batch, self.current_epoch))
         return ev.compute_metrics()
 
     def training_step(self, data_dict, idx=0):

@@ -13,67 +13,13 @@ Differences from the reference, all at the edges:
 There is no CPU implementation here: without a GPU these functions raise.
 """
 import ctypes as C
-import threading
 
 import torch
 from torch.autograd import Function
 
 from . import _lib
 from ._lib import check
-
-_ws_cache = {}
-
-
-# the calling thread's current stream / device straight from the runtime bindings: `torch.cuda.current_stream()` builds a
-# Stream object (~5 us) and `torch.cuda.current_device()` walks the lazy-init checks; at ~45 library calls per step inside
-# the host-bound stretches of the step (after a count phase the host has no lead over the GPU) that is time the GPU waits for
-_RAW_STREAM = getattr(torch._C, "_cuda_getCurrentRawStream", None)
-_RAW_DEVICE = getattr(torch._C, "_cuda_getDevice", None)
-
-
-def _stream():
-    if _RAW_STREAM is not None and _RAW_DEVICE is not None:
-        return C.c_void_p(_RAW_STREAM(_RAW_DEVICE()))
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr())
-
-
-def _workspace(nbytes, device, tag):
-    """A cached, growing device scratch buffer per (device, tag, host thread, current stream)."""
-    # per host thread AND per stream: the two clustering branches of PointGroup.forward run concurrently on their own streams, from
-    # two threads (the helper-thread fallback beyond the padded lists' budget) or from one -- and a call may return with kernels that read its workspace still in flight
-    # (d3_bfs_cluster_run's speculative fill), so one thread driving two streams must never hand both the same buffer (r05_f: the
-    # 16-scene batch, whose lists go the compact way, faulted exactly so)
-    key = (device.index if device.index is not None else torch.cuda.current_device(), tag, threading.get_ident(),
-           (_stream().value or 0) if device.type == "cuda" else 0)
-    buf = _ws_cache.get(key)
-    if buf is None or buf.numel() < nbytes:
-        buf = torch.empty(int(nbytes * 1.25) + 1024, dtype=torch.uint8, device=device)
-        _ws_cache[key] = buf
-    return buf
-
-
-class _NoGuard:
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        return False
-
-
-_NOGUARD = _NoGuard()
-
-
-def _on(device):
-    """device guard for the raw library calls: a no-op (sub-microsecond) when `device` is already current --
-    `torch.cuda.device(...)` costs ~10 us per use, which at ~600 operator calls per step is host time the GPU waits for"""
-    if device.index is None:
-        return _NOGUARD
-    cur = _RAW_DEVICE() if _RAW_DEVICE is not None else torch.cuda.current_device()
-    return _NOGUARD if device.index == cur else torch.cuda.device(device)
+from ._call import _on, _ptr, _stream, _workspace  # noqa: F401 -- tests and tools import the four from here
 
 
 def _device_of(*tensors):

@@ -28,7 +28,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .pointgroup_ops import _ptr, _stream
+from ._call import _ptr, _stream
 
 # prepare_scannet.py:13, :23-25; prepare_scannet_inst_gt.py:15
 DONOTCARE_CLASS_IDS = (1, 2, 22)

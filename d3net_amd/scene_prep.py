@@ -24,7 +24,7 @@ import numpy as np
 import torch
 
 from . import _lib, pointgroup_ops
-from .pointgroup_ops import _ptr, _stream
+from ._call import _ptr, _stream
 
 _NOISE_MODES = ("host", "device")
 

@@ -10,7 +10,6 @@ Split as `evaluator.py` splits the detection metric:
     get_semantic_iou :28-44) run on the host in float64 numpy over those counts -- an epoch-end metric.
 File interop: `write_predictions` / `write_gt` produce the reference's file layout and formats (model/pointgroup.py:603-625,
 lib/utils/eval.py:14-56), `evaluate_*_files` score such files (ours or the reference's) through the same device counting."""
-import ctypes as C
 import math
 import os
 
@@ -40,6 +39,7 @@ def count(gt_sem, gt_inst, pred_sem, batch_offsets, pick=None, proposals_idx=Non
     flags], inter (n,G).  Raises D3Error (D3_ERR_RANGE) when a scene has more instances than the kernel's LDS bound."""
     import torch
     from . import _lib
+    from ._call import call, on, ptr, stream
     dev = gt_sem.device
     i32 = lambda t: t.to(device=dev, dtype=torch.int32).contiguous()
     gs, gi, ps = i32(gt_sem), i32(gt_inst), i32(pred_sem)
@@ -60,14 +60,10 @@ def count(gt_sem, gt_inst, pred_sem, batch_offsets, pick=None, proposals_idx=Non
     bo = torch.from_numpy(bo_h.astype(np.int32)).to(dev)
     z = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=dev)
     conf, gts, pst, inter, status = z(NUM_IDS, NUM_IDS), z(B, max(G, 1), 2), z(max(n, 1), 5), z(max(n, 1), max(G, 1)), z(1)
-    L = _lib.lib()
-    ws = torch.empty(max(int(L.d3_seg_eval_ws_bytes(B, G)), 4), dtype=torch.uint8, device=dev)
-    p_ = lambda t: C.c_void_p(t.data_ptr())
-    with torch.cuda.device(dev):
-        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        _lib.check(L.d3_seg_eval(p_(gs), p_(gi), p_(ps), p_(bo), B, N, int(np.diff(bo_h).max()), G, p_(pk), n, p_(pidx), p_(poff),
-                                 P, S, INST_CLASS_MASK, p_(conf), p_(gts), p_(pst), p_(inter), p_(status), p_(ws), ws.numel(), st),
-                   "seg_eval")
+    ws = torch.empty(max(int(_lib.lib().d3_seg_eval_ws_bytes(B, G)), 4), dtype=torch.uint8, device=dev)
+    with on(dev):
+        call("seg_eval", ptr(gs), ptr(gi), ptr(ps), ptr(bo), B, N, int(np.diff(bo_h).max()), G, ptr(pk), n, ptr(pidx), ptr(poff),
+             P, S, INST_CLASS_MASK, ptr(conf), ptr(gts), ptr(pst), ptr(inter), ptr(status), ptr(ws), ws.numel(), stream())
     if int(status.item()):
         raise ValueError("seg_eval: point labels outside [0, 40) or instance ids outside [0, G]")
     gts = gts.cpu().numpy()[:, :G]

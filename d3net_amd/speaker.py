@@ -25,7 +25,7 @@ import torch.nn.functional as F
 from . import _lib
 from . import nativelinear
 from ._lib import check
-from .pointgroup_ops import _on, _ptr, _stream
+from ._call import _on, _ptr, _stream
 
 JOINED_DECODES = True   # the self-critical step's beam search and greedy baseline as one chain (tools/ab.py py:d3net_amd.speaker.JOINED_DECODES=0,1)
 

@@ -15,44 +15,22 @@ import json
 import numpy as np
 import torch
 
-from .evaluator import POST_DICT
+from . import _lib
+from ._call import call, on, ptr, stream
+from .devstate import FLAGS, FLOATS, GROUND_MAX_K, INTS, RecordStore, as_i64, check_batch, read_back
+from .evaluator import POST_DICT, nms_pred_mask_device
 
 SUBMIT_MAX_K, SUBMIT_MAX_TOKENS, SUBMIT_MAX_ROWS = 256, 62, 1 << 20      # proposal slots / caption tokens / rows per batch of csrc/submission.hip
-GROUND_MAX_K = 4096
 NUM_CLASS = 18
-_INTS = (torch.int32, torch.int64)
-_FLAGS = (torch.float32, torch.bool, torch.uint8) + _INTS
-_CAP_KEYS = ("proposal_bbox_batched", "proposal_sem_cls_batched", "proposal_scores_batched", "proposal_batch_mask", "lang_cap", "id")
-_GROUND_KEYS = ("cluster_ref", "proposal_bbox_batched", "unique_multiple", "object_cat", "id", "chunk_ids")
-
-
-def _on_gpu(name, d, keys, device, state):
-    for k in keys:
-        t = d[k]
-        if not t.is_cuda:
-            raise ValueError("%s: %s is in host memory (%s); the writers run on the GPU, there is no CPU fallback" % (name, k, t.device))
-        if (device.index is not None and t.device != device) or t.device != d[keys[0]].device or (state is not None and t.device != state.device):
-            raise ValueError("%s: %s is on %s; the batches of one submission live on one GPU (%s)" % (name, k, t.device, device))
-
-
-def _present(name, d, keys):
-    missing = [k for k in keys if k not in d]
-    if missing:
-        raise ValueError("%s: missing %s" % (name, missing))
-    for k in keys:
-        if not torch.is_tensor(d[k]):
-            raise ValueError("%s: %s must be a tensor" % (name, k))
-
-
-def _bytes_back(tensors):
-    """the one read-back: the tensors as one byte run -> numpy arrays of their dtypes and shapes"""
-    flat = torch.cat([t.contiguous().view(-1).view(torch.uint8) for t in tensors]).cpu().numpy()
-    out, pos = [], 0
-    for t in tensors:
-        n = t.numel() * t.element_size()
-        out.append(flat[pos:pos + n].view(np.dtype(str(t.dtype).replace("torch.", ""))).reshape(tuple(t.shape)))
-        pos += n
-    return out
+_ROWS = (("B", "C"), ("N",))                                              # one value per description, batched or flat
+_CAP_TABLE = {"proposal_bbox_batched": (FLOATS, None), "proposal_sem_cls_batched": (FLOATS, (("B", "K"),)),
+              "proposal_scores_batched": (FLOATS, (("B", "K"),)), "proposal_batch_mask": (FLAGS, (("B", "K"),)),
+              "lang_cap": ((torch.int64,), (("B", "K", "T"),)), "id": (INTS, (("B",),))}
+_CAP_STATE = ("box", "cls", "score", "ntok", "tok", "count", "first_seen", "status")         # the state `records` reads back
+_GROUND_TABLE = {"cluster_ref": (FLOATS, None), "proposal_bbox_batched": (FLOATS, None), "unique_multiple": (INTS, _ROWS),
+                 "object_cat": (INTS, _ROWS), "id": (INTS, (("B",),)), "chunk_ids": (INTS, (("B", "C"),))}
+_GROUND_REC = dict(bbox=((8, 3), torch.float32), pred_ref=((), torch.int32), unique_multiple=((), torch.int64), others=((), torch.int32),
+                   key=((), torch.int32), keep=((), torch.int32), ids=((2,), torch.int64))
 
 
 class CaptionSubmission:
@@ -95,38 +73,28 @@ class CaptionSubmission:
     def reset(self):
         self._state, self._seq = None, 0
 
-    def _checked(self, d):
+    def _geometry(self, d):
         name = "CaptionSubmission.add_batch"
-        _present(name, d, _CAP_KEYS)
-        boxes, sem, scores, mask, caps, ids = (d[k] for k in _CAP_KEYS)
+        boxes, caps = d["proposal_bbox_batched"], d["lang_cap"]
         if boxes.dim() != 4 or tuple(boxes.shape[2:]) != (8, 3):
             raise ValueError("%s: proposal_bbox_batched (B,K,8,3) expected, got %s" % (name, tuple(boxes.shape)))
         B, K = boxes.shape[:2]
         if not 1 <= B <= SUBMIT_MAX_ROWS or not 1 <= K <= self.max_proposals:
             raise ValueError("%s: 1 <= B <= %d and 1 <= K <= %d (got B %d, K %d)" % (name, SUBMIT_MAX_ROWS, self.max_proposals, B, K))
-        for k in _CAP_KEYS[1:4]:
-            if tuple(d[k].shape) != (B, K):
-                raise ValueError("%s: %s has shape %s, expected %s" % (name, k, tuple(d[k].shape), (B, K)))
-        if caps.dim() != 3 or tuple(caps.shape[:2]) != (B, K):
+        if caps.dim() != 3:
             raise ValueError("%s: lang_cap has shape %s, expected (%d, %d, T)" % (name, tuple(caps.shape), B, K))
         T = caps.shape[2]
         if not 1 <= T <= self.max_len:
             raise ValueError("%s: captions of T = %d tokens, the state holds 1 <= T <= %d" % (name, T, self.max_len))
-        if tuple(ids.shape) != (B,):
-            raise ValueError("%s: id has shape %s, expected %s" % (name, tuple(ids.shape), (B,)))
-        floats = (torch.float32,)
-        ok = dict(zip(_CAP_KEYS, (floats, floats, floats, _FLAGS, (torch.int64,), _INTS)))
-        for k in _CAP_KEYS:
-            if d[k].dtype not in ok[k]:
-                raise ValueError("%s: %s has dtype %s, expected one of %s" % (name, k, d[k].dtype, ok[k]))
-        _on_gpu(name, d, _CAP_KEYS, self.device, None if self._state is None else self._state["status"])
-        return B, K, T
+        return dict(B=B, K=K, T=T)
+
+    def _checked(self, d):
+        dims = check_batch("CaptionSubmission.add_batch", d, _CAP_TABLE, self._geometry, self.device,
+                           None if self._state is None else self._state["status"])
+        return dims["B"], dims["K"], dims["T"]
 
     def add_batch(self, data_dict):
         """two launches (d3_nms3d_samecls, d3_caption_submit_batch), nothing read back; `data_dict` is left as it is"""
-        import ctypes as C
-        from . import _lib
-        from .evaluator import nms_pred_mask_device
         d = data_dict
         B, K, T = self._checked(d)
         dev = d["lang_cap"].device
@@ -139,25 +107,22 @@ class CaptionSubmission:
                                table=torch.from_numpy(self._table).to(dev))
         st = self._state
         pick = nms_pred_mask_device(d, self.nms_iou, self.old_type)
-        boxes, sem, scores = (d[k].detach().contiguous() for k in _CAP_KEYS[:3])
-        caps, ids = d["lang_cap"].detach().contiguous(), d["id"].detach().long().contiguous()
-        p = lambda t: C.c_void_p(t.data_ptr())
-        with torch.cuda.device(dev):
-            _lib.check(_lib.lib().d3_caption_submit_batch(
-                p(boxes), p(sem), p(scores), p(pick), p(caps), p(ids), p(st["table"]), st["table"].numel(), B, K, T, self.V, self.eos, self._seq,
-                len(self.scene_ids), self.max_proposals, self.max_len, p(st["box"]), p(st["cls"]), p(st["score"]), p(st["ntok"]), p(st["tok"]),
-                p(st["count"]), p(st["first_seen"]), p(st["status"]), C.c_void_p(torch.cuda.current_stream().cuda_stream)), "caption_submit_batch")
+        boxes, sem, scores, caps = (d[k].detach().contiguous() for k in ("proposal_bbox_batched", "proposal_sem_cls_batched",
+                                                                         "proposal_scores_batched", "lang_cap"))
+        ids = as_i64(d["id"])
+        with on(dev):
+            call("caption_submit_batch", ptr(boxes), ptr(sem), ptr(scores), ptr(pick), ptr(caps), ptr(ids), ptr(st["table"]),
+                 st["table"].numel(), B, K, T, self.V, self.eos, self._seq, len(self.scene_ids), self.max_proposals, self.max_len,
+                 *[ptr(st[k]) for k in _CAP_STATE], stream())
         self._seq += 1
 
     def records(self):
         """the state read back once -> dict of numpy arrays (box, cls, score, ntok, tok, count, first_seen, status)"""
         if self._state is None:
             raise ValueError("CaptionSubmission: no batch was added")
-        keys = ("box", "cls", "score", "ntok", "tok", "count", "first_seen", "status")
-        return dict(zip(keys, _bytes_back([self._state[k] for k in keys])))
+        return dict(zip(_CAP_STATE, read_back([self._state[k] for k in _CAP_STATE])))
 
     def results(self):
-        from . import _lib
         rec = self.records()
         status = int(rec["status"][0])
         if status & 1:
@@ -214,11 +179,10 @@ class GroundingSubmission:
 
     def reset(self):
         self._rec = self._status = self._key_of = None
-        self._rows = 0
 
-    def _checked(self, d):
+    @staticmethod
+    def _geometry(d):
         name = "GroundingSubmission.add_batch"
-        _present(name, d, _GROUND_KEYS)
         ref, boxes = d["cluster_ref"], d["proposal_bbox_batched"]
         if ref.dim() != 2 or boxes.dim() != 4 or tuple(boxes.shape[2:]) != (8, 3):
             raise ValueError("%s: cluster_ref (N,K) and proposal_bbox_batched (B,K,8,3) expected" % name)
@@ -226,56 +190,38 @@ class GroundingSubmission:
         if B < 1 or N < 1 or N % B or not 1 <= K <= GROUND_MAX_K or boxes.shape[1] != K:
             raise ValueError("%s: B >= 1, N = B * C >= 1 and 1 <= K <= %d, the same for scores and boxes (got B %d, N %d, K %d and %d)"
                              % (name, GROUND_MAX_K, B, N, K, boxes.shape[1]))
-        Cn = N // B
-        want = {"unique_multiple": ((B, Cn), (N,)), "object_cat": ((B, Cn), (N,)), "id": ((B,),), "chunk_ids": ((B, Cn),)}
-        for k, shapes in want.items():
-            if tuple(d[k].shape) not in shapes:
-                raise ValueError("%s: %s has shape %s, expected %s" % (name, k, tuple(d[k].shape), " or ".join(map(str, shapes))))
-        floats = (torch.float32,)
-        ok = dict(zip(_GROUND_KEYS, (floats, floats, _INTS, _INTS, _INTS, _INTS)))
-        for k in _GROUND_KEYS:
-            if d[k].dtype not in ok[k]:
-                raise ValueError("%s: %s has dtype %s, expected one of %s" % (name, k, d[k].dtype, ok[k]))
-        _on_gpu(name, d, _GROUND_KEYS, self.device, self._status)
-        return B, Cn, K, N
+        return dict(B=B, C=N // B, K=K, N=N)
+
+    def _checked(self, d):
+        dims = check_batch("GroundingSubmission.add_batch", d, _GROUND_TABLE, self._geometry, self.device, self._status)
+        return tuple(dims[k] for k in "BCKN")
 
     def add_batch(self, data_dict):
         """one launch, nothing read back; `data_dict` is left as it is"""
-        import ctypes as C
-        from . import _lib
-        from .grounding_eval import GroundingEvaluator
         d = data_dict
         B, Cn, K, N = self._checked(d)
         dev = d["cluster_ref"].device
         if self._status is None:
             self._status = torch.zeros(1, dtype=torch.int32, device=dev)
             self._key_of = torch.from_numpy(self._table).to(dev)
-            z = lambda shape, dt: torch.zeros((1024,) + shape, dtype=dt, device=dev)
-            self._rec = dict(bbox=z((8, 3), torch.float32), pred_ref=z((), torch.int32), unique_multiple=z((), torch.int64),
-                             others=z((), torch.int32), key=z((), torch.int32), keep=z((), torch.int32), ids=z((2,), torch.int64))
-        self._rec = {k: GroundingEvaluator._grown(t, self._rows + N) for k, t in self._rec.items()}
-        i64 = lambda t: t.detach().contiguous() if t.dtype == torch.int64 else t.detach().long().contiguous()
-        ref, boxes = d["cluster_ref"].detach().contiguous(), d["proposal_bbox_batched"].detach().contiguous()
-        um, cat, ids, chunks = (i64(d[k]) for k in _GROUND_KEYS[2:])
-        p = lambda t: C.c_void_p(t.data_ptr())
+            self._rec = RecordStore(dev, **_GROUND_REC)
         r = self._rec
-        with torch.cuda.device(dev):
-            _lib.check(_lib.lib().d3_ground_submit_batch(
-                p(ref), p(boxes), p(um), p(cat), p(ids), p(chunks), p(self._key_of), self._table.shape[0], self._table.shape[1], B, Cn, K,
-                self._rows, p(r["bbox"]), p(r["pred_ref"]), p(r["unique_multiple"]), p(r["others"]), p(r["key"]), p(r["keep"]), p(r["ids"]),
-                p(self._status), C.c_void_p(torch.cuda.current_stream().cuda_stream)), "ground_submit_batch")
-        self._rows += N
+        r.reserve(r.rows + N)
+        ref, boxes = d["cluster_ref"].detach().contiguous(), d["proposal_bbox_batched"].detach().contiguous()
+        um, cat, ids, chunks = (as_i64(d[k]) for k in ("unique_multiple", "object_cat", "id", "chunk_ids"))
+        with on(dev):
+            call("ground_submit_batch", ptr(ref), ptr(boxes), ptr(um), ptr(cat), ptr(ids), ptr(chunks), ptr(self._key_of),
+                 self._table.shape[0], self._table.shape[1], B, Cn, K, r.rows, *[ptr(r[k]) for k in _GROUND_REC], ptr(self._status), stream())
+        r.rows += N
 
     def records(self):
         """the rows read back once -> dict of numpy arrays (bbox, pred_ref, unique_multiple, others, key, keep, ids, status)"""
         if self._rec is None:
             raise ValueError("GroundingSubmission: no batch was added")
-        keys = tuple(self._rec)
-        back = _bytes_back([self._rec[k][:self._rows] for k in keys] + [self._status])
-        return dict(zip(keys + ("status",), back))
+        rec, (status,) = self._rec.read_back(self._status)
+        return dict(rec, status=status)
 
     def results(self):
-        from . import _lib
         rec = self.records()
         if int(rec["status"][0]) & 1:
             raise _lib.D3Error("GroundingSubmission: an `id` / `chunk_ids` pair names no annotation of chunked_data")

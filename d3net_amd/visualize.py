@@ -13,11 +13,15 @@ refused (or dropped, on_degenerate="skip"); the reference prints 110 lines of `n
 `write_aligned_mesh` writes the scene's mesh.ply itself; the reference writes it through plyfile, which is not a dependency here, so
 that file is NOT claimed to be byte-equal (see its docstring).  No CPU fallback: the vertices and the text come from the GPU.
 """
+import ctypes as C
 import math
 import os
 
 import numpy as np
 import torch
+
+from . import _lib
+from ._call import call, on, ptr, stream
 
 EDGES, STACKS, SLICES, RADIUS = 12, 10, 10, 0.03
 VERTS_PER_BOX = EDGES * (STACKS + 1) * SLICES           # 1320
@@ -31,7 +35,6 @@ _cache = {}
 
 def _ring():
     """0.03 cos / sin of the ten slice angles from the host's libm (create_cylinder_mesh, visualize_grounding.py:81-82)"""
-    import ctypes as C
     if "ring" not in _cache:
         theta = [i2 * 2.0 * math.pi / SLICES for i2 in range(SLICES)]
         _cache["ring"] = (C.c_double * 20)(*([RADIUS * math.cos(t) for t in theta] + [RADIUS * math.sin(t) for t in theta]))
@@ -64,8 +67,6 @@ def _file_parts():
 
 
 def _limits():
-    import ctypes as C
-    from . import _lib
     if "limits" not in _cache:
         v, s, f = C.c_int(0), C.c_int(0), C.c_int(0)
         _lib.check(_lib.lib().d3_box_wire_limits(C.byref(v), C.byref(s), C.byref(f)), "box_wire_limits")
@@ -141,7 +142,6 @@ def _upload(c, m, device):
 
 
 def _raise_status(name, status, offset=0):
-    from . import _lib
     bits, first = int(status[0]), int(status[1])
     text = "; ".join(t for b, t in sorted(_STATUS_TEXT.items()) if bits & b)
     raise _lib.D3Error("%s: box %d is the first outside the limits (%s)" % (name, first + offset, text))
@@ -152,8 +152,6 @@ def box_wireframes(corners, modes, device="cuda"):
     prediction -> (verts, faces, colors): verts (M,1320,3) float64 on the device, exactly the doubles the reference formats (one
     d3_box_wire_verts launch, nothing read back but the status word); faces the constant (2400,3) int32 host array of `wire_faces`;
     colors (M,3) uint8 host array, `0 255 0` or `0 0 255` per box.  Raises on a box outside the limits (module docstring)."""
-    import ctypes as C
-    from . import _lib
     name = "box_wireframes"
     c, m, _, dev_in, M = _boxes(corners, modes, name, "raise")
     colors = np.array([PALETTE[0], PALETTE[1]], np.uint8)[(m.cpu().numpy() if torch.is_tensor(m) else m)]
@@ -163,10 +161,8 @@ def box_wireframes(corners, modes, device="cuda"):
     _limits()
     verts = torch.empty((M, VERTS_PER_BOX, 3), dtype=torch.float64, device=c.device)
     status = torch.tensor([0, 0x7fffffff], dtype=torch.int32, device=c.device)
-    with torch.cuda.device(c.device):
-        _lib.check(_lib.lib().d3_box_wire_verts(C.c_void_p(c.data_ptr()), M, _ring(), C.c_void_p(verts.data_ptr()),
-                                                C.c_void_p(status.data_ptr()), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
-                   "box_wire_verts")
+    with on(c.device):
+        call("box_wire_verts", ptr(c), M, _ring(), ptr(verts), ptr(status), stream())
     st = status.cpu().numpy()
     if st[0]:
         _raise_status(name, st)
@@ -175,8 +171,6 @@ def box_wireframes(corners, modes, device="cuda"):
 
 def format_f6(values, device="cuda"):
     """"{:f}".format(v) of every double, formatted on the device (d3_format_f6) -> list of str.  |v| >= 1e15 (finite) is refused."""
-    import ctypes as C
-    from . import _lib
     if torch.is_tensor(values) and values.is_cuda:
         v = values.detach().double().contiguous().view(-1)
     else:
@@ -187,10 +181,8 @@ def format_f6(values, device="cuda"):
     slot = _limits()[1]
     buf = torch.empty(8 + 4 * n + slot * n, dtype=torch.uint8, device=v.device)
     buf[:8].zero_()
-    p = lambda o: C.c_void_p(buf.data_ptr() + o)
-    with torch.cuda.device(v.device):
-        _lib.check(_lib.lib().d3_format_f6(C.c_void_p(v.data_ptr()), n, p(8 + 4 * n), p(8), p(0),
-                                           C.c_void_p(torch.cuda.current_stream().cuda_stream)), "format_f6")
+    with on(v.device):
+        call("format_f6", ptr(v), n, ptr(buf[8 + 4 * n:]), ptr(buf[8:]), ptr(buf), stream())
     host = buf.cpu().numpy()
     lens = host[8:8 + 4 * n].view(np.int32)
     if host[:4].view(np.int32)[0]:
@@ -208,9 +200,7 @@ def write_box_plys(corners, modes, paths, chunk=4096, device="cuda", on_degenera
     on the device are checked by the kernel and raise D3Error, naming the first bad box, with no file of this call left on disk.
     on_degenerate="skip" drops such boxes instead.  Directories must exist.  timings: a dict that receives the seconds spent in
     launch + read-back ("device_s") and in writing files ("files_s"), for tools/visualize_time.py."""
-    import ctypes as C
     import time
-    from . import _lib
     name = "write_box_plys"
     paths = list(paths)
     c, m, kept, dev_in, given = _boxes(corners, modes, name, on_degenerate)
@@ -229,16 +219,13 @@ def write_box_plys(corners, modes, paths, chunk=4096, device="cuda", on_degenera
     n_max = min(int(chunk), total)
     buf = torch.empty(8 + 4 * n_max + stride * n_max, dtype=torch.uint8, device=c.device)
     init = torch.tensor([0, 0x7fffffff], dtype=torch.int32, device=c.device).view(torch.uint8)
-    p = lambda o: C.c_void_p(buf.data_ptr() + o)
     written = []
     for lo in range(0, total, n_max):
         n = min(n_max, total - lo)
         t0 = time.perf_counter()
         buf[:8].copy_(init)
-        with torch.cuda.device(c.device):
-            _lib.check(_lib.lib().d3_box_wire_text(C.c_void_p(c[lo:].data_ptr()), C.c_void_p(m[lo:].data_ptr()), n, _ring(),
-                                                   p(8 + 4 * n_max), p(8), p(0), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
-                       "box_wire_text")
+        with on(c.device):
+            call("box_wire_text", ptr(c[lo:]), ptr(m[lo:]), n, _ring(), ptr(buf[8 + 4 * n_max:]), ptr(buf[8:]), ptr(buf), stream())
         host = buf[:8 + 4 * n_max + stride * n].cpu().numpy()                       # the one read-back
         status, nbytes = host[:8].view(np.int32), host[8:8 + 4 * n].view(np.int32)
         t1 = time.perf_counter()
