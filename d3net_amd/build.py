@@ -35,10 +35,10 @@ def sources():
     return sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hip"))
 
 
-def _stamp(paths):
+def _stamp(paths, by_name=False):
     h = hashlib.sha1()
     for p in sorted(paths):
-        h.update(p.encode()); h.update(open(p, "rb").read())
+        h.update((os.path.basename(p) if by_name else p).encode()); h.update(open(p, "rb").read())
     h.update(" ".join(CXXFLAGS).encode())
     return h.hexdigest()
 
@@ -63,9 +63,18 @@ def build(force=False, verbose=False):
     os.makedirs(LIBDIR, exist_ok=True)
     os.makedirs(OBJDIR, exist_ok=True)
     srcs = sources()
+    # the library's own stamp (every source, header and flag): a tree that carries libd3hip.so built from exactly these files
+    # but not the object files -- a snapshot shipped to the GPU box -- loads it instead of compiling everything again
+    lib_stamp = _stamp(srcs + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")] +
+                       [os.path.join(HERE, "..", "include", "d3hip.h")], by_name=True)      # (the tree may sit elsewhere there)
+    lib_stamp_file = SO + ".stamp"
+    if not force and os.path.exists(SO) and os.path.exists(lib_stamp_file) and open(lib_stamp_file).read() == lib_stamp:
+        return SO
     if force:
         for f in os.listdir(OBJDIR):
             os.remove(os.path.join(OBJDIR, f))
+    if os.path.exists(lib_stamp_file):
+        os.remove(lib_stamp_file)
     with cf.ThreadPoolExecutor(max_workers=min(6, len(srcs))) as ex:
         objs = list(ex.map(_compile, srcs))
     newest = max(os.path.getmtime(o) for o in objs)
@@ -77,6 +86,7 @@ def build(force=False, verbose=False):
             raise RuntimeError("link failed:\n%s\n%s" % (r.stdout, r.stderr))
         if verbose:
             print("built", SO)
+    open(lib_stamp_file, "w").write(lib_stamp)
     return SO
 
 

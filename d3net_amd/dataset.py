@@ -1,0 +1,473 @@
+"""The dataset loader: what joins the preparation chain (`scan_export` -> `enet` -> `multiview` -> `scene_prep` / `lang_prep`) to
+the fit loop (`trainer.Trainer`), in place of the reference's `PipelineDataset._load` (lib/dataset/pipeline.py:384-413), the three
+`init_*_data` functions of scripts/train.py:30-245 and the `DistributedSampler` Lightning installs for them.
+
+  * `SceneStore`: one split's scenes packed into four flat arrays, resident on the device (or pinned on the host); `scene(id)` hands
+    `scene_prep.prepare_scene` views of them, so a batch uploads nothing.
+  * `PipelineLoader`: a re-iterable source of batches for `Trainer.fit` -- the samples of one rank in `DistributedSampler`'s order,
+    in groups of `data.batch_size`, each built by `prepare_scene` per sample, ONE `scene_prep.collate_scenes_device` launch and, with
+    descriptions, `lang_prep`'s two launches.
+  * `PairedLoader`: the joint mode's `[speaker batch, listener batch]` source.
+  * `build_loaders`: the sources and the `dataset` namespace of a configuration, from the paths of conf/path.yaml.
+
+The per-sample order of random draws is `lang_prep.prepare_pipeline_batch`'s / `scene_prep.prepare_batch`'s; the generators are the
+loader's own, seeded from (seed, epoch, rank), never the global ones.
+"""
+import copy
+import json
+import os
+import pickle
+import random
+import types
+import warnings
+
+import numpy as np
+import torch
+
+from . import lang_prep, scene_prep
+
+_FIELDS = ("points", "feats", "sem_labels", "instance_ids")
+SYNTHETIC = "SYNTHETIC"
+
+
+# ------------------------------------------------------------------------------------------------ annotation lists (host only)
+def synthetic_entry(scene_id):
+    """the description-less entry of scripts/train.py:53-60 / :135-142"""
+    return {"scene_id": scene_id, "object_id": SYNTHETIC, "object_name": SYNTHETIC, "ann_id": SYNTHETIC, "description": SYNTHETIC,
+            "token": [SYNTHETIC]}
+
+
+def read_scan_list(path):
+    return [s.rstrip() for s in open(path).readlines()]
+
+
+def scan_list_of(raw):
+    """scripts/train.py:109: the sorted scene ids of an annotation list"""
+    return sorted(list(set(d["scene_id"] for d in raw)))
+
+
+def detector_entries(scan_list):
+    """`init_detector_data` (scripts/train.py:51-73): one SYNTHETIC entry per scan, in list order"""
+    return [synthetic_entry(s) for s in scan_list]
+
+
+def speaker_val_entries(raw_val):
+    """`init_speaker_data` (scripts/train.py:112-118): one entry per validation scene, a copy of raw_val[0] with the scene id swapped"""
+    out = []
+    for scene_id in scan_list_of(raw_val):
+        d = copy.deepcopy(raw_val[0])
+        d["scene_id"] = scene_id
+        out.append(d)
+    return out
+
+
+def speaker_train_entries(raw_train, all_train_scans, extra_ratio, pyrng):
+    """`init_speaker_data` (scripts/train.py:120-150) -> (data_train, scan_list_train): with extra_ratio > 0 the SYNTHETIC fill
+    over the scans without annotations (`random.choice` once they run out) and the `random.shuffle` of the whole list, both drawn
+    from `pyrng` (a random.Random) where the reference uses the global generator"""
+    data = copy.deepcopy(raw_train)
+    scans = scan_list_of(raw_train)
+    if extra_ratio > 0:
+        num_extra = int(len(raw_train) * extra_ratio)
+        extra_scans = [s for s in all_train_scans if s not in scans]
+        extra = [synthetic_entry(extra_scans[i] if i < len(extra_scans) else pyrng.choice(extra_scans)) for i in range(num_extra)]
+        data += extra
+        scans = scans + scan_list_of(extra)
+        pyrng.shuffle(data)
+    return data, scans
+
+
+def organize(raw_data):
+    """`_organize_data` (pipeline.py:567-581): organized[scene_id][object_id] -> the entries, SYNTHETIC ones left out"""
+    out = {}
+    for d in raw_data:
+        if d["object_id"] != SYNTHETIC:
+            out.setdefault(d["scene_id"], {}).setdefault(d["object_id"], []).append(d)
+    return out
+
+
+def sampler_indices(n, world=1, rank=0, shuffle=True, seed=0, epoch=0):
+    """`list(torch.utils.data.DistributedSampler(range(n), num_replicas=world, rank=rank, shuffle=shuffle, seed=seed,
+    drop_last=False))` after `set_epoch(epoch)`: randperm under manual_seed(seed + epoch), padded by wrap-around to a multiple of
+    `world`, rank r takes r::world"""
+    if not 0 <= rank < world:
+        raise ValueError("rank %d outside [0, %d)" % (rank, world))
+    if shuffle:
+        g = torch.Generator()
+        g.manual_seed(seed + epoch)
+        idx = torch.randperm(n, generator=g).tolist()
+    else:
+        idx = list(range(n))
+    total = (n + world - 1) // world * world
+    pad = total - n
+    if pad:
+        idx += idx[:pad] if pad <= n else (idx * ((pad + n - 1) // n))[:pad]
+    return idx[rank:total:world]
+
+
+# ------------------------------------------------------------------------------------------------ the scene store
+def _host(x, dtype):
+    if torch.is_tensor(x):
+        x = x.detach().cpu().numpy()
+    return np.ascontiguousarray(np.asarray(x).astype(dtype, copy=False))
+
+
+def mesh_features(mesh, use_color, use_normal, multiview=None):
+    """`_get_coord_and_feat_from_mesh` (pipeline.py:774-802) on an aligned mesh (N, 6 or 9): -> (points (N,3), feats (N,C)) float32;
+    colours if use_color, normals if use_normal (the mesh must then have 9 columns, as the reference asserts), then the (N,128)
+    multiview rows when `multiview` is not None"""
+    mesh = _host(mesh, np.float32)
+    cols = []
+    if use_color:
+        cols.append(mesh[:, 3:6])
+    if use_normal:
+        if mesh.shape[1] != 9:
+            raise ValueError("use_normal needs xyz, rgb and normals: the mesh has %d columns, not 9" % mesh.shape[1])
+        cols.append(mesh[:, 6:9])
+    if multiview is not None:
+        mv = _host(multiview, np.float32)
+        if mv.shape != (mesh.shape[0], 128):
+            raise ValueError("multiview features are %s, expected %s" % (mv.shape, (mesh.shape[0], 128)))
+        cols.append(mv)
+    feats = np.concatenate(cols, 1) if cols else np.zeros((mesh.shape[0], 0), np.float32)
+    return np.ascontiguousarray(mesh[:, :3]), np.ascontiguousarray(feats)
+
+
+class SceneStore:
+    """The scenes of one split as four flat, per-scene-contiguous arrays -- `points` (N,3) float32, `feats` (N,C) float32,
+    `sem_labels` (N,) int32, `instance_ids` (N,) int32, N the split's point total -- with the host table `offsets` (S+1) of row
+    offsets and `scene_ids`.  Everything is packed on the host and goes up in ONE upload per array.
+
+    `scene(scene_id)` returns the raw-scene dict `scene_prep.prepare_scene` takes as zero-copy row slices of the packed arrays: no
+    kernel, no copy, and `prepare_scene` finds them on its device with its dtypes, so its own conversions are no-ops too.
+    The views alias the store: writing to one changes the scene for every later batch.  `prepare_scene` does not write to its
+    inputs -- every kernel that reads them (`d3_scene_transform`, `d3_scene_emit`) takes them `const` and writes fresh tensors
+    (csrc/scene_prep.hip, include/d3hip.h) -- so the loader never needs a copy; a caller who wants to edit a scene clones it first.
+
+    With device="cpu" the arrays are pinned host memory and `scene()` returns non-blocking device copies issued on the caller's
+    current stream (for a split whose multiview features someone does not want resident); the batches are the same."""
+
+    def __init__(self, scene_ids, offsets, arrays, device):
+        self.scene_ids, self.offsets = list(scene_ids), np.asarray(offsets, np.int64)
+        self._row = {s: i for i, s in enumerate(self.scene_ids)}
+        if len(self._row) != len(self.scene_ids):
+            raise ValueError("SceneStore: a scene id appears twice")
+        self.device = torch.device(device)
+        for k in _FIELDS:
+            t = torch.from_numpy(arrays[k])
+            setattr(self, k, t.pin_memory() if self.device.type == "cpu" and torch.cuda.is_available() else t.to(self.device))
+
+    # --------------------------------------------------------------------------------------------- construction
+    @classmethod
+    def from_scenes(cls, scenes, cfg=None, device="cuda", multiview=None):
+        """scenes: {scene_id: scene} in the store's order.  A scene is a raw-scene dict (`points`, `feats`, `sem_labels`,
+        `instance_ids`; taken as it is) or what the reference's scene file holds (`aligned_mesh` (N,6|9), `sem_labels`,
+        `instance_ids`; a `scan_export.ScanExport` counts), whose feature columns follow cfg.model.use_color / use_normal /
+        use_multiview (`mesh_features`).  multiview: {scene_id: (N,128) array or tensor}; a scene missing from it gets the
+        reference's zero placeholder (pipeline.py:794-795).  Arrays may be numpy or tensors on any device."""
+        packed = {k: [] for k in _FIELDS}
+        offsets, width = [0], None
+        for sid, sc in scenes.items():
+            if hasattr(sc, "to_reference_dict"):
+                sc = sc.to_reference_dict()
+            if "points" in sc:
+                pts, feats = _host(sc["points"], np.float32), _host(sc["feats"], np.float32)
+                feats = feats.reshape(pts.shape[0], -1)
+            else:
+                if cfg is None:
+                    raise ValueError("SceneStore.from_scenes: cfg.model's use_color / use_normal / use_multiview select a mesh's features")
+                m, mv = cfg.model, None
+                if m.use_multiview:
+                    mv = (multiview or {}).get(sid)
+                    if mv is None:
+                        mv = np.zeros((sc["aligned_mesh"].shape[0], 128), np.float32)
+                pts, feats = mesh_features(sc["aligned_mesh"], m.use_color, m.use_normal, mv)
+            n = pts.shape[0]
+            sem, ids = _host(sc["sem_labels"], np.int32).reshape(-1), _host(sc["instance_ids"], np.int32).reshape(-1)
+            if pts.shape != (n, 3) or feats.shape[0] != n or sem.shape != (n,) or ids.shape != (n,):
+                raise ValueError("%s: points %s, feats %s, sem_labels %s, instance_ids %s" % (sid, pts.shape, feats.shape, sem.shape, ids.shape))
+            if width is not None and feats.shape[1] != width:
+                raise ValueError("%s: %d feature columns, the scenes before have %d" % (sid, feats.shape[1], width))
+            width = feats.shape[1]
+            for k, a in zip(_FIELDS, (pts, feats, sem, ids)):
+                packed[k].append(a)
+            offsets.append(offsets[-1] + n)
+        if width is None:
+            raise ValueError("SceneStore: no scenes")
+        return cls(list(scenes), offsets, {k: np.ascontiguousarray(np.concatenate(v, 0)) for k, v in packed.items()}, device)
+
+    @classmethod
+    def load(cls, cfg, split, scan_list, device="cuda", multiview=None):
+        """`_load`'s scene half (pipeline.py:387): torch.load of `<SCANNETV2_PATH.split_data>/<split>/<scene_id><data.file_suffix>`
+        per scan of `scan_list`.  multiview: as in `from_scenes`; None with model.use_multiview reads the reference's HDF5 file
+        (SCANNETV2_PATH.multiview_features) when `h5py` imports, and otherwise warns and leaves the zero placeholder."""
+        root = os.path.join(cfg.SCANNETV2_PATH.split_data, split)
+        scenes = {s: torch.load(os.path.join(root, s + cfg.data.file_suffix), weights_only=False) for s in scan_list}
+        h5 = None
+        if cfg.model.use_multiview and multiview is None:
+            try:
+                import h5py
+            except ImportError:
+                warnings.warn("model.use_multiview is set, no multiview= mapping was given and h5py does not import: "
+                              "the 128 multiview columns are the zero placeholder")
+            else:
+                h5 = h5py.File(cfg.SCANNETV2_PATH.multiview_features, "r", libver="latest")
+                multiview = {s: h5[s][()] for s in scan_list if s in h5}
+        try:
+            return cls.from_scenes(scenes, cfg, device, multiview)
+        finally:
+            if h5 is not None:
+                h5.close()
+
+    # --------------------------------------------------------------------------------------------- access
+    def __len__(self):
+        return len(self.scene_ids)
+
+    def __contains__(self, scene_id):
+        return scene_id in self._row
+
+    def num_points(self, scene_id):
+        i = self._row[scene_id]
+        return int(self.offsets[i + 1] - self.offsets[i])
+
+    def bytes(self):
+        """the footprint of the four packed arrays"""
+        return sum(getattr(self, k).numel() * getattr(self, k).element_size() for k in _FIELDS)
+
+    def scene(self, scene_id, device=None):
+        """the raw-scene dict of `prepare_scene`: views (device store) or non-blocking device copies (pinned store; `device`
+        defaults to the current one)"""
+        i = self._row[scene_id]
+        a, b = int(self.offsets[i]), int(self.offsets[i + 1])
+        out = {k: getattr(self, k)[a:b] for k in _FIELDS}
+        if self.device.type == "cpu" and (device is not None or torch.cuda.is_available()):
+            device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+            out = {k: v.to(device, non_blocking=True) for k, v in out.items()}
+        return out
+
+
+# ------------------------------------------------------------------------------------------------ the batch source
+def _opt(node, key, default):
+    """an optional config key of a `config.Cfg` or of a plain namespace"""
+    if node is None:
+        return default
+    return node.get(key, default) if isinstance(node, dict) else getattr(node, key, default)
+
+
+class PipelineLoader:
+    """A re-iterable source of batches over `store` for one rank.
+
+    index: the split's `lang_prep.DescriptionIndex` -- a sample is then one chunk (`index.chunks`, the reference's
+    `_get_chunked_data`) -- or None in the pure detector mode, where a sample is one scene of `scene_ids` (default: the store's,
+    the SYNTHETIC entries of `init_detector_data`).  mode: the reference dataset's "speaker" / "listener" / "detector", kept
+    for the log.  `__iter__` starts a new pass at the loader's current epoch in `sampler_indices`' order, i.e. that of
+    `DistributedSampler(shuffle=shuffle, seed=seed, drop_last=False)`, which Lightning installs for the reference under DDP (world=1:
+    a seeded shuffle=True), cut into consecutive groups of data.batch_size (the last one short).  `set_epoch(e)` sets the epoch
+    of the next pass; every pass without it advances by one.  shuffle defaults to split == "train"; is_augment to False, as
+    scripts/train.py builds its datasets.
+
+    A batch is `lang_prep.prepare_pipeline_batch`'s (with an index) or `scene_prep.prepare_batch`'s (without) over
+    `store.scene(...)`, stacked by `scene_prep.collate_scenes_device`; draws come from `generators(epoch)`."""
+
+    def __init__(self, cfg, store, index, split, mode, rank=0, world=1, seed=None, shuffle=None, is_augment=False, mean_size_arr=None,
+                 noise="device", device=None, scene_ids=None):
+        self.cfg, self.store, self.index, self.split, self.mode = cfg, store, index, split, mode
+        self.rank, self.world = int(rank), int(world)
+        self.seed = int(cfg.general.manual_seed if seed is None else seed)
+        self.shuffle = (split == "train") if shuffle is None else bool(shuffle)
+        self.is_augment, self.noise, self.device = bool(is_augment), noise, device
+        self.batch_size, self.voxel_mode = int(cfg.data.batch_size), int(_opt(cfg.data, "mode", 4) or 4)
+        self.apply_word_erase = bool(_opt(_opt(cfg, "train", None), "apply_word_erase", True))
+        self.mean_size_arr = mean_size_arr
+        self.scene_ids = list(store.scene_ids if scene_ids is None else scene_ids) if index is None else None
+        self._next_epoch = 0
+        self.last_order = None
+        missing = sorted({self.sample_scene(i) for i in range(self.num_samples())} - set(store.scene_ids))
+        if missing:
+            raise ValueError("PipelineLoader: %d scenes are not in the store (%s ...)" % (len(missing), missing[0]))
+
+    def num_samples(self):
+        return len(self.index) if self.index is not None else len(self.scene_ids)
+
+    def sample_scene(self, i):
+        return self.index.scene_id(i) if self.index is not None else self.scene_ids[i]
+
+    def set_epoch(self, epoch):
+        self._next_epoch = int(epoch)
+
+    def order(self, epoch):
+        """this rank's sample indices of `epoch`"""
+        return sampler_indices(self.num_samples(), self.world, self.rank, self.shuffle, self.seed, epoch)
+
+    def generators(self, epoch):
+        """the pass's (numpy RandomState, random.Random), seeded from (seed, epoch, rank)"""
+        return (np.random.RandomState([self.seed & 0xFFFFFFFF, int(epoch), self.rank]),
+                random.Random("%d/%d/%d" % (self.seed, int(epoch), self.rank)))
+
+    def __len__(self):
+        per_rank = (self.num_samples() + self.world - 1) // self.world
+        return (per_rank + self.batch_size - 1) // self.batch_size
+
+    def build(self, idxs, rng, pyrng):
+        """one batch of the samples `idxs`"""
+        dev = torch.device("cuda", torch.cuda.current_device()) if self.device is None else torch.device(self.device)
+        prep = lambda sid: scene_prep.prepare_scene(self.store.scene(sid), self.cfg, self.mean_size_arr, rng=rng, is_augment=self.is_augment,
+                                                    noise=self.noise, device=dev)
+        if self.index is None:
+            return scene_prep.collate_scenes_device([prep(self.scene_ids[i]) for i in idxs], dev, self.voxel_mode)
+        index = self.index
+        dev = lang_prep._device(index, dev)
+        draws, samples = [], []
+        for c in idxs:                                     # per sample: the description draws, then the scene's (pipeline.py:91-, :145-)
+            draws.append(lang_prep.draw_descriptions(index, c, rng, pyrng, self.is_augment, self.apply_word_erase))
+            samples.append(prep(index.scene_id(c)))
+        batch = scene_prep.collate_scenes_device(samples, dev, self.voxel_mode)
+        batch.update(lang_prep._launch(index, draws, idxs, batch, dev))
+        return batch
+
+    def __iter__(self):
+        epoch = self._next_epoch
+        self._next_epoch = epoch + 1
+        order = self.last_order = self.order(epoch)
+        return self._batches(order, *self.generators(epoch))
+
+    def _batches(self, order, rng, pyrng):
+        for i in range(0, len(order), self.batch_size):
+            yield self.build(order[i:i + self.batch_size], rng, pyrng)
+
+
+class PairedLoader:
+    """The joint mode's training source: `[speaker batch, listener batch]` pairs over the LONGER of the sources, the shorter one
+    restarted when it runs out.  This is what Lightning does with a list of training loaders, `CombinedLoader(mode=
+    "max_size_cycle")` (its default for `train_dataloaders=[a, b]`, scripts/train.py:360-365): the epoch has max(len) batches and
+    a `CycleIterator` re-creates the exhausted loader's iterator.  The restarted pass repeats the epoch's order, as a
+    `DistributedSampler` whose epoch Lightning set once per epoch does."""
+
+    def __init__(self, *sources):
+        self.sources = list(sources)
+        self._epoch = None
+
+    def __len__(self):
+        return max(len(s) for s in self.sources)
+
+    def set_epoch(self, epoch):
+        self._epoch = int(epoch)
+        for s in self.sources:
+            if hasattr(s, "set_epoch"):
+                s.set_epoch(epoch)
+
+    def __iter__(self):
+        epoch = self._epoch
+        its = [iter(s) for s in self.sources]
+        for _ in range(len(self)):
+            pair = []
+            for k, s in enumerate(self.sources):
+                try:
+                    b = next(its[k])
+                except StopIteration:
+                    if epoch is not None and hasattr(s, "set_epoch"):
+                        s.set_epoch(epoch)
+                    its[k] = iter(s)
+                    b = next(its[k])
+                pair.append(b)
+            yield pair
+        if epoch is not None:
+            self._epoch = epoch + 1
+
+
+# ------------------------------------------------------------------------------------------------ a configuration's sources
+def load_vocabulary(cfg, name):
+    """`_build_vocabulary` (pipeline.py:433-502) -> (vocabulary, glove (V,300)): the vocabulary json of `<NAME>_PATH.vocabulary`
+    (with the special-token entry the reference patches in), the trimmed GloVe table of `glove_numpy`, or -- as the reference --
+    built from `glove_pickle` and saved there when that file is missing"""
+    paths = cfg["%s_PATH" % name.upper()]
+    if not os.path.exists(paths.vocabulary):
+        raise FileNotFoundError("no vocabulary at %s (the reference builds it on its first training run)" % paths.vocabulary)
+    vocabulary = json.load(open(paths.vocabulary))
+    vocabulary.setdefault("special_tokens", {"bos_token": "sos", "eos_token": "eos", "unk_token": "unk", "pad_token": "pad_"})
+    if os.path.exists(paths.glove_numpy):
+        glove = np.load(paths.glove_numpy)
+    else:
+        all_glove = pickle.load(open(paths.glove_pickle, "rb"))
+        glove = np.zeros((len(vocabulary["word2idx"]), 300))
+        for word, idx in vocabulary["word2idx"].items():
+            glove[int(idx)] = all_glove[word] if word in all_glove else all_glove["unk"]
+        np.save(paths.glove_numpy, glove)
+    return vocabulary, glove
+
+
+def _namespace(index, vocabulary, glove):
+    """the `dataset` object PipelineNet reads (train.py:synthetic_dataset's shape)"""
+    raw = index.raw_data
+    return types.SimpleNamespace(vocabulary=vocabulary, glove=glove, raw_data=raw, organized=organize(raw),
+                                 chunked_data=[[raw[n] for n in chunk] for chunk in index.chunks])
+
+
+def build_loaders(cfg, device, rank=0, world=1, multiview=None, store_device=None):
+    """`init_data` (scripts/train.py:220-245) with its `init_detector_data` / `init_speaker_data` / `init_listener_data` and the
+    loader choice of `start_training` (:338-365) -> (training source, validation source(s), dataset, stores):
+
+      mode 0   PipelineLoader over the scans of SCANNETV2_PATH.train_list / val_list, one scene per sample;
+      mode 1   the speaker's: <DATASET>_PATH.train_split (plus the data.extra_ratio SYNTHETIC fill and shuffle, under
+               random.Random(general.manual_seed)), validation = one entry per validation scene (`speaker_val_entries`);
+      mode 2   the listener's: train_split and the full val_split;
+      mode 3   PairedLoader(speaker, listener) and the pair of validation sources.
+
+    Training sources shuffle, validation sources do not; both are sharded over `world` ranks (Lightning's DistributedSampler).
+    dataset: {"train", "val"} namespaces with vocabulary, glove, chunked_data, organized, raw_data -- the speaker's when there
+    is one (scripts/train.py:284), else the listener's, None in mode 0.  stores: {"train", "val"} SceneStores on `store_device`
+    (default `device`), one per split, shared by the split's loaders."""
+    m = cfg.model
+    if m.no_detection:
+        raise NotImplementedError("GT-proposal modes 4-6 (no_detection) are not on the hot path")
+    if m.no_captioning and m.no_grounding and m.no_detection:
+        raise ValueError("invalid mode: detection, captioning and grounding are all off")
+    device = torch.device(device)
+    store_device = device if store_device is None else torch.device(store_device)
+    seed = int(cfg.general.manual_seed)
+    means = np.load(os.path.join(cfg.SCANNETV2_PATH.meta_data, "scannet_reference_means.npz"))["arr_0"]
+    lists = {}                                             # (role, split) -> (raw_data, scan list)
+    if m.no_captioning and m.no_grounding:
+        for split, key in (("train", "train_list"), ("val", "val_list")):
+            scans = read_scan_list(cfg.SCANNETV2_PATH[key])
+            lists[("detector", split)] = (detector_entries(scans), scans)
+    else:
+        paths = cfg["%s_PATH" % cfg.general.dataset.upper()]
+        raw_train, raw_val = json.load(open(paths.train_split)), json.load(open(paths.val_split))
+        if not m.no_captioning:
+            all_scans = read_scan_list(cfg.SCANNETV2_PATH.train_list) if cfg.data.extra_ratio > 0 else []
+            lists[("speaker", "train")] = speaker_train_entries(raw_train, all_scans, cfg.data.extra_ratio, random.Random(seed))
+            val = speaker_val_entries(raw_val)
+            lists[("speaker", "val")] = (val, scan_list_of(raw_val))
+        if not m.no_grounding:
+            lists[("listener", "train")] = (copy.deepcopy(raw_train), scan_list_of(raw_train))
+            lists[("listener", "val")] = (copy.deepcopy(raw_val), scan_list_of(raw_val))
+
+    stores = {}
+    for split in ("train", "val"):
+        scans = []
+        for (role, sp), (_raw, lst) in lists.items():
+            scans += [s for s in lst if sp == split and s not in scans]
+        stores[split] = SceneStore.load(cfg, split, scans, store_device, multiview)
+
+    loaders, indexes = {}, {}
+    if ("detector", "train") in lists:
+        for split in ("train", "val"):
+            loaders[("detector", split)] = PipelineLoader(cfg, stores[split], None, split, "detector", rank, world, seed, mean_size_arr=means,
+                                                          device=device, scene_ids=lists[("detector", split)][1])
+        return loaders[("detector", "train")], loaders[("detector", "val")], None, stores
+    vocabulary, glove = load_vocabulary(cfg, cfg.general.dataset)
+    raw2label = lang_prep.raw2label_from_tsv(cfg.SCANNETV2_PATH.combine_file)
+    scan2cad = json.load(open(cfg.SCAN2CAD)) if os.path.exists(cfg.SCAN2CAD) else None
+    for (role, split), (raw, _lst) in lists.items():
+        max_len = cfg.data.max_spk_len if role == "speaker" else cfg.data.max_lis_len
+        indexes[(role, split)] = lang_prep.DescriptionIndex(raw, vocabulary, glove, max_len, cfg.data.num_des_per_scene, raw2label,
+                                                            scan2cad_rotation=scan2cad, split=split, device=device)
+        loaders[(role, split)] = PipelineLoader(cfg, stores[split], indexes[(role, split)], split, role, rank, world, seed,
+                                                mean_size_arr=means, device=device)
+    role = "listener" if m.no_captioning else "speaker"
+    dataset = {split: _namespace(indexes[(role, split)], vocabulary, glove) for split in ("train", "val")}
+    if m.no_captioning or m.no_grounding:
+        return loaders[(role, "train")], loaders[(role, "val")], dataset, stores
+    return (PairedLoader(loaders[("speaker", "train")], loaders[("listener", "train")]),
+            (loaders[("speaker", "val")], loaders[("listener", "val")]), dataset, stores)

@@ -19,12 +19,13 @@ device (Philox4x32-10 + Box-Muller): the training path then pays no host RNG for
 every later draw -- differs from the reference's.
 """
 import ctypes as C
+import threading
 
 import numpy as np
 import torch
 
 from . import _lib, pointgroup_ops
-from ._call import _ptr, _stream
+from ._call import _on, _ptr, _stream, _workspace, call
 
 _NOISE_MODES = ("host", "device")
 
@@ -288,6 +289,90 @@ def collate_scenes(samples, device, mode=4):
         data["gt_proposals_idx"] = torch.cat(gt_idx, 0)
         data["gt_proposals_offset"] = torch.cat(gt_off, 0)
     data["voxel_locs"], data["p2v_map"], data["v2p_map"] = pointgroup_ops.voxelization_idx(data["locs_scaled"], len(samples), mode)
+    return data
+
+
+_POINT_KEYS = ("locs", "locs_scaled", "feats", "sem_labels", "instance_ids", "instance_info", "instance_num_point",
+               "gt_proposals_idx", "gt_proposals_offset")
+_I64_BOX = ("sem_cls_label", "heading_class_label", "size_class_label", "gt_bbox_object_id", "gt_bbox_label")
+_BOX_TAIL = {"center_label": (3,), "size_residual_label": (3,), "gt_bbox": (8, 3)}
+_tables = {}
+
+
+def _collate_table(nbytes, device):
+    """the pinned table of one batch, per (device, host thread, stream) like the workspace, with the event that tells when its
+    copy to the device has run"""
+    key = (device.index, threading.get_ident(), _stream().value or 0)
+    ent = _tables.get(key)
+    if ent is None or ent[0].numel() < nbytes:
+        ent = (torch.empty(int(nbytes * 1.25) + 1024, dtype=torch.uint8).pin_memory(), torch.cuda.Event())
+        _tables[key] = ent
+    else:
+        ent[1].synchronize()            # the earlier batch's copy (long done: prepare_scene has read back since)
+    return ent
+
+
+def collate_scenes_device(samples, device, mode=4):
+    """`collate_scenes` as ONE launch (csrc/collate.hip, `d3_collate_scenes`): the same keys, dtypes, shapes and bits, from the
+    per-scene dicts of `prepare_scene`.  The per-scene pointers and counts go up as one pinned table in one asynchronous copy;
+    the voxelisation is `pointgroup_ops.voxelization_idx`, as there.  One batch `collate_scenes` cannot stack has a result here: with
+    GT proposal lists, an instance-less scene followed by another leaves that function asking an empty list for its last element
+    (IndexError, as in the reference); the kernel shifts each scene's offsets by the proposal entries before it."""
+    device = torch.device(device)
+    if device.index is None:
+        device = torch.device(device.type, torch.cuda.current_device())
+    B = len(samples)
+    if B < 1:
+        raise ValueError("collate_scenes_device: no samples")
+    has_gt = "gt_proposals_idx" in samples[0]
+    if any(("gt_proposals_idx" in s) != has_gt for s in samples):
+        raise ValueError("collate_scenes_device: GT proposal lists on some samples only")
+    Cf, R = samples[0]["feats"].shape[1], samples[0]["center_label"].shape[0]
+    f32, i32, i64 = torch.float32, torch.int32, torch.int64
+    keep, ptrs, counts = [], np.zeros((B, len(_POINT_KEYS) + len(_BOX_KEYS)), np.uint64), np.zeros((B, 3), np.int32)
+    for i, s in enumerate(samples):
+        n, K = s["locs"].shape[0], int(s["num_instance"])
+        Lp = s["gt_proposals_idx"].shape[0] if has_gt else 0
+        want = {"locs": (f32, (n, 3)), "locs_scaled": (f32, (n, 3)), "feats": (f32, (n, Cf)), "sem_labels": (i32, (n,)),
+                "instance_ids": (i32, (n,)), "instance_info": (f32, (n, 12)), "instance_num_point": (i32, (K,))}
+        if has_gt:
+            want.update(gt_proposals_idx=(i32, (Lp, 2)), gt_proposals_offset=(i32, (K + 1,)))
+        want.update({k: (i64 if k in _I64_BOX else f32, (R,) + _BOX_TAIL.get(k, ())) for k in _BOX_KEYS})
+        for j, k in enumerate(_POINT_KEYS + _BOX_KEYS):
+            if k not in want:
+                continue
+            t = s[k]
+            if t.dtype != want[k][0] or tuple(t.shape) != want[k][1] or t.device != device:
+                raise ValueError("collate_scenes_device: sample %d %s is %s %s on %s, expected %s %s on %s"
+                                 % (i, k, t.dtype, tuple(t.shape), t.device, want[k][0], want[k][1], device))
+            t = t.contiguous()
+            keep.append(t)
+            ptrs[i, j] = t.data_ptr()
+        counts[i] = (n, K, Lp)
+    N, I, Lt = (int(v) for v in counts.sum(0, dtype=np.int64))
+    if max(N, I, Lt) >= 2 ** 31:
+        _range_error("collate_scenes_device: %d points / %d instances / %d proposal entries" % (N, I, Lt))
+    new = lambda shape, dt: torch.empty(shape, dtype=dt, device=device)
+    data = {"locs": new((N, 3), f32), "locs_scaled": new((N, 4), i64), "feats": new((N, Cf), f32), "sem_labels": new((N,), i64),
+            "instance_ids": new((N,), i64), "instance_info": new((N, 12), f32), "instance_num_point": new((I,), i32)}
+    if has_gt:
+        data.update(gt_proposals_idx=new((Lt, 2), i32), gt_proposals_offset=new((I + 1,), i32))
+    data.update(batch_offsets=new((B + 1,), i32), instance_offsets=new((B + 1,), i32))
+    data.update({k: new((B, R) + _BOX_TAIL.get(k, ()), i64 if k in _I64_BOX else f32) for k in _BOX_KEYS})
+    out = np.array([data[k].data_ptr() if k in data else 0
+                    for k in _POINT_KEYS + ("batch_offsets", "instance_offsets") + _BOX_KEYS], np.uint64)
+    hp = lambda a: a.ctypes.data_as(C.c_void_p)
+    with _on(device):
+        nbytes = int(_lib.lib().d3_collate_table_bytes(B))
+        if nbytes == 0:
+            _range_error("collate_scenes_device: %d scenes" % B)
+        table, copied = _collate_table(nbytes, device)
+        ws = _workspace(nbytes, device, "collate")
+        call("collate_scenes", hp(ptrs), hp(counts), B, Cf, R, int(has_gt), hp(out), C.c_void_p(table.data_ptr()), _ptr(ws), nbytes,
+             _stream())
+        copied.record()
+    # `keep` (the contiguous inputs) lives until here; the launch is queued on their stream, which orders any later reuse
+    data["voxel_locs"], data["p2v_map"], data["v2p_map"] = pointgroup_ops.voxelization_idx(data["locs_scaled"], B, mode)
     return data
 
 

@@ -1,9 +1,15 @@
-"""`python -m d3net_amd.train -c <conf> --synthetic N [--epochs E] [--root DIR]`: `Trainer.fit` on synthetic scenes
-(d3net_amd/synthetic.py), in place of scripts/train.py's `__main__` (:329-391).  A smoke path and a worked example of the fit
-loop -- the batches are what `scene_prep.prepare_batch` / `lang_prep.prepare_pipeline_batch` produce from real scenes
- -- not a dataset loader: N scenes in batches of `data.batch_size`, the first batch doubles as the validation
-split."""
+"""`python -m d3net_amd.train -c <conf> (--synthetic N | --data) [--epochs E] [--root DIR]`, in place of scripts/train.py's
+`__main__` (:329-391).
+
+`--synthetic N`: `Trainer.fit` on synthetic scenes (d3net_amd/synthetic.py) -- a smoke path and a worked example of the fit loop,
+not a dataset loader: N scenes in batches of `data.batch_size`, the first batch doubles as the validation split.
+
+`--data`: `Trainer.fit` on the splits the configuration's paths name (conf/path.yaml): `dataset.build_loaders` loads each split into
+a device-resident `SceneStore` and returns the mode's training and validation sources.  Under a launcher that sets WORLD_SIZE /
+RANK / LOCAL_RANK (torch.distributed.run) every rank takes its shard of each pass.  Pretrained weights and freezes are applied as
+`init_model` does (scripts/train.py:282-327); `--teacher` clusters on the labels, for a run that has no detector weights."""
 import argparse
+import copy
 import os
 import types
 
@@ -48,18 +54,62 @@ def synthetic_batches(cfg, mode, n_scenes, dev):
     return Batches(train), (Batches([train[0][0]]), Batches([train[0][1]]))
 
 
-def main(argv=None):
+def _ranks():
+    """(world, rank, local rank) from the launcher's environment, as bench.py reads them; the process group of a multi-rank run"""
+    import torch.distributed as dist
+    world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
+    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
+    if world > 1 and not dist.is_initialized():
+        dist.init_process_group(os.environ.get("D3_DIST_BACKEND", "nccl"), rank=rank, world_size=world)
+    return world, rank, local_rank
+
+
+def fit_data(cfg, root, teacher=False):
+    """--data: the configuration's splits through `dataset.build_loaders` into `Trainer.fit`"""
+    from .checkpoint import apply_freeze, load_pretrained
+    from .dataset import build_loaders
+    world, rank, local_rank = _ranks()
+    dev = torch.device("cuda", local_rank)
+    torch.cuda.set_device(dev)
+    torch.manual_seed(cfg.general.manual_seed)
+    train, val, dataset, stores = build_loaders(cfg, dev, rank, world)
+    model = PipelineNet(cfg, dataset).to(dev)             # init_model (scripts/train.py:282-327)
+    loaded, frozen = load_pretrained(model, cfg), apply_freeze(model, cfg)
+    print("=> pretrained: %s; frozen: %s" % (", ".join(loaded) or "none", ", ".join(frozen) or "none"))
+    model.detector.teacher = bool(teacher)
+    trainer = Trainer(cfg, model, root=root)
+    nval = [len(v) for v in val] if isinstance(val, (tuple, list)) else len(val)
+    print("=> train with MODE: %d, rank %d of %d; scene store: %s; %d training batches per epoch, %s validation batches, %d epochs -> %s"
+          % (model.mode, rank, world, ", ".join("%s %d scenes %.1f MiB on %s" % (k, len(s), s.bytes() / 2 ** 20, s.device)
+                                                for k, s in stores.items()), len(train), nval, trainer.epochs, trainer.root))
+    trainer.fit(train, val)
+    return trainer
+
+
+def main(argv=None, overrides=None):
+    """overrides: a nested dict merged over the configuration files before `${...}` is resolved (e.g. {"DATA_PATH": ...})"""
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("-c", "--config", default="pointgroup.yaml", help="a task yaml: a path, or a file name under conf/")
-    ap.add_argument("--synthetic", type=int, required=True, metavar="N", help="train on N synthetic scenes")
+    src = ap.add_mutually_exclusive_group(required=True)
+    src.add_argument("--synthetic", type=int, metavar="N", help="train on N synthetic scenes")
+    src.add_argument("--data", action="store_true", help="train on the splits the configuration's paths name (dataset.build_loaders)")
+    ap.add_argument("--teacher", action="store_true", help="with --data: cluster on the labels instead of the detector's predictions "
+                    "(the switch --synthetic always sets; for a run without pretrained detector weights)")
     ap.add_argument("--epochs", type=int, default=None, help="override train.epochs")
     ap.add_argument("--root", default=None, help="run directory (default: <general.output_root>/<EXPERIMENT>)")
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("d3net_amd.train needs a GPU: the product has no CPU path")
     conf = args.config if os.path.exists(args.config) else os.path.join(CONF_DIR, args.config)
-    over = {"train": {"epochs": args.epochs}} if args.epochs is not None else None
-    cfg = load_conf(os.path.join(CONF_DIR, "path.yaml"), conf, overrides=over)
+    over = copy.deepcopy(overrides) if overrides else {}
+    if args.epochs is not None:
+        over.setdefault("train", {})["epochs"] = args.epochs
+    cfg = load_conf(os.path.join(CONF_DIR, "path.yaml"), conf, overrides=over or None)
+    if args.data:
+        trainer = fit_data(cfg, args.root, args.teacher)
+        print("=> best %s: %s (epoch %s); metrics: %s" % (trainer.monitor, trainer.best_score, trainer.best_epoch,
+                                                        os.path.join(trainer.root, "logs", "metrics.jsonl")))
+        return trainer
     dev = torch.device("cuda", 0)
     torch.manual_seed(cfg.general.manual_seed)
     language = not (cfg.model.no_captioning and cfg.model.no_grounding)

@@ -7,6 +7,7 @@ filename="model", save_last=True)`'s two files.
 
 `train_batches` / `val_batches` are re-iterable sources of batches (lists, or objects whose `__iter__` starts a new pass); in
 mode 3 a training batch is the pair `training_step` asserts and `val_batches` is a pair of sources (`dataloader_idx` 0 and 1).
+A training source with a `set_epoch` method (`dataset.PipelineLoader`) gets `set_epoch(epoch)` before each pass.
 Config keys read (all of them shipped by every conf/*.yaml): `train.epochs`, `train.check_val_every_n_epoch`,
 `train.num_sanity_val_steps` (-1: all validation batches), `train.log_every_n_steps`, `general.monitor`,
 `general.monitor_mode`, `model.use_checkpoint` (resume from `<general.output_root>/<use_checkpoint>/last.ckpt`,
@@ -247,6 +248,8 @@ class Trainer:
             self.current_epoch = model.current_epoch = epoch      # (the detector's prepare_epochs gate reads it)
             model.train()
             self.train_log.reset()
+            if hasattr(train_batches, "set_epoch"):
+                train_batches.set_epoch(epoch)            # (a loader's pass order follows the epoch: a resumed run continues the sequence)
             for i, batch in enumerate(train_batches):
                 self.training_batch(batch, i, grad_sync)
             for s in self.schedulers:

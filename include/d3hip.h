@@ -1050,6 +1050,30 @@ int d3_ref_targets(const long long *gt_ids, const long long *gt_label, const flo
                    int R, const int *rot_off, const int *rot_ids, const float *rot_mats, int Ns, const int *scene_host,
                    long long *ref_label, float *ref_corner, float *rots, long long *rot_masks, void *ws, size_t ws_bytes, void *stream);
 
+/* ---- batch stacking (csrc/collate.hip, driven by d3net_amd/scene_prep.py:collate_scenes_device) -------------------------------
+ * lib/dataset/pipeline.py:917- (sparse_collate_fn) over B per-scene samples that are already on the device, in ONE launch.
+ *   ptrs_host (B,18), HOST memory: per scene the device pointers of locs (n,3) f32, locs_scaled (n,3) f32, feats (n,C) f32,
+ *     sem_labels (n) i32, instance_ids (n) i32, instance_info (n,12) f32, instance_num_point (K) i32, gt_proposals_idx (Lp,2) i32,
+ *     gt_proposals_offset (K+1) i32 (the last two read only when has_gt), then the nine box labels of R rows: center_label (R,3)
+ *     f32, sem_cls_label (R) i64, heading_class_label (R) i64, heading_residual_label (R) f32, size_class_label (R) i64,
+ *     size_residual_label (R,3) f32, gt_bbox_object_id (R) i64, gt_bbox_label (R) i64, gt_bbox (R,8,3) f32; all contiguous.
+ *   counts_host (B,3), HOST memory: n points, K instances, Lp proposal entries per scene.
+ *   out_host (20), HOST memory: the device pointers of the stacked outputs, N / I / L the sums of n / K / Lp: locs (N,3) f32,
+ *     locs_scaled (N,4) i64 = [scene index, (int64) of each coordinate], feats (N,C) f32, sem_labels (N) i64, instance_ids (N) i64
+ *     (ids other than -1 shifted by the instances of the scenes before), instance_info (N,12) f32, instance_num_point (I) i32,
+ *     gt_proposals_idx (L,2) i32 (column 0 shifted by the instances, column 1 by the points before), gt_proposals_offset (I+1) i32
+ *     (each scene's leading 0 dropped after the first, shifted by the entries before), batch_offsets (B+1) i32, instance_offsets
+ *     (B+1) i32, then the nine box labels stacked to (B,R,...).  Outputs 7 and 8 may be NULL when has_gt == 0.
+ *   table_host: d3_collate_table_bytes(B) bytes of (pinned) HOST memory the call fills with its job list, tile prefix and offset
+ *     tables and copies to table_dev (as many device bytes) with ONE asynchronous copy on the stream: keep it unchanged until that
+ *     copy has run.  One kernel: a block finds its job by binary search in the prefix table held in LDS; 16-byte accesses where
+ *     source and destination are 16-byte aligned, lane-consecutive words otherwise; plain stores, one writer per element.
+ *   B outside [1, 512] or sums outside int32: D3_ERR_RANGE (d3_collate_table_bytes: 0); a NULL pointer with a non-zero count, a
+ *   negative count or a misaligned int64 output: D3_ERR_ARG; all checked on the host before any copy or launch. */
+size_t d3_collate_table_bytes(int B);
+int d3_collate_scenes(const void *const *ptrs_host, const int *counts_host, int B, int C, int R, int has_gt, void *const *out_host,
+                      void *table_host, void *table_dev, size_t table_bytes, void *stream);
+
 /* ---- multiview feature projection (csrc/multiview.hip, driven by d3net_amd/multiview.py) --------------------------------------
  * The reference's ProjectionHelper.compute_projection / project (lib/utils/projection.py:180-256) and the per-scene loop of
  * data/scannet/project_multiview_features.py:88-205.  One scene: points (N,3) float32 mesh vertices; F frames in the caller's order:
