@@ -8,32 +8,13 @@
 // corner terms in scipy's hypercube order.  The validation path (no augmentation) is float32 throughout, as in the reference.
 // Every reduction that feeds an output is deterministic: min / max via integer atomics on an order-preserving encoding, sums
 // in a fixed sequential order per instance, counts via integer atomics.
-#include "common.h"
-
-#define SP_MAX_POINTS (1 << 24)
-#define SP_MAX_GRID_DIM 2048
-#define SP_MAX_GRID (1 << 25)
-#define SP_MAX_ID 65535
-#define SP_MAX_FEAT 256
-#define SP_BLOCK 256
-
-typedef unsigned long long u64;
+#include "scene_prep.h"
 
 int d3_scene_limits(int *max_points, int *max_grid, int *max_id) {
     if (max_points) *max_points = SP_MAX_POINTS;
     if (max_grid) *max_grid = SP_MAX_GRID;
     if (max_id) *max_id = SP_MAX_ID;
     return 0;
-}
-
-// order-preserving u64 image of a double (a < b  <=>  enc(a) < enc(b)); the host decodes it (scene_prep.py)
-__device__ __forceinline__ u64 sp_enc(double d) {
-    u64 b = (u64)__double_as_longlong(d);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double sp_dec(u64 e) {
-    u64 b = (e >> 63) ? (e & 0x7fffffffffffffffull) : ~e;
-    return __longlong_as_double((long long)b);
 }
 
 static inline int sp_grid(long long n) {

@@ -6,7 +6,8 @@ the fit loop (`trainer.Trainer`), in place of the reference's `PipelineDataset._
     `scene_prep.prepare_scene` views of them, so a batch uploads nothing.
   * `PipelineLoader`: a re-iterable source of batches for `Trainer.fit` -- the samples of one rank in `DistributedSampler`'s order,
     in groups of `data.batch_size`, each built by `prepare_scene` per sample, ONE `scene_prep.collate_scenes_device` launch and, with
-    descriptions, `lang_prep`'s two launches.
+    descriptions, `lang_prep`'s two launches.  With `fused=True` the scene half of a batch comes straight from the store and its
+    `InstanceIndex` instead (`scene_prep.prepare_batch_store`: no read-back, the same bits) wherever that path applies.
   * `PairedLoader`: the joint mode's `[speaker batch, listener batch]` source.
   * `build_loaders`: the sources and the `dataset` namespace of a configuration, from the paths of conf/path.yaml.
 
@@ -14,6 +15,7 @@ The per-sample order of random draws is `lang_prep.prepare_pipeline_batch`'s / `
 loader's own, seeded from (seed, epoch, rank), never the global ones.
 """
 import copy
+import ctypes as C
 import json
 import os
 import pickle
@@ -24,7 +26,7 @@ import warnings
 import numpy as np
 import torch
 
-from . import lang_prep, scene_prep
+from . import _lib, lang_prep, scene_prep
 
 _FIELDS = ("points", "feats", "sem_labels", "instance_ids")
 SYNTHETIC = "SYNTHETIC"
@@ -133,6 +135,70 @@ def mesh_features(mesh, use_color, use_normal, multiview=None):
     return np.ascontiguousarray(mesh[:, :3]), np.ascontiguousarray(feats)
 
 
+def scene_instance_tables(ids):
+    """One scene's part of the `InstanceIndex` from its instance ids (n,), all >= -1, with V = max(ids.max(), 0) + 1:
+    -> (hist (V+1), rank (V+1), start (V+1), order (n)): hist[0] the unlabelled points and hist[v + 1] those with id v; rank / start
+    the exclusive scans of presence / count over the id values with the totals K / Lp as last entry; order the stable sort of the
+    point indices by rank, unlabelled points behind every instance (`sp_hist_kernel` ... `sp_keys_kernel` and the sort of
+    csrc/scene_prep.hip:d3_scene_instances)."""
+    ids = np.asarray(ids, np.int64).reshape(-1)
+    V = max(int(ids.max()) if len(ids) else -1, 0) + 1
+    hist = np.bincount(ids + 1, minlength=V + 1)
+    rank = np.concatenate([[0], np.cumsum(hist[1:] > 0)])
+    start = np.concatenate([[0], np.cumsum(hist[1:])])
+    key = np.where(ids >= 0, rank[np.maximum(ids, 0)], rank[V])
+    return hist, rank, start, np.argsort(key, kind="stable").astype(np.int32)
+
+
+class InstanceIndex:
+    """What `scene_prep.prepare_scene` derives per scene and per batch from a scene's `instance_ids` alone (csrc/scene_prep.hip,
+    `sp_hist_kernel` ... `sp_totals_kernel`, `sp_keys_kernel` and the stable sort of `d3_scene_instances`), computed ONCE for a
+    whole store -- valid wherever a scene keeps all its points, i.e. without the crop of the augmented detector-only path:
+
+      * per scene V = max(id_hi, 0) + 1 and, from `table_offsets[scene]`, V + 1 entries of each flat table: `hist` (hist[0] the
+        unlabelled points, hist[v + 1] those with id v), `rank` / `start` (the exclusive scans of presence / count, i.e. the
+        instance's place in np.unique order and its first row in the GT proposal list; the extra last entry is K / Lp);
+      * `sorted` (one int32 per store point, at the scene's rows): scene-local point indices grouped by instance in np.unique
+        order, ascending inside each instance, the unlabelled points last;
+      * `scalars` (S,5) on the HOST: id_lo, id_hi, K instances, Lp labelled points, has_unlabelled -- the output shapes of every
+        later batch, read here once instead of once per scene and batch.
+
+    The tables are integer functions of the ids, built on the host from one copy of `instance_ids` (a stable argsort is the
+    kernels' stable radix sort) and uploaded once; this is a one-off per store.  What `prepare_scene` refuses per scene is
+    refused here with the same error and the scene's name: an id below -1, an id above the library's limit, too many points."""
+
+    def __init__(self, store):
+        if store.device.type == "cpu":
+            raise ValueError("SceneStore.instance_index: the store is pinned host memory; the index serves the resident store only")
+        max_points, max_id = C.c_int(0), C.c_int(0)
+        _lib.lib().d3_scene_limits(C.byref(max_points), None, C.byref(max_id))
+        ids_all = store.instance_ids.cpu().numpy()
+        S = len(store)
+        self.scalars = np.zeros((S, 5), np.int64)
+        self.table_offsets = np.zeros(S + 1, np.int64)
+        hist, rank, start = [], [], []
+        order = np.empty(ids_all.shape[0], np.int32)
+        for i, sid in enumerate(store.scene_ids):
+            a, b = int(store.offsets[i]), int(store.offsets[i + 1])
+            ids, n = ids_all[a:b].astype(np.int64), b - a
+            id_lo, id_hi = (int(ids.min()), int(ids.max())) if n else (-1, -1)
+            if id_lo < -1:
+                scene_prep._range_error("scene_prep: scene %s: instance id %d < -1" % (sid, id_lo))
+            if n > max_points.value or id_hi > max_id.value:
+                scene_prep._range_error("scene_prep: scene %s: %d points / instance id %d" % (sid, n, id_hi))
+            V = max(id_hi, 0) + 1
+            h, r, st, order[a:b] = scene_instance_tables(ids)
+            hist.append(h); rank.append(r); start.append(st)
+            self.scalars[i] = (id_lo, id_hi, int(r[V]), int(st[V]), int(h[0] > 0))
+            self.table_offsets[i + 1] = self.table_offsets[i] + V + 1
+        up = lambda parts: torch.from_numpy(np.concatenate(parts).astype(np.int32)).to(store.points.device)
+        self.hist, self.rank, self.start = up(hist), up(rank), up(start)
+        self.sorted = torch.from_numpy(order).to(store.points.device)
+
+    def bytes(self):
+        return sum(t.numel() * t.element_size() for t in (self.hist, self.rank, self.start, self.sorted))
+
+
 class SceneStore:
     """The scenes of one split as four flat, per-scene-contiguous arrays -- `points` (N,3) float32, `feats` (N,C) float32,
     `sem_labels` (N,) int32, `instance_ids` (N,) int32, N the split's point total -- with the host table `offsets` (S+1) of row
@@ -156,6 +222,7 @@ class SceneStore:
         for k in _FIELDS:
             t = torch.from_numpy(arrays[k])
             setattr(self, k, t.pin_memory() if self.device.type == "cpu" and torch.cuda.is_available() else t.to(self.device))
+        self._index = None
 
     # --------------------------------------------------------------------------------------------- construction
     @classmethod
@@ -234,6 +301,22 @@ class SceneStore:
         """the footprint of the four packed arrays"""
         return sum(getattr(self, k).numel() * getattr(self, k).element_size() for k in _FIELDS)
 
+    def row_of(self, scene_id):
+        """the scene's place in `scene_ids` / `offsets`"""
+        return self._row[scene_id]
+
+    def instance_index(self):
+        """the store's `InstanceIndex`, built on first use and kept (`scene_prep.prepare_batch_store` reads it); a resident store
+        only: a pinned-host store raises ValueError.  The store's arrays must not change afterwards."""
+        if self._index is None:
+            self._index = InstanceIndex(self)
+        return self._index
+
+    def index_bytes(self):
+        """the device footprint of the instance index (4 bytes per point plus the small tables), 0 while it is not built;
+        `bytes()` does not count it"""
+        return 0 if self._index is None else self._index.bytes()
+
     def scene(self, scene_id, device=None):
         """the raw-scene dict of `prepare_scene`: views (device store) or non-blocking device copies (pinned store; `device`
         defaults to the current one)"""
@@ -267,10 +350,15 @@ class PipelineLoader:
     scripts/train.py builds its datasets.
 
     A batch is `lang_prep.prepare_pipeline_batch`'s (with an index) or `scene_prep.prepare_batch`'s (without) over
-    `store.scene(...)`, stacked by `scene_prep.collate_scenes_device`; draws come from `generators(epoch)`."""
+    `store.scene(...)`, stacked by `scene_prep.collate_scenes_device`; draws come from `generators(epoch)`.
+
+    fused=True builds the scene half of every batch with `scene_prep.prepare_batch_store` instead -- straight from the store and its
+    instance index, no read-back, no per-scene tensor, the same draws in the same order and the same bits -- wherever
+    `fused_active()` holds.  Elsewhere it silently takes the path above: the augmented detector-only mode (elastic distortion and
+    crop make the point count data-dependent), a pinned-host store or one on another device, and noise="host"."""
 
     def __init__(self, cfg, store, index, split, mode, rank=0, world=1, seed=None, shuffle=None, is_augment=False, mean_size_arr=None,
-                 noise="device", device=None, scene_ids=None):
+                 noise="device", device=None, scene_ids=None, fused=False):
         self.cfg, self.store, self.index, self.split, self.mode = cfg, store, index, split, mode
         self.rank, self.world = int(rank), int(world)
         self.seed = int(cfg.general.manual_seed if seed is None else seed)
@@ -279,6 +367,7 @@ class PipelineLoader:
         self.batch_size, self.voxel_mode = int(cfg.data.batch_size), int(_opt(cfg.data, "mode", 4) or 4)
         self.apply_word_erase = bool(_opt(_opt(cfg, "train", None), "apply_word_erase", True))
         self.mean_size_arr = mean_size_arr
+        self.fused, self._mean_size_dev = bool(fused), None
         self.scene_ids = list(store.scene_ids if scene_ids is None else scene_ids) if index is None else None
         self._next_epoch = 0
         self.last_order = None
@@ -308,9 +397,37 @@ class PipelineLoader:
         per_rank = (self.num_samples() + self.world - 1) // self.world
         return (per_rank + self.batch_size - 1) // self.batch_size
 
+    def fused_active(self, device=None):
+        """whether `build` takes `scene_prep.prepare_batch_store` (a host predicate)"""
+        if not (self.fused and self.noise != "host" and scene_prep.fused_applicable(self.cfg, self.is_augment, self.store)):
+            return False
+        dev = self.device if device is None else device
+        dev = torch.device("cuda", torch.cuda.current_device()) if dev is None else torch.device(dev)
+        return dev.type == "cuda" and dev.index in (None, self.store.points.device.index)
+
+    def _build_fused(self, idxs, rng, pyrng, dev):
+        if self._mean_size_dev is None or self._mean_size_dev.device != self.store.points.device:
+            self._mean_size_dev = torch.from_numpy(np.ascontiguousarray(self.mean_size_arr, dtype=np.float64)).to(self.store.points.device)
+        fused = lambda sids, mats: scene_prep.prepare_batch_store(self.store, sids, self.cfg, self._mean_size_dev, rng=rng, is_augment=self.is_augment,
+                                                                  device=dev, mode=self.voxel_mode, matrices=mats)
+        if self.index is None:
+            return fused([self.scene_ids[i] for i in idxs], None)
+        index = self.index
+        dev = lang_prep._device(index, dev)
+        draws, mats = [], []
+        for c in idxs:                                     # the per-sample order of draws below: descriptions, then the matrix
+            draws.append(lang_prep.draw_descriptions(index, c, rng, pyrng, self.is_augment, self.apply_word_erase))
+            if self.is_augment:
+                mats.append(scene_prep.augment_matrix(rng, self.cfg.data.transform))
+        batch = fused([index.scene_id(c) for c in idxs], mats if self.is_augment else None)
+        batch.update(lang_prep._launch(index, draws, idxs, batch, dev))
+        return batch
+
     def build(self, idxs, rng, pyrng):
         """one batch of the samples `idxs`"""
         dev = torch.device("cuda", torch.cuda.current_device()) if self.device is None else torch.device(self.device)
+        if self.fused_active(dev):
+            return self._build_fused(idxs, rng, pyrng, dev)
         prep = lambda sid: scene_prep.prepare_scene(self.store.scene(sid), self.cfg, self.mean_size_arr, rng=rng, is_augment=self.is_augment,
                                                     noise=self.noise, device=dev)
         if self.index is None:
@@ -403,7 +520,7 @@ def _namespace(index, vocabulary, glove):
                                  chunked_data=[[raw[n] for n in chunk] for chunk in index.chunks])
 
 
-def build_loaders(cfg, device, rank=0, world=1, multiview=None, store_device=None):
+def build_loaders(cfg, device, rank=0, world=1, multiview=None, store_device=None, fused=False):
     """`init_data` (scripts/train.py:220-245) with its `init_detector_data` / `init_speaker_data` / `init_listener_data` and the
     loader choice of `start_training` (:338-365) -> (training source, validation source(s), dataset, stores):
 
@@ -416,7 +533,7 @@ def build_loaders(cfg, device, rank=0, world=1, multiview=None, store_device=Non
     Training sources shuffle, validation sources do not; both are sharded over `world` ranks (Lightning's DistributedSampler).
     dataset: {"train", "val"} namespaces with vocabulary, glove, chunked_data, organized, raw_data -- the speaker's when there
     is one (scripts/train.py:284), else the listener's, None in mode 0.  stores: {"train", "val"} SceneStores on `store_device`
-    (default `device`), one per split, shared by the split's loaders."""
+    (default `device`), one per split, shared by the split's loaders.  fused: every loader's `fused=` (`PipelineLoader`)."""
     m = cfg.model
     if m.no_detection:
         raise NotImplementedError("GT-proposal modes 4-6 (no_detection) are not on the hot path")
@@ -454,7 +571,7 @@ def build_loaders(cfg, device, rank=0, world=1, multiview=None, store_device=Non
     if ("detector", "train") in lists:
         for split in ("train", "val"):
             loaders[("detector", split)] = PipelineLoader(cfg, stores[split], None, split, "detector", rank, world, seed, mean_size_arr=means,
-                                                          device=device, scene_ids=lists[("detector", split)][1])
+                                                          device=device, scene_ids=lists[("detector", split)][1], fused=fused)
         return loaders[("detector", "train")], loaders[("detector", "val")], None, stores
     vocabulary, glove = load_vocabulary(cfg, cfg.general.dataset)
     raw2label = lang_prep.raw2label_from_tsv(cfg.SCANNETV2_PATH.combine_file)
@@ -464,7 +581,7 @@ def build_loaders(cfg, device, rank=0, world=1, multiview=None, store_device=Non
         indexes[(role, split)] = lang_prep.DescriptionIndex(raw, vocabulary, glove, max_len, cfg.data.num_des_per_scene, raw2label,
                                                             scan2cad_rotation=scan2cad, split=split, device=device)
         loaders[(role, split)] = PipelineLoader(cfg, stores[split], indexes[(role, split)], split, role, rank, world, seed,
-                                                mean_size_arr=means, device=device)
+                                                mean_size_arr=means, device=device, fused=fused)
     role = "listener" if m.no_captioning else "speaker"
     dataset = {split: _namespace(indexes[(role, split)], vocabulary, glove) for split in ("train", "val")}
     if m.no_captioning or m.no_grounding:

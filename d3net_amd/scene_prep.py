@@ -376,6 +376,111 @@ def collate_scenes_device(samples, device, mode=4):
     return data
 
 
+# ------------------------------------------------------------------------------------------------ a batch from the scene store
+def fused_applicable(cfg, is_augment, store):
+    """Whether `prepare_batch_store` covers this path (a pure host predicate): the store is resident on a device and neither
+    elastic distortion nor crop runs, so every scene keeps all its points.  Not covered, and left to `prepare_scene` +
+    `collate_scenes_device`: the augmented detector-only mode (its point count is data-dependent), a pinned-host store, and
+    noise="host" (which only matters under the elastic; the loader checks it)."""
+    return torch.device(store.device).type == "cuda" and not elastic_enabled(cfg, is_augment)
+
+
+def batch_plan(offsets, table_offsets, scalars, rows):
+    """The host half of one batch over an instance index: offsets (S+1) the store's row offsets, table_offsets (S+1) the index
+    tables' offsets, scalars (S,5) = id_lo, id_hi, K, Lp, has_unlabelled per scene; rows: the store row of each batch slot (a
+    scene may repeat).  -> dict: row0 (B,) int64, slots (B,6) int32 = n, table offset, V, K, Lp, has_unlabelled per slot
+    (`d3_batch_prepare`'s two host arrays), and the totals N points, I instances, L proposal entries, V id values."""
+    rows = np.asarray(rows, np.int64).reshape(-1)
+    offsets, table_offsets, scalars = np.asarray(offsets, np.int64), np.asarray(table_offsets, np.int64), np.asarray(scalars, np.int64)
+    n = offsets[rows + 1] - offsets[rows]
+    V = np.maximum(scalars[rows, 1], 0) + 1
+    slots = np.stack([n, table_offsets[rows], V, scalars[rows, 2], scalars[rows, 3], scalars[rows, 4]], 1)
+    return {"row0": np.ascontiguousarray(offsets[rows]), "slots": np.ascontiguousarray(slots.astype(np.int32)),
+            "N": int(n.sum()), "I": int(scalars[rows, 2].sum()), "L": int(scalars[rows, 3].sum()), "V": int(V.sum())}
+
+
+_TABLE_RING = 4
+_batch_tables = {}
+
+
+def _batch_table(nbytes, device):
+    """`_collate_table` for a path that never reads back: a ring of pinned tables per (device, host thread, stream), so that the
+    host, which may run several batches ahead of the device, waits for a table's earlier copy only when the whole ring is in flight"""
+    key = (device.index, threading.get_ident(), _stream().value or 0)
+    ring = _batch_tables.setdefault(key, {"next": 0, "ents": [None] * _TABLE_RING})
+    k = ring["next"]
+    ring["next"] = (k + 1) % _TABLE_RING
+    ent = ring["ents"][k]
+    if ent is None or ent[0].numel() < nbytes:
+        ent = ring["ents"][k] = (torch.empty(int(nbytes * 1.25) + 1024, dtype=torch.uint8).pin_memory(), torch.cuda.Event())
+    elif not ent[1].query():
+        ent[1].synchronize()
+    return ent
+
+
+def prepare_batch_store(store, scene_ids, cfg, mean_size_arr, rng=None, is_augment=False, device=None, mode=4, matrices=None):
+    """The batch `collate_scenes_device([prepare_scene(store.scene(s), ...) for s in scene_ids])` builds -- the same keys, dtypes,
+    shapes and bits -- straight from a resident `dataset.SceneStore` and its `instance_index()`: one table copy and three launches
+    (csrc/batch_prep.hip, `d3_batch_prepare`) plus `pointgroup_ops.voxelization_idx`, with no read-back and no per-scene tensor.
+    A scene may fill several slots.
+
+    With is_augment one `augment_matrix(rng, ...)` is drawn per slot in slot order -- the per-scene path's draws in its order --
+    and nothing otherwise; `matrices` (one 3x3 per slot) replaces the draws for a caller that interleaves them with its own
+    (`dataset.PipelineLoader`).  mean_size_arr: (18,3), or a float64 tensor already on the device (nothing is uploaded then).
+
+    Only where `fused_applicable` holds: the elastic / crop path and a pinned-host store raise ValueError."""
+    if elastic_enabled(cfg, is_augment):
+        raise ValueError("prepare_batch_store: the augmented detector-only path (elastic distortion, crop) is prepare_scene's")
+    ix = store.instance_index()
+    dev = store.points.device
+    if device is not None and torch.device(device).type != "cpu" and torch.device(device).index not in (None, dev.index):
+        raise ValueError("prepare_batch_store: the store is on %s, not on %s" % (dev, device))
+    B = len(scene_ids)
+    if B < 1:
+        raise ValueError("prepare_batch_store: no scenes")
+    d = cfg.data
+    R, has_gt, Cf = int(d.max_num_instance), bool(d.requires_gt_mask), store.feats.shape[1]
+    mats = None
+    if is_augment:
+        if matrices is None:
+            rng = np.random if rng is None else rng
+            matrices = [augment_matrix(rng, d.transform) for _ in range(B)]
+        mats = np.ascontiguousarray(np.stack([np.asarray(m, np.float64) for m in matrices]).reshape(B, 9))
+    plan = batch_plan(store.offsets, ix.table_offsets, ix.scalars, [store.row_of(s) for s in scene_ids])
+    N, I, Lt = plan["N"], plan["I"], plan["L"]
+    if max(N, I, Lt) >= 2 ** 31:
+        _range_error("prepare_batch_store: %d points / %d instances / %d proposal entries" % (N, I, Lt))
+    ms = mean_size_arr if torch.is_tensor(mean_size_arr) and mean_size_arr.device == dev and mean_size_arr.dtype == torch.float64 \
+        else _dev_tensor(np.asarray(mean_size_arr, dtype=np.float64), torch.float64, dev)
+    if ms.numel() < 54:
+        raise ValueError("prepare_batch_store: mean_size_arr has %d values, 18 x 3 expected" % ms.numel())
+    f32, i32, i64 = torch.float32, torch.int32, torch.int64
+    new = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
+    data = {"locs": new((N, 3), f32), "locs_scaled": new((N, 4), i64), "feats": new((N, Cf), f32), "sem_labels": new((N,), i64),
+            "instance_ids": new((N,), i64), "instance_info": new((N, 12), f32), "instance_num_point": new((I,), i32)}
+    if has_gt:
+        data.update(gt_proposals_idx=new((Lt, 2), i32), gt_proposals_offset=new((I + 1,), i32))
+    data.update(batch_offsets=new((B + 1,), i32), instance_offsets=new((B + 1,), i32))
+    data.update({k: new((B, R) + _BOX_TAIL.get(k, ()), i64 if k in _I64_BOX else f32) for k in _BOX_KEYS})
+    out = np.array([data[k].data_ptr() if k in data else 0
+                    for k in _POINT_KEYS + ("batch_offsets", "instance_offsets") + _BOX_KEYS], np.uint64)
+    hp = lambda a: a.ctypes.data_as(C.c_void_p)
+    with _on(dev):
+        L = _lib.lib()
+        tbytes, nbytes = int(L.d3_batch_prepare_table_bytes(B)), int(L.d3_batch_prepare_ws_bytes(B, plan["V"]))
+        if tbytes == 0 or nbytes == 0:
+            _range_error("prepare_batch_store: %d scenes" % B)
+        table, copied = _batch_table(tbytes, dev)
+        ws = _workspace(nbytes, dev, "batch_prep")
+        call("batch_prepare", _ptr(store.points), _ptr(store.feats), _ptr(store.sem_labels), _ptr(store.instance_ids),
+             store.points.shape[0], _ptr(ix.hist), _ptr(ix.rank), _ptr(ix.start), _ptr(ix.sorted), ix.hist.shape[0],
+             hp(plan["row0"]), hp(plan["slots"]), hp(mats) if mats is not None else None, B, Cf, R, 0 if is_augment else 1,
+             int(has_gt), float(d.scale), _ptr(ms), hp(out), C.c_void_p(table.data_ptr()), _ptr(ws), ws.numel(), _stream())
+        copied.record()
+    data["voxel_locs"], data["p2v_map"], data["v2p_map"] = pointgroup_ops.voxelization_idx(data["locs_scaled"], B, mode)
+    return data
+
+
 def prepare_batch(scenes, cfg, mean_size_arr, rng=None, is_augment=True, noise="device", device=None, mode=4):
     """Raw scenes (dicts of `points` (N,3) metres, `feats` (N,C), `sem_labels` (N,) -1 ignored, `instance_ids` (N,) -1 none; numpy
     or device tensors) -> the device batch `collate.sparse_collate_fn` returns for the reference's per-scene sample dicts built

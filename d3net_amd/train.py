@@ -7,7 +7,9 @@ not a dataset loader: N scenes in batches of `data.batch_size`, the first batch 
 `--data`: `Trainer.fit` on the splits the configuration's paths name (conf/path.yaml): `dataset.build_loaders` loads each split into
 a device-resident `SceneStore` and returns the mode's training and validation sources.  Under a launcher that sets WORLD_SIZE /
 RANK / LOCAL_RANK (torch.distributed.run) every rank takes its shard of each pass.  Pretrained weights and freezes are applied as
-`init_model` does (scripts/train.py:282-327); `--teacher` clusters on the labels, for a run that has no detector weights."""
+`init_model` does (scripts/train.py:282-327); `--teacher` clusters on the labels, for a run that has no detector weights.
+`--fused-prep` builds each batch's scene half straight from the store (`scene_prep.prepare_batch_store`: no read-back, the same
+batches bit for bit) wherever that path applies; the start-up line says whether it is in use and what its index takes."""
 import argparse
 import copy
 import os
@@ -64,7 +66,14 @@ def _ranks():
     return world, rank, local_rank
 
 
-def fit_data(cfg, root, teacher=False):
+def _sources(x):
+    """the PipelineLoaders inside a source, a PairedLoader or a tuple of them"""
+    if isinstance(x, (tuple, list)):
+        return [l for s in x for l in _sources(s)]
+    return _sources(x.sources) if hasattr(x, "sources") else [x]
+
+
+def fit_data(cfg, root, teacher=False, fused=False):
     """--data: the configuration's splits through `dataset.build_loaders` into `Trainer.fit`"""
     from .checkpoint import apply_freeze, load_pretrained
     from .dataset import build_loaders
@@ -72,7 +81,7 @@ def fit_data(cfg, root, teacher=False):
     dev = torch.device("cuda", local_rank)
     torch.cuda.set_device(dev)
     torch.manual_seed(cfg.general.manual_seed)
-    train, val, dataset, stores = build_loaders(cfg, dev, rank, world)
+    train, val, dataset, stores = build_loaders(cfg, dev, rank, world, fused=fused)
     model = PipelineNet(cfg, dataset).to(dev)             # init_model (scripts/train.py:282-327)
     loaded, frozen = load_pretrained(model, cfg), apply_freeze(model, cfg)
     print("=> pretrained: %s; frozen: %s" % (", ".join(loaded) or "none", ", ".join(frozen) or "none"))
@@ -82,6 +91,13 @@ def fit_data(cfg, root, teacher=False):
     print("=> train with MODE: %d, rank %d of %d; scene store: %s; %d training batches per epoch, %s validation batches, %d epochs -> %s"
           % (model.mode, rank, world, ", ".join("%s %d scenes %.1f MiB on %s" % (k, len(s), s.bytes() / 2 ** 20, s.device)
                                                 for k, s in stores.items()), len(train), nval, trainer.epochs, trainer.root))
+    if fused:
+        loaders = _sources(train) + _sources(val)
+        active = [l for l in loaders if l.fused_active(dev)]
+        for l in active:
+            l.store.instance_index()                      # built here, once per store, not inside the first batch
+        print("=> fused batch preparation: in use by %d of %d loaders; instance index: %s"
+              % (len(active), len(loaders), ", ".join("%s %.1f MiB" % (k, s.index_bytes() / 2 ** 20) for k, s in stores.items())))
     trainer.fit(train, val)
     return trainer
 
@@ -95,6 +111,8 @@ def main(argv=None, overrides=None):
     src.add_argument("--data", action="store_true", help="train on the splits the configuration's paths name (dataset.build_loaders)")
     ap.add_argument("--teacher", action="store_true", help="with --data: cluster on the labels instead of the detector's predictions "
                     "(the switch --synthetic always sets; for a run without pretrained detector weights)")
+    ap.add_argument("--fused-prep", action="store_true", help="with --data: build batches straight from the scene store "
+                    "(scene_prep.prepare_batch_store) where that path applies")
     ap.add_argument("--epochs", type=int, default=None, help="override train.epochs")
     ap.add_argument("--root", default=None, help="run directory (default: <general.output_root>/<EXPERIMENT>)")
     args = ap.parse_args(argv)
@@ -106,7 +124,7 @@ def main(argv=None, overrides=None):
         over.setdefault("train", {})["epochs"] = args.epochs
     cfg = load_conf(os.path.join(CONF_DIR, "path.yaml"), conf, overrides=over or None)
     if args.data:
-        trainer = fit_data(cfg, args.root, args.teacher)
+        trainer = fit_data(cfg, args.root, args.teacher, args.fused_prep)
         print("=> best %s: %s (epoch %s); metrics: %s" % (trainer.monitor, trainer.best_score, trainer.best_epoch,
                                                         os.path.join(trainer.root, "logs", "metrics.jsonl")))
         return trainer

@@ -1074,6 +1074,44 @@ size_t d3_collate_table_bytes(int B);
 int d3_collate_scenes(const void *const *ptrs_host, const int *counts_host, int B, int C, int R, int has_gt, void *const *out_host,
                       void *table_host, void *table_dev, size_t table_bytes, void *stream);
 
+/* ---- a batch straight from the resident scene store (csrc/batch_prep.hip, driven by d3net_amd/scene_prep.py:prepare_batch_store)
+ * What d3_scene_transform ... d3_scene_instances per scene and d3_collate_scenes per batch compute on the path WITHOUT elastic
+ * distortion and crop (every scene keeps all its points), bit for bit, in ONE copy and THREE launches whatever B is, with no
+ * read-back: everything that depends only on a scene's instance_ids / sem_labels comes from the store's instance index.
+ *   xyz (S,3) f32, feats (S,C) f32, sem / ids (S) i32: the store's packed arrays of S rows (device), read only.
+ *   ix_hist / ix_rank / ix_start (T) i32: per scene V + 1 entries from its table offset, V = max(largest id, 0) + 1: hist[0] the
+ *     unlabelled points and hist[v + 1] those with id v; rank[v] / start[v] the exclusive scans of presence / count (np.unique
+ *     order, first row in the proposal list).  ix_sorted (S) i32, per scene from its row offset: scene-local point indices
+ *     grouped by instance in np.unique order, ascending inside each, unlabelled points last.  All read only.
+ *   row0_host (B) i64, HOST: each slot's first store row.  slots_host (B,6) i32, HOST: n points, table offset, V, K instances,
+ *     Lp labelled points, has-unlabelled flag.  One scene may fill several slots.  mats_host (B,9) f64, HOST: each slot's
+ *     augmentation matrix; read when fp32 == 0 (fp32 != 0: the float32 validation path, y = xyz).
+ *   mean_size (18,3) f64 device.  out_host (20), HOST: the device pointers of d3_collate_scenes' outputs, in its order and with
+ *     its shapes and dtypes for N / I / L the sums of n / K / Lp (7 and 8 may be NULL when has_gt == 0, and so may an output without elements); none needs zeroing.
+ *   table_host: d3_batch_prepare_table_bytes(B) bytes of (pinned) HOST memory the call fills -- per slot the offsets, counts,
+ *     matrix and running point / instance / proposal-entry totals, the three stages' tile-prefix tables, and the start values of
+ *     the per-slot minima -- and copies into ws with ONE asynchronous copy: keep it unchanged until that copy has run.
+ *   ws: d3_batch_prepare_ws_bytes(B, sum of V) device bytes: the table's copy and 9 doubles per (slot, id value).
+ * Stages, each a flat grid whose blocks find their (slot, tile) by binary search of the prefix table in LDS:
+ *   1 transform + feature rows: s = (xyz @ M) * scale per point, the per-slot minimum by integer atomics on the order-preserving
+ *     encoding; the feature rows copied once, store to batch, 16-byte accesses where both ends are 16-byte aligned;
+ *   2 one wave per (slot, id value): count, exact min / max, the sum sequential over ascending point index (float when fp32,
+ *     else double) -> instance_num_point, gt_proposals_offset, the instance's row of the nine box labels (the slot -1 / k >= 128 /
+ *     k >= R rules of d3_scene_instances); rows no instance owns are written as zeros, and the two offset tables;
+ *   3 per point locs, locs_scaled [slot, (int64) s - min], sem_labels, instance_ids (+ instances before unless -1),
+ *     instance_info; per labelled point its gt_proposals_idx row with both shifts.
+ * One writer per output element; no floating-point atomics.  y and s are recomputed where they are used, not stored.
+ *   B outside [1, 512], a slot beyond d3_scene_limits, or a total outside int32: D3_ERR_RANGE (d3_batch_prepare_table_bytes: 0);
+ *   a slot outside the store (store_rows) or the index tables (table_len), K > V, Lp > n, a NULL or misaligned pointer:
+ *   D3_ERR_ARG; all checked on the host before anything is queued. */
+size_t d3_batch_prepare_table_bytes(int B);
+size_t d3_batch_prepare_ws_bytes(int B, long long v_total);
+int d3_batch_prepare(const float *xyz, const float *feats, const int *sem, const int *ids, long long store_rows,
+                     const int *ix_hist, const int *ix_rank, const int *ix_start, const int *ix_sorted, long long table_len,
+                     const long long *row0_host, const int *slots_host, const double *mats_host, int B, int C, int R, int fp32,
+                     int has_gt, double scale, const double *mean_size, void *const *out_host, void *table_host, void *ws,
+                     size_t ws_bytes, void *stream);
+
 /* ---- multiview feature projection (csrc/multiview.hip, driven by d3net_amd/multiview.py) --------------------------------------
  * The reference's ProjectionHelper.compute_projection / project (lib/utils/projection.py:180-256) and the per-scene loop of
  * data/scannet/project_multiview_features.py:88-205.  One scene: points (N,3) float32 mesh vertices; F frames in the caller's order:
