@@ -202,6 +202,12 @@ SIGNATURES = {
     "d3_batch_prepare_table_bytes": (sz, [i32]),
     "d3_batch_prepare_ws_bytes": (sz, [i32, i64]),
     "d3_batch_prepare": (i32, [vp, vp, vp, vp, i64, vp, vp, vp, vp, i64, vp, vp, vp, i32, i32, i32, i32, i32, f64, vp, vp, vp, vp, sz, vp]),
+    "d3_store_extents_table_bytes": (sz, [i32]),
+    "d3_store_extents_ws_bytes": (sz, [i32]),
+    "d3_store_extents": (i32, [vp, i64, vp, i32, f64, vp, vp, vp, sz, vp]),
+    "d3_points_batch_table_bytes": (sz, [i32]),
+    "d3_points_batch_ws_bytes": (sz, [i32]),
+    "d3_points_batch": (i32, [vp, vp, i64, vp, i32, vp, vp, vp, i32, i32, f64, vp, vp, vp, vp, vp, vp, sz, vp]),
     "d3_multiview_limits": (i32, [pi, pi, pi]),
     "d3_multiview_project_ws_bytes": (sz, [i32, i32]),
     "d3_multiview_project": (i32, [vp, i32, vp, vp, vp, i32, C.POINTER(f64), i32, i32, vp, vp, vp, sz, vp]),

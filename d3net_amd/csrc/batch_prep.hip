@@ -13,6 +13,11 @@
 // same order as sp_transform_kernel; -ffp-contract=off), never stored: 12 bytes read per use instead of 48 written and read.
 // Every reduction is deterministic: the per-slot minimum by integer atomics on the order-preserving encoding, the per-instance
 // sums sequential over ascending point index.  Every output element has exactly one writer.
+//
+// The second half of the file is the label-free batch of the test split (d3_store_extents, d3_points_batch; driven by
+// scene_prep.py:prepare_points_store), which shares bp_find and bp_transform.  pb_points_kernel REPEATS stage 1's feature-row
+// copy line for line instead of sharing a helper: moving the copy into a function changed stage 1's generated code, and that
+// kernel's measured time is on record.  Keep the two copies in step.
 #include "scene_prep.h"
 
 #define BP_BLOCK 256
@@ -449,5 +454,269 @@ int d3_batch_prepare(const float *xyz, const float *feats, const int *sem, const
         else hipLaunchKernelGGL(bp_stage3_kernel<double>, dim3((unsigned)tiles[2]), dim3(BP_BLOCK), lds, st, a);
         D3_LAUNCH_CHECK();
     }
+    return 0;
+}
+
+// ==== the label-free scene half (lib/dataset/pipeline.py:352-380, :937-976): the test split's batch, which has no label key =========
+// Nothing is drawn and no point is dropped there, so the per-scene minimum of fl32(x * scale) is a constant of the (store, scale)
+// pair: d3_store_extents computes it ONCE for every scene of a store, and d3_points_batch is then a pure row-wise map from the
+// store's rows to the batch's rows -- one launch, no reduction, no atomics, no read-back.  The expressions are stage 1's and
+// stage 3's fp32 ones, so the keys equal the labelled path's bit for bit.
+#define SE_MAX_S 8192                 // scenes per store: a prefix table of S + 1 ints in LDS (32 KiB)
+
+struct SeScene { long long row0; int n, pad; };
+struct SeArgs { const float *xyz; const SeScene *scenes; const int *prefix; u64 *ext; int S; float scale_f; };
+
+// one launch over all scenes: job = scene, BP_PTILE points per block; the encoded minima are combined by the integer atomicMin
+__global__ void __launch_bounds__(BP_BLOCK) se_extents_kernel(SeArgs a) {
+    extern __shared__ int s_prefix[];
+    __shared__ u64 s_min[BP_BLOCK / 64][3];
+    const int t = (int)threadIdx.x;
+    const int j = bp_find(s_prefix, a.prefix, a.S);
+    const int tile = (int)blockIdx.x - s_prefix[j];
+    const int n = a.scenes[j].n;
+    const float *__restrict__ x = a.xyz + 3 * a.scenes[j].row0;
+    u64 mn[3] = {~0ull, ~0ull, ~0ull};
+    for (int k = 0; k < BP_PTILE / BP_BLOCK; ++k) {
+        int i = tile * BP_PTILE + t + k * BP_BLOCK;
+        if (i < n) {
+            double y[3], s[3];
+            bp_transform(x[3 * (size_t)i], x[3 * (size_t)i + 1], x[3 * (size_t)i + 2], nullptr, 1, 0.0, a.scale_f, y, s);
+            for (int d = 0; d < 3; d++) {
+                u64 e = sp_enc(s[d]);
+                mn[d] = e < mn[d] ? e : mn[d];
+            }
+        }
+    }
+    for (int off = 32; off > 0; off >>= 1)
+        for (int d = 0; d < 3; d++) {
+            u64 b = __shfl_xor(mn[d], off);
+            mn[d] = b < mn[d] ? b : mn[d];
+        }
+    if (d3_lane() == 0)
+        for (int d = 0; d < 3; d++) s_min[t >> 6][d] = mn[d];
+    __syncthreads();
+    if (t < 3) {
+        u64 v = s_min[0][t];
+        for (int w = 1; w < BP_BLOCK / 64; w++) v = s_min[w][t] < v ? s_min[w][t] : v;
+        atomicMin(&a.ext[3 * (size_t)j + t], v);
+    }
+}
+
+struct SeTable { SeScene *scenes; int *prefix; };
+static void se_table_layout(D3Carver &c, int S, SeTable &w) {
+    w.scenes = c.take<SeScene>(S);
+    w.prefix = c.take<int>((size_t)S + 1);
+}
+struct SeWs { char *table; };
+static void se_ws_layout(D3Carver &c, size_t table_bytes, SeWs &w) { w.table = c.take<char>(table_bytes); }
+
+size_t d3_store_extents_table_bytes(int S) {
+    if (S < 1 || S > SE_MAX_S) return 0;
+    D3Carver c(nullptr, 0);
+    SeTable w;
+    se_table_layout(c, S, w);
+    return c.off;
+}
+
+size_t d3_store_extents_ws_bytes(int S) {
+    const size_t tb = d3_store_extents_table_bytes(S);
+    if (tb == 0) return 0;
+    D3Carver c(nullptr, 0);
+    SeWs w;
+    se_ws_layout(c, tb, w);
+    return c.off;
+}
+
+int d3_store_extents(const float *xyz, long long store_rows, const long long *offsets_host, int S, double scale,
+                     unsigned long long *extents, void *table_host, void *ws, size_t ws_bytes, void *stream) {
+    if (S < 1 || S > SE_MAX_S) return D3_ERR_RANGE;
+    if (!xyz || !offsets_host || !extents || !table_host || !ws || ((size_t)extents & 7)) return D3_ERR_ARG;
+    const size_t tb = d3_store_extents_table_bytes(S);
+    D3Carver ch(table_host, tb);
+    SeTable h;
+    se_table_layout(ch, S, h);
+    const long long lim = 0x7fffffffll - BP_WTILE;
+    long long tiles = 0;
+    for (int i = 0; i < S; ++i) {
+        const long long row0 = offsets_host[i], n = offsets_host[i + 1] - row0;
+        if (n < 1 || n > SP_MAX_POINTS) return D3_ERR_RANGE;            // points.min(0) of an empty scene raises in the reference
+        if (row0 < 0 || row0 + n > store_rows) return D3_ERR_ARG;
+        h.scenes[i].row0 = row0; h.scenes[i].n = (int)n; h.scenes[i].pad = 0;
+        h.prefix[i] = (int)tiles;
+        tiles += (n + BP_PTILE - 1) / BP_PTILE;
+        if (tiles > lim) return D3_ERR_RANGE;
+    }
+    h.prefix[S] = (int)tiles;
+
+    D3Carver cw(ws, ws_bytes);
+    SeWs w;
+    se_ws_layout(cw, tb, w);
+    if (!cw.ok()) return D3_ERR_WORKSPACE;
+    D3Carver cd(w.table, tb);
+    SeTable d;
+    se_table_layout(cd, S, d);
+
+    SeArgs a;
+    a.xyz = xyz; a.scenes = d.scenes; a.prefix = d.prefix; a.ext = (u64 *)extents; a.S = S; a.scale_f = (float)scale;
+    hipStream_t st = d3_stream(stream);
+    D3_CLEAR();
+    D3_CHECK(hipMemcpyAsync(w.table, table_host, ch.off, hipMemcpyHostToDevice, st));
+    D3_CHECK(hipMemsetAsync(extents, 0xff, 3 * (size_t)S * sizeof(u64), st));      // the start value of every minimum: ~0
+    hipLaunchKernelGGL(se_extents_kernel, dim3((unsigned)tiles), dim3(BP_BLOCK), ((size_t)S + 1) * sizeof(int), st, a);
+    D3_LAUNCH_CHECK();
+    return 0;
+}
+
+struct PbSlot { long long row0; int n, srow, P, pad; };   // first store row, points, the scene's store row, points of the slots before
+struct PbArgs {
+    const float *xyz, *feats;
+    const u64 *ext;                   // (S,3) d3_store_extents
+    const PbSlot *slots;
+    const int *prefix;                // 2 jobs per slot, 2 * B + 1 entries
+    float *locs; long long *locs_scaled; float *ofeats; int *boff;
+    int B, C; float scale_f;
+};
+
+// the point rows (job 2 * slot; its first thread also writes the slot's batch_offsets entry) and the feature words (job 2 * slot + 1)
+__global__ void __launch_bounds__(BP_BLOCK) pb_points_kernel(PbArgs a) {
+    extern __shared__ int s_prefix[];
+    const int t = (int)threadIdx.x;
+    const int j = bp_find(s_prefix, a.prefix, 2 * a.B);
+    const int slot = j >> 1, tile = (int)blockIdx.x - s_prefix[j];
+    const PbSlot *__restrict__ sl = a.slots + slot;
+    const int n = sl->n, P = sl->P;
+    const long long row0 = sl->row0;
+
+    if (j & 1) {                                                  // bp_stage1_kernel's copy
+        const long long count = (long long)n * a.C, base = (long long)tile * BP_WTILE;
+        const unsigned *__restrict__ src = (const unsigned *)a.feats + row0 * a.C;
+        unsigned *__restrict__ dst = (unsigned *)a.ofeats + (long long)P * a.C;
+        if ((((size_t)src | (size_t)dst) & 15) == 0) {            // 16-byte accesses, the four loads in flight together
+            const uint4 *__restrict__ s4 = (const uint4 *)(src + base) + t;
+            uint4 *__restrict__ d4 = (uint4 *)(dst + base) + t;
+            if (base + BP_WTILE <= count) {
+                uint4 v0 = s4[0], v1 = s4[BP_BLOCK], v2 = s4[2 * BP_BLOCK], v3 = s4[3 * BP_BLOCK];
+                d4[0] = v0; d4[BP_BLOCK] = v1; d4[2 * BP_BLOCK] = v2; d4[3 * BP_BLOCK] = v3;
+            } else {                                              // the slot's last tile
+                for (int k = 0; k < BP_WTILE / (4 * BP_BLOCK); ++k) {
+                    const long long w = base + 4ll * (k * BP_BLOCK + t);
+                    if (w + 4 <= count) d4[k * BP_BLOCK] = s4[k * BP_BLOCK];
+                    else
+                        for (long long u = w; u < count; ++u) dst[u] = src[u];   // at most 3 words, in one thread
+                }
+            }
+        } else {                                                  // lane-consecutive words
+            for (int k = 0; k < BP_WTILE / BP_BLOCK; ++k) {
+                long long w = base + t + k * BP_BLOCK;
+                if (w < count) dst[w] = src[w];
+            }
+        }
+        return;
+    }
+
+    if (tile == 0 && t == 0) {                                    // every slot has points, so every slot has this block
+        a.boff[slot] = P;
+        if (slot == a.B - 1) a.boff[a.B] = P + n;
+    }
+    double mnd[3];
+    for (int d = 0; d < 3; d++) mnd[d] = sp_dec(a.ext[3 * (size_t)sl->srow + d]);
+    const float *__restrict__ x = a.xyz + 3 * row0;
+    for (int k = 0; k < BP_PTILE / BP_BLOCK; ++k) {
+        int i = tile * BP_PTILE + t + k * BP_BLOCK;
+        if (i >= n) continue;
+        const long long g = (long long)P + i;
+        double y[3], s[3];
+        bp_transform(x[3 * (size_t)i], x[3 * (size_t)i + 1], x[3 * (size_t)i + 2], nullptr, 1, 0.0, a.scale_f, y, s);
+        float ls[3];
+        for (int d = 0; d < 3; d++) {
+            a.locs[3 * g + d] = (float)y[d];
+            ls[d] = (float)(double)((float)s[d] - (float)mnd[d]);     // bp_stage3_kernel's fp32 expression
+        }
+        longlong2 *lo = (longlong2 *)(a.locs_scaled + 4 * g);         // 32-byte rows from a 16-byte aligned base
+        lo[0] = make_longlong2((long long)slot, (long long)ls[0]);
+        lo[1] = make_longlong2((long long)ls[1], (long long)ls[2]);
+    }
+}
+
+struct PbTable { PbSlot *slots; int *prefix; };
+static void pb_table_layout(D3Carver &c, int B, PbTable &w) {
+    w.slots = c.take<PbSlot>(B);
+    w.prefix = c.take<int>(2 * (size_t)B + 1);
+}
+struct PbWs { char *table; };
+static void pb_ws_layout(D3Carver &c, size_t table_bytes, PbWs &w) { w.table = c.take<char>(table_bytes); }
+
+size_t d3_points_batch_table_bytes(int B) {
+    if (B < 1 || B > BP_MAX_B) return 0;
+    D3Carver c(nullptr, 0);
+    PbTable w;
+    pb_table_layout(c, B, w);
+    return c.off;
+}
+
+size_t d3_points_batch_ws_bytes(int B) {
+    const size_t tb = d3_points_batch_table_bytes(B);
+    if (tb == 0) return 0;
+    D3Carver c(nullptr, 0);
+    PbWs w;
+    pb_ws_layout(c, tb, w);
+    return c.off;
+}
+
+int d3_points_batch(const float *xyz, const float *feats, long long store_rows, const unsigned long long *extents, int S,
+                    const long long *row0_host, const int *srow_host, const int *n_host, int B, int C, double scale,
+                    float *locs, long long *locs_scaled, float *out_feats, int *batch_offsets, void *table_host, void *ws,
+                    size_t ws_bytes, void *stream) {
+    if (B < 1 || B > BP_MAX_B || C < 0 || C > SP_MAX_FEAT || S < 1) return D3_ERR_RANGE;
+    if (!xyz || !extents || !row0_host || !srow_host || !n_host || !locs || !locs_scaled || !batch_offsets || !table_host || !ws ||
+        (C > 0 && (!feats || !out_feats)))
+        return D3_ERR_ARG;
+    // locs_scaled rows are stored 16 bytes at a time
+    if (((size_t)locs_scaled & 15) || (((size_t)locs | (size_t)out_feats | (size_t)batch_offsets | (size_t)extents) & 3) ||
+        ((size_t)extents & 7))
+        return D3_ERR_ARG;
+
+    const size_t tb = d3_points_batch_table_bytes(B);
+    D3Carver ch(table_host, tb);
+    PbTable h;
+    pb_table_layout(ch, B, h);
+    const long long lim = 0x7fffffffll - BP_WTILE;
+    long long P = 0, tiles = 0;
+    for (int i = 0; i < B; ++i) {
+        const int n = n_host[i], srow = srow_host[i];
+        const long long row0 = row0_host[i];
+        if (n < 1 || n > SP_MAX_POINTS) return D3_ERR_RANGE;             // n == 0: points.min(0) raises in the reference
+        if ((long long)n * (C > 4 ? C : 4) > lim) return D3_ERR_RANGE;
+        if (row0 < 0 || row0 + n > store_rows || srow < 0 || srow >= S) return D3_ERR_ARG;
+        PbSlot &o = h.slots[i];
+        o.row0 = row0; o.n = n; o.srow = srow; o.P = (int)P; o.pad = 0;
+        h.prefix[2 * i] = (int)tiles;
+        tiles += (n + BP_PTILE - 1) / BP_PTILE;
+        h.prefix[2 * i + 1] = (int)tiles;
+        tiles += ((long long)n * C + BP_WTILE - 1) / BP_WTILE;
+        P += n;
+        if (P > lim || tiles > lim) return D3_ERR_RANGE;
+    }
+    h.prefix[2 * B] = (int)tiles;
+
+    D3Carver cw(ws, ws_bytes);
+    PbWs w;
+    pb_ws_layout(cw, tb, w);
+    if (!cw.ok()) return D3_ERR_WORKSPACE;
+    D3Carver cd(w.table, tb);
+    PbTable d;
+    pb_table_layout(cd, B, d);
+
+    PbArgs a;
+    a.xyz = xyz; a.feats = feats; a.ext = (const u64 *)extents; a.slots = d.slots; a.prefix = d.prefix;
+    a.locs = locs; a.locs_scaled = locs_scaled; a.ofeats = out_feats; a.boff = batch_offsets;
+    a.B = B; a.C = C; a.scale_f = (float)scale;
+    hipStream_t st = d3_stream(stream);
+    D3_CLEAR();
+    // ONE copy: table_host is the caller's pinned buffer and must stay as it is until the copy has run
+    D3_CHECK(hipMemcpyAsync(w.table, table_host, ch.off, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(pb_points_kernel, dim3((unsigned)tiles), dim3(BP_BLOCK), (2 * (size_t)B + 1) * sizeof(int), st, a);
+    D3_LAUNCH_CHECK();
     return 0;
 }

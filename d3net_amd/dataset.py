@@ -10,6 +10,8 @@ the fit loop (`trainer.Trainer`), in place of the reference's `PipelineDataset._
     `InstanceIndex` instead (`scene_prep.prepare_batch_store`: no read-back, the same bits) wherever that path applies.
   * `PairedLoader`: the joint mode's `[speaker batch, listener batch]` source.
   * `build_loaders`: the sources and the `dataset` namespace of a configuration, from the paths of conf/path.yaml.
+  * `build_test_loader`: the `init_data` of benchmark/benchmark_captioning.py / benchmark_grounding.py -- a `SceneStore(labels=False)`
+    and a `PipelineLoader(label_free=True)`, whose batches (`scene_prep.prepare_points_store`) carry no label key; `predict.py` runs it.
 
 The per-sample order of random draws is `lang_prep.prepare_pipeline_batch`'s / `scene_prep.prepare_batch`'s; the generators are the
 loader's own, seeded from (seed, epoch, rank), never the global ones.
@@ -213,30 +215,38 @@ class SceneStore:
     With device="cpu" the arrays are pinned host memory and `scene()` returns non-blocking device copies issued on the caller's
     current stream (for a split whose multiview features someone does not want resident); the batches are the same."""
 
-    def __init__(self, scene_ids, offsets, arrays, device):
+    def __init__(self, scene_ids, offsets, arrays, device, labels=True):
         self.scene_ids, self.offsets = list(scene_ids), np.asarray(offsets, np.int64)
+        self.labels = bool(labels)
         self._row = {s: i for i, s in enumerate(self.scene_ids)}
         if len(self._row) != len(self.scene_ids):
             raise ValueError("SceneStore: a scene id appears twice")
         self.device = torch.device(device)
         for k in _FIELDS:
             t = torch.from_numpy(arrays[k])
-            setattr(self, k, t.pin_memory() if self.device.type == "cpu" and torch.cuda.is_available() else t.to(self.device))
+            setattr(self, k, t.pin_memory() if self.device.type == "cpu" and torch.cuda.is_available() and t.numel() else t.to(self.device))
         self._index = None
+        self._extents = {}
 
     # --------------------------------------------------------------------------------------------- construction
     @classmethod
-    def from_scenes(cls, scenes, cfg=None, device="cuda", multiview=None):
+    def from_scenes(cls, scenes, cfg=None, device="cuda", multiview=None, labels=True):
         """scenes: {scene_id: scene} in the store's order.  A scene is a raw-scene dict (`points`, `feats`, `sem_labels`,
         `instance_ids`; taken as it is) or what the reference's scene file holds (`aligned_mesh` (N,6|9), `sem_labels`,
         `instance_ids`; a `scan_export.ScanExport` counts), whose feature columns follow cfg.model.use_color / use_normal /
         use_multiview (`mesh_features`).  multiview: {scene_id: (N,128) array or tensor}; a scene missing from it gets the
-        reference's zero placeholder (pipeline.py:794-795).  Arrays may be numpy or tensors on any device."""
+        reference's zero placeholder (pipeline.py:794-795).  Arrays may be numpy or tensors on any device.
+
+        labels=False is the test split's store (pipeline.py:320-380 never reads the label arrays there, and prepare_scannet.py
+        writes placeholders): `sem_labels` / `instance_ids` are not read -- a scene may lack them -- and the store keeps two
+        zero-length arrays in their place; a scene without points is refused by name (`points.min(0)` raises in the reference)."""
         packed = {k: [] for k in _FIELDS}
         offsets, width = [0], None
         for sid, sc in scenes.items():
             if hasattr(sc, "to_reference_dict"):
                 sc = sc.to_reference_dict()
+            if not labels and len(sc["points"] if "points" in sc else sc["aligned_mesh"]) == 0:
+                raise ValueError("SceneStore: scene %s has no points" % sid)
             if "points" in sc:
                 pts, feats = _host(sc["points"], np.float32), _host(sc["feats"], np.float32)
                 feats = feats.reshape(pts.shape[0], -1)
@@ -250,8 +260,13 @@ class SceneStore:
                         mv = np.zeros((sc["aligned_mesh"].shape[0], 128), np.float32)
                 pts, feats = mesh_features(sc["aligned_mesh"], m.use_color, m.use_normal, mv)
             n = pts.shape[0]
-            sem, ids = _host(sc["sem_labels"], np.int32).reshape(-1), _host(sc["instance_ids"], np.int32).reshape(-1)
-            if pts.shape != (n, 3) or feats.shape[0] != n or sem.shape != (n,) or ids.shape != (n,):
+            if not labels:
+                if pts.shape != (n, 3) or feats.shape[0] != n:
+                    raise ValueError("%s: points %s, feats %s" % (sid, pts.shape, feats.shape))
+                sem = ids = np.zeros(0, np.int32)
+            else:
+                sem, ids = _host(sc["sem_labels"], np.int32).reshape(-1), _host(sc["instance_ids"], np.int32).reshape(-1)
+            if labels and (pts.shape != (n, 3) or feats.shape[0] != n or sem.shape != (n,) or ids.shape != (n,)):
                 raise ValueError("%s: points %s, feats %s, sem_labels %s, instance_ids %s" % (sid, pts.shape, feats.shape, sem.shape, ids.shape))
             if width is not None and feats.shape[1] != width:
                 raise ValueError("%s: %d feature columns, the scenes before have %d" % (sid, feats.shape[1], width))
@@ -261,13 +276,14 @@ class SceneStore:
             offsets.append(offsets[-1] + n)
         if width is None:
             raise ValueError("SceneStore: no scenes")
-        return cls(list(scenes), offsets, {k: np.ascontiguousarray(np.concatenate(v, 0)) for k, v in packed.items()}, device)
+        return cls(list(scenes), offsets, {k: np.ascontiguousarray(np.concatenate(v, 0)) for k, v in packed.items()}, device, labels)
 
     @classmethod
-    def load(cls, cfg, split, scan_list, device="cuda", multiview=None):
+    def load(cls, cfg, split, scan_list, device="cuda", multiview=None, labels=True):
         """`_load`'s scene half (pipeline.py:387): torch.load of `<SCANNETV2_PATH.split_data>/<split>/<scene_id><data.file_suffix>`
         per scan of `scan_list`.  multiview: as in `from_scenes`; None with model.use_multiview reads the reference's HDF5 file
-        (SCANNETV2_PATH.multiview_features) when `h5py` imports, and otherwise warns and leaves the zero placeholder."""
+        (SCANNETV2_PATH.multiview_features) when `h5py` imports, and otherwise warns and leaves the zero placeholder.
+        labels: as in `from_scenes`."""
         root = os.path.join(cfg.SCANNETV2_PATH.split_data, split)
         scenes = {s: torch.load(os.path.join(root, s + cfg.data.file_suffix), weights_only=False) for s in scan_list}
         h5 = None
@@ -281,7 +297,7 @@ class SceneStore:
                 h5 = h5py.File(cfg.SCANNETV2_PATH.multiview_features, "r", libver="latest")
                 multiview = {s: h5[s][()] for s in scan_list if s in h5}
         try:
-            return cls.from_scenes(scenes, cfg, device, multiview)
+            return cls.from_scenes(scenes, cfg, device, multiview, labels)
         finally:
             if h5 is not None:
                 h5.close()
@@ -298,7 +314,7 @@ class SceneStore:
         return int(self.offsets[i + 1] - self.offsets[i])
 
     def bytes(self):
-        """the footprint of the four packed arrays"""
+        """the footprint of the four packed arrays (the two label arrays of a labels=False store are empty)"""
         return sum(getattr(self, k).numel() * getattr(self, k).element_size() for k in _FIELDS)
 
     def row_of(self, scene_id):
@@ -307,7 +323,10 @@ class SceneStore:
 
     def instance_index(self):
         """the store's `InstanceIndex`, built on first use and kept (`scene_prep.prepare_batch_store` reads it); a resident store
-        only: a pinned-host store raises ValueError.  The store's arrays must not change afterwards."""
+        only: a pinned-host store raises ValueError, and so does a labels=False store.  The store's arrays must not change
+        afterwards."""
+        if not self.labels:
+            raise ValueError("SceneStore.instance_index: the store was built with labels=False and holds no instance ids")
         if self._index is None:
             self._index = InstanceIndex(self)
         return self._index
@@ -317,12 +336,27 @@ class SceneStore:
         `bytes()` does not count it"""
         return 0 if self._index is None else self._index.bytes()
 
+    def extents(self, scale):
+        """the (S,3) device table of `scene_prep.store_extents` for `scale` -- per scene and axis the minimum of fl32(x * scale),
+        what the label-free path subtracts (pipeline.py:352-380), in the kernels' order-preserving int64 encoding
+        (`scene_prep._decode` reads it) -- built on first use and kept per scale (`scene_prep.prepare_points_store` reads it); a
+        resident store only: a pinned-host store raises ValueError.  The store's points must not change afterwards."""
+        key = float(scale)
+        if key not in self._extents:
+            if self.device.type == "cpu":
+                raise ValueError("SceneStore.extents: the store is pinned host memory; the table serves the resident store only")
+            empty = np.flatnonzero(np.diff(self.offsets) == 0)
+            if len(empty):
+                raise ValueError("SceneStore.extents: scene %s has no points" % self.scene_ids[int(empty[0])])
+            self._extents[key] = scene_prep.store_extents(self, scale)
+        return self._extents[key]
+
     def scene(self, scene_id, device=None):
         """the raw-scene dict of `prepare_scene`: views (device store) or non-blocking device copies (pinned store; `device`
-        defaults to the current one)"""
+        defaults to the current one); `points` and `feats` only from a labels=False store"""
         i = self._row[scene_id]
         a, b = int(self.offsets[i]), int(self.offsets[i + 1])
-        out = {k: getattr(self, k)[a:b] for k in _FIELDS}
+        out = {k: getattr(self, k)[a:b] for k in (_FIELDS if self.labels else _FIELDS[:2])}
         if self.device.type == "cpu" and (device is not None or torch.cuda.is_available()):
             device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
             out = {k: v.to(device, non_blocking=True) for k, v in out.items()}
@@ -355,14 +389,23 @@ class PipelineLoader:
     fused=True builds the scene half of every batch with `scene_prep.prepare_batch_store` instead -- straight from the store and its
     instance index, no read-back, no per-scene tensor, the same draws in the same order and the same bits -- wherever
     `fused_active()` holds.  Elsewhere it silently takes the path above: the augmented detector-only mode (elastic distortion and
-    crop make the point count data-dependent), a pinned-host store or one on another device, and noise="host"."""
+    crop make the point count data-dependent), a pinned-host store or one on another device, and noise="host".
+
+    label_free (default: split == "test"; True on another split is the reference's general.task == "test") takes the `else:`
+    branch of the reference's `__getitem__` (pipeline.py:320-380): a batch is `scene_prep.prepare_points_store`'s seven keys plus,
+    with an index, the description keys of `lang_prep._launch(..., boxes=None)` -- no label key, no draw for the scene, nothing read
+    from the store's label arrays (a labels=False store serves).  shuffle then defaults to False; is_augment=True raises
+    ValueError; `fused` and `fused_active()` do not bear on it."""
 
     def __init__(self, cfg, store, index, split, mode, rank=0, world=1, seed=None, shuffle=None, is_augment=False, mean_size_arr=None,
-                 noise="device", device=None, scene_ids=None, fused=False):
+                 noise="device", device=None, scene_ids=None, fused=False, label_free=None):
         self.cfg, self.store, self.index, self.split, self.mode = cfg, store, index, split, mode
         self.rank, self.world = int(rank), int(world)
         self.seed = int(cfg.general.manual_seed if seed is None else seed)
-        self.shuffle = (split == "train") if shuffle is None else bool(shuffle)
+        self.label_free = (split == "test") if label_free is None else bool(label_free)
+        if self.label_free and is_augment:
+            raise ValueError("PipelineLoader: label_free batches are never augmented (pipeline.py:352-380 draws nothing)")
+        self.shuffle = (split == "train" and not self.label_free) if shuffle is None else bool(shuffle)
         self.is_augment, self.noise, self.device = bool(is_augment), noise, device
         self.batch_size, self.voxel_mode = int(cfg.data.batch_size), int(_opt(cfg.data, "mode", 4) or 4)
         self.apply_word_erase = bool(_opt(_opt(cfg, "train", None), "apply_word_erase", True))
@@ -423,9 +466,22 @@ class PipelineLoader:
         batch.update(lang_prep._launch(index, draws, idxs, batch, dev))
         return batch
 
+    def _build_label_free(self, idxs, rng, pyrng, dev):
+        points = lambda sids: scene_prep.prepare_points_store(self.store, sids, self.cfg, device=dev, mode=self.voxel_mode)
+        if self.index is None:
+            return points([self.scene_ids[i] for i in idxs])
+        index = self.index
+        dev = lang_prep._device(index, dev)
+        draws = [lang_prep.draw_descriptions(index, c, rng, pyrng, False, self.apply_word_erase) for c in idxs]
+        batch = points([index.scene_id(c) for c in idxs])
+        batch.update(lang_prep._launch(index, draws, idxs, None, dev))
+        return batch
+
     def build(self, idxs, rng, pyrng):
         """one batch of the samples `idxs`"""
         dev = torch.device("cuda", torch.cuda.current_device()) if self.device is None else torch.device(self.device)
+        if self.label_free:
+            return self._build_label_free(idxs, rng, pyrng, dev)
         if self.fused_active(dev):
             return self._build_fused(idxs, rng, pyrng, dev)
         prep = lambda sid: scene_prep.prepare_scene(self.store.scene(sid), self.cfg, self.mean_size_arr, rng=rng, is_augment=self.is_augment,
@@ -588,3 +644,42 @@ def build_loaders(cfg, device, rank=0, world=1, multiview=None, store_device=Non
         return loaders[(role, "train")], loaders[(role, "val")], dataset, stores
     return (PairedLoader(loaders[("speaker", "train")], loaders[("listener", "train")]),
             (loaders[("speaker", "val")], loaders[("listener", "val")]), dataset, stores)
+
+
+def prediction_entries(raw, split, task):
+    """the annotation list of a prediction run -> (entries, scan list).  captioning on the test split: one copy of raw[0] per
+    scene (benchmark/benchmark_captioning.py:66-72, `speaker_val_entries`); every other case the full list
+    (benchmark_captioning.py:75-81 for the other splits, benchmark/benchmark_grounding.py:62-69)"""
+    if task not in ("captioning", "grounding"):
+        raise ValueError("task must be 'captioning' or 'grounding', not %r" % (task,))
+    entries = speaker_val_entries(raw) if (task == "captioning" and split == "test") else copy.deepcopy(raw)
+    return entries, scan_list_of(raw)
+
+
+def build_test_loader(cfg, device, task, split="test", rank=0, world=1, multiview=None, store_device=None):
+    """`init_data` of benchmark/benchmark_captioning.py:49-104 (task="captioning": the speaker's role and max_spk_len) and of
+    benchmark/benchmark_grounding.py:45-92 (task="grounding": the listener's role and max_lis_len, no Scan2CAD table), for `split`
+    alone -> (loader, dataset, store):
+
+      loader   a label-free `PipelineLoader` over `prediction_entries` of <DATASET>_PATH.<split>_split, unshuffled;
+      dataset  {"train": a namespace with vocabulary and glove only, split: the split's `_namespace`} -- what `PipelineNet(cfg,
+               dataset)` and the submission's `chunked_data` need; the training split's scenes are not loaded;
+      store    `SceneStore.load(cfg, split, scans, labels=False)` on `store_device` (default `device`).
+
+    cfg.data.num_des_per_scene is read as it stands: the scripts' own overrides (8 / 1) are `predict.main`'s to apply."""
+    device = torch.device(device)
+    store_device = device if store_device is None else torch.device(store_device)
+    paths = cfg["%s_PATH" % cfg.general.dataset.upper()]
+    raw = json.load(open(paths["%s_split" % split]))
+    entries, scans = prediction_entries(raw, split, task)
+    store = SceneStore.load(cfg, split, scans, store_device, multiview, labels=False)
+    vocabulary, glove = load_vocabulary(cfg, cfg.general.dataset)
+    raw2label = lang_prep.raw2label_from_tsv(cfg.SCANNETV2_PATH.combine_file)
+    scan2cad = json.load(open(cfg.SCAN2CAD)) if task == "captioning" and os.path.exists(cfg.SCAN2CAD) else None
+    role, max_len = ("speaker", cfg.data.max_spk_len) if task == "captioning" else ("listener", cfg.data.max_lis_len)
+    index = lang_prep.DescriptionIndex(entries, vocabulary, glove, max_len, cfg.data.num_des_per_scene, raw2label, scan2cad_rotation=scan2cad,
+                                       split=split, device=device)
+    loader = PipelineLoader(cfg, store, index, split, role, rank, world, int(cfg.general.manual_seed), device=device, label_free=True)
+    dataset = {"train": types.SimpleNamespace(vocabulary=vocabulary, glove=glove)}
+    dataset[split] = _namespace(index, vocabulary, glove)
+    return loader, dataset, store

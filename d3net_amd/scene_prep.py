@@ -481,6 +481,78 @@ def prepare_batch_store(store, scene_ids, cfg, mean_size_arr, rng=None, is_augme
     return data
 
 
+# ------------------------------------------------------------------------------------------------ the label-free batch (test split)
+_LABEL_FREE_KEYS = ("locs", "locs_scaled", "feats", "batch_offsets", "voxel_locs", "p2v_map", "v2p_map")
+
+
+def store_extents(store, scale):
+    """ONE launch over a resident store (csrc/batch_prep.hip, `d3_store_extents`): (S,3) int64 on the store's device, per scene
+    and axis the kernels' order-preserving encoding (`_decode`) of min(fl32(x * fl32(scale))) -- `points.min(0)` of
+    pipeline.py:352-380, a constant of the (store, scale) pair since that branch draws nothing and drops no point.
+    `SceneStore.extents` caches it."""
+    dev, S = store.points.device, len(store)
+    if dev.type != "cuda":
+        raise ValueError("store_extents: the store is pinned host memory; the table serves the resident store only")
+    ext = torch.empty((S, 3), dtype=torch.int64, device=dev)
+    offsets = np.ascontiguousarray(store.offsets, dtype=np.int64)
+    with _on(dev):
+        L = _lib.lib()
+        tbytes, nbytes = int(L.d3_store_extents_table_bytes(S)), int(L.d3_store_extents_ws_bytes(S))
+        if tbytes == 0 or nbytes == 0:
+            _range_error("store_extents: %d scenes" % S)
+        table, copied = _batch_table(tbytes, dev)
+        ws = _workspace(nbytes, dev, "store_extents")
+        call("store_extents", _ptr(store.points), store.points.shape[0], offsets.ctypes.data_as(C.c_void_p), S, float(scale), _ptr(ext),
+             C.c_void_p(table.data_ptr()), _ptr(ws), ws.numel(), _stream())
+        copied.record()
+    return ext
+
+
+def prepare_points_store(store, scene_ids, cfg, device=None, mode=4):
+    """The label-free batch of the reference's test branch (pipeline.py:352-380 per sample, `sparse_collate_fn`'s :937-976 and
+    :992) straight from a resident `dataset.SceneStore`: locs (N,3) float32, locs_scaled (N,4) int64, feats (N,C) float32,
+    batch_offsets (B+1) int32 and voxel_locs / p2v_map / v2p_map -- no label key.  The arithmetic is the unaugmented labelled
+    branch's, so these seven keys equal, bit for bit, those of `collate_scenes_device([prepare_scene(store.scene(s), cfg, ...,
+    is_augment=False) for s in scene_ids])`.  One table copy and ONE launch (`d3_points_batch`) plus
+    `pointgroup_ops.voxelization_idx`; the per-scene minima come from `store.extents(cfg.data.scale)`, built on the first call.
+    The store's labels, if it has any, are ignored; a scene may fill several slots.  A pinned-host store raises ValueError.
+    The extents launch covers every scene of the store, so a store that holds a scene without points (a labelled store may) is
+    refused by that scene's name on the first call, whether or not the batch names it."""
+    dev = store.points.device
+    if dev.type != "cuda":
+        raise ValueError("prepare_points_store: the store is pinned host memory; this path serves the resident store only")
+    if device is not None and torch.device(device).type != "cpu" and torch.device(device).index not in (None, dev.index):
+        raise ValueError("prepare_points_store: the store is on %s, not on %s" % (dev, device))
+    B = len(scene_ids)
+    if B < 1:
+        raise ValueError("prepare_points_store: no scenes")
+    scale, Cf = cfg.data.scale, store.feats.shape[1]
+    ext = store.extents(scale)
+    srow = np.ascontiguousarray([store.row_of(s) for s in scene_ids], dtype=np.int32)
+    row0 = np.ascontiguousarray(store.offsets[srow], dtype=np.int64)
+    n = np.ascontiguousarray(store.offsets[srow + 1] - row0, dtype=np.int32)
+    N = int(n.sum(dtype=np.int64))
+    if N >= 2 ** 31:
+        _range_error("prepare_points_store: %d points" % N)
+    f32 = torch.float32
+    data = {"locs": torch.empty((N, 3), dtype=f32, device=dev), "locs_scaled": torch.empty((N, 4), dtype=torch.int64, device=dev),
+            "feats": torch.empty((N, Cf), dtype=f32, device=dev), "batch_offsets": torch.empty((B + 1,), dtype=torch.int32, device=dev)}
+    hp = lambda a: a.ctypes.data_as(C.c_void_p)
+    with _on(dev):
+        L = _lib.lib()
+        tbytes, nbytes = int(L.d3_points_batch_table_bytes(B)), int(L.d3_points_batch_ws_bytes(B))
+        if tbytes == 0 or nbytes == 0:
+            _range_error("prepare_points_store: %d scenes" % B)
+        table, copied = _batch_table(tbytes, dev)
+        ws = _workspace(nbytes, dev, "points_batch")
+        call("points_batch", _ptr(store.points), _ptr(store.feats), store.points.shape[0], _ptr(ext), len(store), hp(row0), hp(srow), hp(n),
+             B, Cf, float(scale), _ptr(data["locs"]), _ptr(data["locs_scaled"]), _ptr(data["feats"]), _ptr(data["batch_offsets"]),
+             C.c_void_p(table.data_ptr()), _ptr(ws), ws.numel(), _stream())
+        copied.record()
+    data["voxel_locs"], data["p2v_map"], data["v2p_map"] = pointgroup_ops.voxelization_idx(data["locs_scaled"], B, mode)
+    return data
+
+
 def prepare_batch(scenes, cfg, mean_size_arr, rng=None, is_augment=True, noise="device", device=None, mode=4):
     """Raw scenes (dicts of `points` (N,3) metres, `feats` (N,C), `sem_labels` (N,) -1 ignored, `instance_ids` (N,) -1 none; numpy
     or device tensors) -> the device batch `collate.sparse_collate_fn` returns for the reference's per-scene sample dicts built

@@ -1112,6 +1112,48 @@ int d3_batch_prepare(const float *xyz, const float *feats, const int *sem, const
                      int has_gt, double scale, const double *mean_size, void *const *out_host, void *table_host, void *ws,
                      size_t ws_bytes, void *stream);
 
+/* ---- the label-free scene half of a test-split batch (csrc/batch_prep.hip, driven by d3net_amd/scene_prep.py:prepare_points_store
+ * and d3net_amd/dataset.py:SceneStore.extents) ----
+ * lib/dataset/pipeline.py:352-380 (the `else:` branch of __getitem__: points * scale, minus points.min(0), no label read) and
+ * :937-976 (sparse_collate_fn's label-free half).  Nothing is drawn and no point is dropped there, so the per-scene minimum of
+ * fl32(x * scale) is a constant of the (store, scale) pair and the batch is a row-wise map of the store's rows.
+ *
+ * d3_store_extents (lib/dataset/pipeline.py:352-380, `points -= points.min(0)`): ONE launch over all S scenes of a store.
+ *   xyz (store_rows,3) f32 device, read only.  offsets_host (S+1) i64, HOST: the scenes' row offsets.
+ *   extents (S,3) u64 device, 8-byte aligned: per scene and axis the ORDER-PRESERVING ENCODING (csrc/scene_prep.h:sp_enc; the host
+ *     decodes it with scene_prep._decode) of min over the scene's points of (double)fl32(x * fl32(scale)); the call presets it
+ *     to ~0 itself.  The table stays encoded: d3_points_batch decodes it where it reads it, as stage 3 of d3_batch_prepare does.
+ *   table_host: d3_store_extents_table_bytes(S) bytes of (pinned) HOST memory the call fills (row offset, count, tile prefix) and
+ *     copies into ws (d3_store_extents_ws_bytes(S) device bytes) with ONE asynchronous copy: keep it until that copy has run.
+ *   A block finds its (scene, tile) by binary search of the tile-prefix table in LDS, reduces in the wave, then in the block, and
+ *   combines blocks by the integer atomicMin on the encoding (deterministic).
+ *   S outside [1, 8192], a scene without points or beyond d3_scene_limits, tiles outside int32: D3_ERR_RANGE (the size queries:
+ *   0); a NULL or misaligned pointer, offsets outside [0, store_rows]: D3_ERR_ARG; all checked before anything is queued. */
+size_t d3_store_extents_table_bytes(int S);
+size_t d3_store_extents_ws_bytes(int S);
+int d3_store_extents(const float *xyz, long long store_rows, const long long *offsets_host, int S, double scale,
+                     unsigned long long *extents, void *table_host, void *ws, size_t ws_bytes, void *stream);
+/* d3_points_batch (lib/dataset/pipeline.py:352-380 per sample, :937-976 stacked): ONE copy and ONE launch per batch.
+ *   xyz (store_rows,3) f32, feats (store_rows,C) f32: the store's packed arrays (device), read only.  extents (S,3) u64: the
+ *   table d3_store_extents wrote for the same store and scale.  row0_host (B) i64, srow_host (B) i32, n_host (B) i32, HOST: per
+ *   slot its first store row, its scene's row of `extents` and its point count; one scene may fill several slots.
+ *   Outputs (device), N the sum of n: locs (N,3) f32 = the store's xyz; locs_scaled (N,4) i64, 16-byte aligned = [slot, (int64)
+ *   (float) of fl32(fl32(x * fl32(scale)) - min) per axis] -- d3_batch_prepare's fp32 expressions, so the same bits; out_feats
+ *   (N,C) f32 (16-byte accesses where both ends are 16-byte aligned, lane-consecutive words otherwise); batch_offsets (B+1) i32,
+ *   written inside the same launch by one designated thread per slot.  None needs zeroing; one writer per element, plain stores,
+ *   no workspace reduction, no atomics, no read-back.
+ *   table_host: d3_points_batch_table_bytes(B) bytes of (pinned) HOST memory the call fills (slots, tile prefix) and copies into
+ *   ws (d3_points_batch_ws_bytes(B) device bytes) with ONE asynchronous copy: keep it unchanged until that copy has run.
+ *   B outside [1, 512], C outside [0, 256], n outside [1, d3_scene_limits' points] (an empty slot: points.min(0) raises in the
+ *   reference), a total outside int32: D3_ERR_RANGE (the size queries: 0); a NULL or misaligned pointer, a slot outside the store
+ *   or the extents table: D3_ERR_ARG; all checked on the host before anything is queued. */
+size_t d3_points_batch_table_bytes(int B);
+size_t d3_points_batch_ws_bytes(int B);
+int d3_points_batch(const float *xyz, const float *feats, long long store_rows, const unsigned long long *extents, int S,
+                    const long long *row0_host, const int *srow_host, const int *n_host, int B, int C, double scale,
+                    float *locs, long long *locs_scaled, float *out_feats, int *batch_offsets, void *table_host, void *ws,
+                    size_t ws_bytes, void *stream);
+
 /* ---- multiview feature projection (csrc/multiview.hip, driven by d3net_amd/multiview.py) --------------------------------------
  * The reference's ProjectionHelper.compute_projection / project (lib/utils/projection.py:180-256) and the per-scene loop of
  * data/scannet/project_multiview_features.py:88-205.  One scene: points (N,3) float32 mesh vertices; F frames in the caller's order:
