@@ -64,9 +64,11 @@ class _LinearMulti(Function):
             M, K = x.shape
             N = W.shape[0]
             y = torch.empty((M, N), dtype=torch.float32, device=dev)
-            probs.append(_prob(_seg(x, K, False, W, K, False, K), M, N, y, N, bias=b, relu=relu))
+            if M > 0:       # (an empty batch has no storage to point at: nothing to launch)
+                probs.append(_prob(_seg(x, K, False, W, K, False, K), M, N, y, N, bias=b, relu=relu))
             ys.append(y)
-        _launch(probs, dev)
+        if probs:
+            _launch(probs, dev)
         ctx.n, ctx.relu = n, relu
         ctx.has_b = [b is not None for b in bs]
         ctx.save_for_backward(*xs, *Ws, *(ys if relu else ()))
@@ -94,6 +96,15 @@ class _LinearMulti(Function):
             if relu:
                 dy = dy * (ys[i] > 0).to(dy.dtype)
             dx = dW = db = None
+            if M == 0:      # an empty batch: dW = dy^T x would be a K = 0 reduction, which d3_hgemm refuses (d3hip.h: K >= 1)
+                if ctx.needs_input_grad[2 + i]:
+                    dx = torch.empty((0, K), dtype=torch.float32, device=dev)
+                if ctx.needs_input_grad[2 + n + i]:
+                    dW = torch.zeros((N, K), dtype=torch.float32, device=dev)
+                if ctx.has_b[i] and ctx.needs_input_grad[2 + 2 * n + i]:
+                    db = torch.zeros(N, dtype=torch.float32, device=dev)
+                dxs.append(dx); dWs.append(dW); dbs.append(db)
+                continue
             if ctx.needs_input_grad[2 + i]:            # dx = dy W : B k-major
                 dx = torch.empty((M, K), dtype=torch.float32, device=dev)
                 probs.append(_prob(_seg(dy, N, False, W, K, True, N), M, K, dx, K))
