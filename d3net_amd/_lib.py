@@ -181,6 +181,12 @@ SIGNATURES = {
     "d3_box_wire_verts": (i32, [vp, i32, C.POINTER(f64), vp, vp, vp]),
     "d3_box_wire_text": (i32, [vp, vp, i32, C.POINTER(f64), vp, vp, vp, vp]),
     "d3_format_f6": (i32, [vp, i64, vp, vp, vp, vp]),
+    "d3_seg_submit_limits": (i32, [pi, pi, pi, pi]),
+    "d3_seg_cluster_table": (i32, [vp, i32, vp, i64, vp, i32, vp, vp, i64, vp, i32, vp, i32, vp, vp, vp, vp]),
+    "d3_seg_cluster_ids": (i32, [vp, vp, i32, vp, i64, vp, i32, vp, i32, i64, vp, vp]),
+    "d3_seg_int_lines_ws_bytes": (sz, [i32, i32]),
+    "d3_seg_int_lines": (i32, [vp, vp, i32, i32, vp, vp, vp, vp, i32, i32, vp, vp, i64, vp, vp, i32, i32, vp, vp, sz, vp]),
+    "d3_seg_mask_lines": (i32, [vp, vp, i32, vp, i64, vp, i32, i32, i32, i32, i32, i32, vp, sz, vp]),
     "d3_scene_limits": (i32, [pi, pi, pi]),
     "d3_scene_transform": (i32, [vp, i32, vp, f64, i32, vp, vp, vp]),
     "d3_scene_reduce": (i32, [vp, vp, i32, vp, vp]),

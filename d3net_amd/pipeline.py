@@ -393,6 +393,13 @@ class PipelineNet(nn.Module):
             sub = GroundingSubmission(self._description_store("predict_grounding"), device=next(self.parameters()).device)
         return self._predict(batches, sub, self.listener)
 
+    def predict_segmentation(self, batches, submission, scene_names=None, with_gt=False):
+        """the ScanNet segmentation submission files of the detector over `batches` (model/pointgroup.py:543-625 test):
+        PointGroup.predict_segmentation"""
+        if self.no_detection:
+            raise NotImplementedError("predict_segmentation needs the detector (model.no_detection is set)")
+        return self.detector.predict_segmentation(batches, submission, scene_names, with_gt)
+
     def forward(self, data_dict):
         """inference entry point (model/pipeline.py:894-925): detector -> speaker -> listener, whichever exist"""
         if not self.no_detection:

@@ -936,6 +936,36 @@ class PointGroup(nn.Module):
                 ev.add_batch(self.predict_instances(batch), gt)
         return ev.instance_results()[0], ev.semantic_results()[0]
 
+    def predict_segmentation(self, batches, submission, scene_names=None, with_gt=False):
+        """The files of the reference's test() (model/pointgroup.py:543-625) over `batches`: predict_instances in eval() mode, then
+        `submission.add_batch` (seg_submission.SegmentationSubmission: text made on the device) per batch.  A batch's scene names
+        are its `scene_id`; a batch without that key takes the next list of `scene_names`, an iterable of one list per batch.
+        with_gt: the batches carry sem_labels and instance_ids, and `submission.add_gt` writes their GT files as well.  A batch
+        without `center_label` (a label-free one) is fed under general.task == "test", for that call only.  -> the submission"""
+        named = iter(scene_names) if scene_names is not None else None
+        with evaluating(self):
+            for batch in batches:
+                if "scene_id" in batch:
+                    names = list(batch["scene_id"])
+                elif named is not None:
+                    names = list(next(named))
+                else:
+                    raise ValueError("predict_segmentation: a batch without scene_id needs scene_names (one list per batch)")
+                if with_gt and not ("sem_labels" in batch and "instance_ids" in batch):
+                    raise ValueError("predict_segmentation: with_gt needs sem_labels and instance_ids in every batch")
+                gt = {k: batch[k] for k in ("sem_labels", "instance_ids", "batch_offsets", "instance_offsets") if k in batch}
+                task = self.cfg.general.task
+                if "center_label" not in batch:
+                    self.cfg.general.task = "test"
+                try:
+                    pred = self.predict_instances(batch)
+                finally:
+                    self.cfg.general.task = task
+                submission.add_batch(pred, gt, names)
+                if with_gt:
+                    submission.add_gt(gt, names)
+        return submission
+
     def evaluate_detection(self, batches, evaluator=None):
         """Detection AP / recall per class, mAP and AR of the predictions over `batches` (collated batches that carry gt_bbox,
         gt_bbox_label and sem_cls_label on the GPU), the library's form of scripts/eval.py:128-166 (eval_detection): feed in

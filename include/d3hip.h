@@ -1305,6 +1305,45 @@ int d3_box_wire_text(const double *corners, const int *modes, int M, const doubl
                      void *stream);
 int d3_format_f6(const double *values, long long n, char *text, int *lens, int *status, void *stream);
 
+/* ---- ScanNet segmentation submission files (csrc/seg_submission.hip, driven by d3net_amd/seg_submission.py) ----------------------
+ * In place of the file loop of PointGroup.test, model/pointgroup.py:603-625 (semantic/<scene>.txt, instance/<scene>.txt,
+ * instance/predicted_masks/<scene>_<id:03d>.txt, instance/<scene>.cluster_ids.txt) and of the GT files of lib/utils/eval.py:14-56;
+ * the bytes equal those of d3net_amd/seg_eval.py:write_predictions / write_gt.  All pointers are device memory, int32 unless said.
+ * No kernel waits for another workgroup; plain vector stores and integer atomics only; no workspace but d3_seg_int_lines'.
+ * d3_seg_submit_limits : lines per tile of d3_seg_int_lines (1024), its largest width (12), the most scenes per batch (4096), the
+ *   ints per row of the cluster table (5).
+ * d3_seg_cluster_table : model/pointgroup.py:608-623.  pick (n) proposal ids in pick order, proposals_idx (L,2), proposals_offset
+ *   (P+1), semantic_pred (N), scores (n) float32, batch_offsets (B+1), lut (nlut) = the raw class id of a predicted class.  table
+ *   (n,5) receives per pick [scene of its first member, scene-local id = earlier picks of that scene, lut[semantic_pred[first
+ *   member]], flags, the score's bits]; a pick with an empty member list, or whose first member lies in no scene, is skipped: scene =
+ *   id = -1, flags = 1.  counts (B): picks per scene.  *status |= 2 for a semantic_pred outside [0, nlut) (clamped), |= 4 for a pick
+ *   outside [0, P), offsets outside [0, L] or a first member outside [0, N) (skipped).  One workgroup.
+ * d3_seg_cluster_ids   : model/pointgroup.py:611-619.  cluster_ids (N) = the id of the LAST picked proposal of the point's scene
+ *   that holds it, -1 for none: a fill launch, then atomicMax of the id per member entry; members outside the pick's scene are left.
+ * d3_seg_int_lines     : np.savetxt(fmt="%d") (model/pointgroup.py:606, :625; lib/utils/eval.py:14-35) of one or two value arrays
+ *   (values1 / lens1 NULL: one) cut by the same offsets (B+1) into B segments.  Per text: values (n_values), an optional lut
+ *   applied first, width = the bytes of the longest line with its newline (2..12).  Segment b's text starts at byte offsets[b] *
+ *   width of `text` (n_values * width bytes) and is dense from there; lens (B) int64 receives its length.  tile_prefix (B+1): the
+ *   exclusive scan of ceil(segment length / 1024), tiles its last entry.  Three launches: per-tile byte totals, per-segment scan,
+ *   the text.  *status |= 1 for a value whose line exceeds width (printed as 0), |= 2 for a value outside its lut (clamped), |= 4
+ *   for tables that do not fit n_values (such a tile stores nothing).  ws: d3_seg_int_lines_ws_bytes(tiles, number of texts).
+ * d3_seg_mask_lines    : model/pointgroup.py:614-624, the mask files c_lo .. c_lo + m - 1 of `scene`, whose points are [lo, lo +
+ *   npts): text (16-byte aligned, text_bytes >= 2 m npts rounded up to 16) receives per file npts lines "0\n" / "1\n", file c at
+ *   byte 2 npts (c - c_lo): a fill by 16-byte stores, then one byte store per member entry.  table / pick as above.
+ * B outside [1, 4096], n above 2^20, L / N / n_values * width outside int32, a width outside [2, 12]: D3_ERR_RANGE before any launch. */
+int d3_seg_submit_limits(int *tile_lines, int *max_width, int *max_scenes, int *table_cols);
+int d3_seg_cluster_table(const int *pick, int n, const int *proposals_idx, long long L, const int *proposals_offset, int P,
+                         const int *semantic_pred, const float *scores, long long N, const int *batch_offsets, int B, const int *lut,
+                         int nlut, int *table, int *counts, int *status, void *stream);
+int d3_seg_cluster_ids(const int *table, const int *pick, int n, const int *proposals_idx, long long L, const int *proposals_offset,
+                       int P, const int *batch_offsets, int B, long long N, int *cluster_ids, void *stream);
+size_t d3_seg_int_lines_ws_bytes(int tiles, int ntext);
+int d3_seg_int_lines(const int *values0, const int *lut0, int nlut0, int width0, char *text0, long long *lens0, const int *values1,
+                     const int *lut1, int nlut1, int width1, char *text1, long long *lens1, long long n_values, const int *offsets,
+                     const int *tile_prefix, int B, int tiles, int *status, void *ws, size_t ws_bytes, void *stream);
+int d3_seg_mask_lines(const int *table, const int *pick, int n, const int *proposals_idx, long long L, const int *proposals_offset, int P,
+                      int scene, int lo, int npts, int c_lo, int m, char *text, size_t text_bytes, void *stream);
+
 /* ---- running records of logged scalars (csrc/metric_log.hip, driven by d3net_amd.metric_log.MetricLog) --------------------
  * In place of Lightning's `self.log(..., on_epoch=True)` (model/pipeline.py:149,182,...): one launch per step folds every
  * scalar logged in that step into its slot's record; nothing is read back.
