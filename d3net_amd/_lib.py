@@ -208,6 +208,10 @@ SIGNATURES = {
     "d3_batch_prepare_table_bytes": (sz, [i32]),
     "d3_batch_prepare_ws_bytes": (sz, [i32, i64]),
     "d3_batch_prepare": (i32, [vp, vp, vp, vp, i64, vp, vp, vp, vp, i64, vp, vp, vp, i32, i32, i32, i32, i32, f64, vp, vp, vp, vp, sz, vp]),
+    "d3_batch_elastic_table_bytes": (sz, [i32, i32]),
+    "d3_batch_elastic_ws_bytes": (sz, [vp, i32, i32, i32]),
+    "d3_batch_elastic": (i32, [vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f64, i32, i32, f64, f64, f64, i32, vp, vp,
+                               vp, vp, vp, sz, vp]),
     "d3_store_extents_table_bytes": (sz, [i32]),
     "d3_store_extents_ws_bytes": (sz, [i32]),
     "d3_store_extents": (i32, [vp, i64, vp, i32, f64, vp, vp, vp, sz, vp]),

@@ -15,7 +15,7 @@
 // sums sequential over ascending point index.  Every output element has exactly one writer.
 //
 // The second half of the file is the label-free batch of the test split (d3_store_extents, d3_points_batch; driven by
-// scene_prep.py:prepare_points_store), which shares bp_find and bp_transform.  pb_points_kernel REPEATS stage 1's feature-row
+// scene_prep.py:prepare_points_store), which shares bp_find and bp_transform (scene_prep.h, with the box-label rows).  pb_points_kernel REPEATS stage 1's feature-row
 // copy line for line instead of sharing a helper: moving the copy into a function changed stage 1's generated code, and that
 // kernel's measured time is on record.  Keep the two copies in step.
 #include "scene_prep.h"
@@ -33,13 +33,6 @@ struct BpSlot {
     double m[9];
 };
 
-struct BpOut {                        // scene_prep._POINT_KEYS, batch_offsets, instance_offsets, scene_prep._BOX_KEYS
-    float *locs; long long *locs_scaled; float *feats; long long *sem, *ids; float *info; int *num_point, *gt_idx, *gt_off;
-    int *boff, *ioff;
-    float *center; long long *sem_cls, *head_cls; float *head_res; long long *size_cls; float *size_res;
-    long long *obj_id, *label; float *bbox;
-};
-
 struct BpArgs {
     const float *xyz, *feats;
     const int *sem, *ids, *hist, *rank, *start, *sorted;
@@ -52,35 +45,6 @@ struct BpArgs {
     double scale; float scale_f;
     BpOut o;
 };
-
-// loads the prefix table into LDS and returns the job j with s_prefix[j] <= b < s_prefix[j + 1] (jobs without tiles are skipped)
-__device__ __forceinline__ int bp_find(int *s_prefix, const int *__restrict__ prefix, int J) {
-    for (int i = (int)threadIdx.x; i <= J; i += (int)blockDim.x) s_prefix[i] = prefix[i];
-    __syncthreads();
-    const int b = (int)blockIdx.x;
-    int lo = 0, hi = J;
-    while (hi - lo > 1) {
-        int mid = (lo + hi) >> 1;
-        if (s_prefix[mid] <= b) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
-// sp_transform_kernel's two paths for one point
-__device__ __forceinline__ void bp_transform(float x0, float x1, float x2, const double *m, int fp32, double scale, float scale_f,
-                                             double *y, double *s) {
-    if (fp32) {                                       // points.copy() * scale: float32
-        y[0] = x0; y[1] = x1; y[2] = x2;
-        s[0] = (double)(x0 * scale_f); s[1] = (double)(x1 * scale_f); s[2] = (double)(x2 * scale_f);
-    } else {                                          // np.matmul(xyz, m) in float64, then * scale
-        for (int j = 0; j < 3; j++) {
-            double v = (double)x0 * m[j] + (double)x1 * m[3 + j];
-            v = v + (double)x2 * m[6 + j];
-            y[j] = v;
-            s[j] = v * scale;
-        }
-    }
-}
 
 // ---- stage 1: the per-slot minimum of s (job 2 * slot) and the feature rows, store -> batch (job 2 * slot + 1) ---------------------
 __global__ void __launch_bounds__(BP_BLOCK) bp_stage1_kernel(BpArgs a) {
@@ -164,19 +128,7 @@ __global__ void __launch_bounds__(64) bp_stage2_kernel(BpArgs a) {
     const int kmax = K - 1 - sh;
 
     if (j & 1) {
-        const int k = idx * 64 + lane;
-        if (k < R) {
-            const long long row = (long long)slot * R + k;
-            const bool owned = (k < 128 && k <= kmax) || (sh == 1 && K >= 1 && k == R - 1);
-            a.o.head_cls[row] = 0;
-            a.o.head_res[row] = 0.0f;
-            if (!owned) {
-                for (int d = 0; d < 3; d++) { a.o.center[3 * row + d] = 0.0f; a.o.size_res[3 * row + d] = 0.0f; }
-                a.o.sem_cls[row] = 0; a.o.size_cls[row] = 0; a.o.obj_id[row] = 0; a.o.label[row] = 0;
-                float4 *bb = (float4 *)(a.o.bbox + 24 * row);       // 96-byte rows from a 16-byte aligned base
-                for (int q = 0; q < 6; q++) bb[q] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            }
-        }
+        bp_unowned_rows(a.o, slot, R, K, sh, idx * 64 + lane);
         if (idx == 0 && lane == 0) {
             a.o.boff[slot] = sl->P;
             a.o.ioff[slot] = sl->I;
@@ -236,24 +188,7 @@ __global__ void __launch_bounds__(64) bp_stage2_kernel(BpArgs a) {
     if (k >= 128 || k >= R) return;
     if (k < 0 && R - 1 < 128 && kmax >= R - 1) return;
     const long long row = (long long)slot * R + (k < 0 ? R - 1 : k);
-    int c = a.sem[row0 + sorted[st]];
-    c = c >= 2 ? c - 2 : 17;
-    double ctr[3], size[3];
-    for (int d = 0; d < 3; d++) {
-        ctr[d] = (double)((mn[d] + mx[d]) / (T)2);
-        size[d] = (double)(mx[d] - mn[d]);
-        a.o.center[3 * row + d] = (float)ctr[d];
-        a.o.size_res[3 * row + d] = (float)(size[d] - a.mean_size[3 * c + d]);
-    }
-    a.o.sem_cls[row] = c; a.o.size_cls[row] = c; a.o.obj_id[row] = v; a.o.label[row] = 1;
-    // get_3d_box_batch with heading 0: corners = center + (+-l/2, +-w/2, +-h/2)
-    const int sx[8] = {1, 1, -1, -1, 1, 1, -1, -1}, sy[8] = {1, -1, -1, 1, 1, -1, -1, 1}, sz[8] = {1, 1, 1, 1, -1, -1, -1, -1};
-    float *bb = a.o.bbox + 24 * row;
-    for (int q = 0; q < 8; q++) {
-        bb[3 * q] = (float)(sx[q] * (size[0] / 2) + ctr[0]);
-        bb[3 * q + 1] = (float)(sy[q] * (size[1] / 2) + ctr[1]);
-        bb[3 * q + 2] = (float)(sz[q] * (size[2] / 2) + ctr[2]);
-    }
+    bp_box_row<T>(a.o, row, a.sem[row0 + sorted[st]], v, mn, mx, a.mean_size);
 }
 
 // ---- stage 3: the point rows (job 2 * slot) and the GT proposal list (job 2 * slot + 1) ------------------------------------------------

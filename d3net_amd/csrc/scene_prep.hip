@@ -117,26 +117,11 @@ int d3_scene_reduce(const double *s, const int *ids, int n, unsigned long long *
 }
 
 // ---- device noise: Philox4x32-10 + Box-Muller, counter = element index / 4, key = seed --------------------------------------
-__device__ __forceinline__ uint4 sp_philox(uint4 c, uint2 k) {
-    for (int r = 0; r < 10; r++) {
-        unsigned lo0 = 0xD2511F53u * c.x, hi0 = __umulhi(0xD2511F53u, c.x);
-        unsigned lo1 = 0xCD9E8D57u * c.z, hi1 = __umulhi(0xCD9E8D57u, c.z);
-        c = make_uint4(hi1 ^ c.y ^ k.x, lo1, hi0 ^ c.w ^ k.y, lo0);
-        k.x += 0x9E3779B9u; k.y += 0xBB67AE85u;
-    }
-    return c;
-}
-
 __global__ void sp_noise_kernel(float *__restrict__ g, long long count, u64 seed) {
     long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     for (; 4 * t < count; t += (long long)gridDim.x * blockDim.x) {
-        uint4 r = sp_philox(make_uint4((unsigned)t, (unsigned)(t >> 32), 0u, 0u), make_uint2((unsigned)seed, (unsigned)(seed >> 32)));
-        const float inv = 2.3283064365386963e-10f;                 // 2^-32
-        float u1 = ((float)r.x + 1.0f) * inv, u2 = (float)r.y * inv;  // u1 in (0, 1]
-        float u3 = ((float)r.z + 1.0f) * inv, u4 = (float)r.w * inv;
-        u1 = fminf(u1, 1.0f); u3 = fminf(u3, 1.0f);
-        float ra = sqrtf(-2.0f * logf(u1)), rb = sqrtf(-2.0f * logf(u3));
-        float z[4] = {ra * cospif(2.0f * u2), ra * sinpif(2.0f * u2), rb * cospif(2.0f * u4), rb * sinpif(2.0f * u4)};
+        float z[4];
+        sp_noise_quad(t, seed, z);
         for (int j = 0; j < 4; j++)
             if (4 * t + j < count) g[4 * t + j] = z[j];
     }
@@ -158,7 +143,6 @@ int d3_scene_noise(float *grid, long long count, unsigned long long seed, void *
 // for the z passes; the grids are at most a few MB (L2-resident) and the six launches cost microseconds.
 __global__ void sp_blur_kernel(const float *__restrict__ in, float *__restrict__ out, int X, int Y, int Z, int axis) {
     long long per = (long long)X * Y * Z, total = 3 * per;
-    const double w = (double)(1.0f / 3.0f);
     long long stride = axis == 0 ? (long long)Y * Z : (axis == 1 ? Z : 1);
     int L = axis == 0 ? X : (axis == 1 ? Y : Z);
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
@@ -167,54 +151,15 @@ __global__ void sp_blur_kernel(const float *__restrict__ in, float *__restrict__
         float a = c > 0 ? in[i - stride] : 0.0f;
         float b = in[i];
         float d = c < L - 1 ? in[i + stride] : 0.0f;
-        double t = 0.0;
-        t += (double)a * w;
-        t += (double)b * w;
-        t += (double)d * w;
-        out[i] = (float)t;
+        out[i] = sp_blur_tap(a, b, d);
     }
-}
-
-// largest k in [0, L-2] with ax[k] <= x (scipy's find_interval_ascending, in-range x)
-__device__ __forceinline__ int sp_interval(const double *ax, int L, double x) {
-    int lo = 0, hi = L - 1;
-    while (lo < hi - 1) {
-        int mid = (lo + hi) >> 1;
-        if (x < ax[mid]) hi = mid; else lo = mid;
-    }
-    return lo;
 }
 
 // RegularGridInterpolator(ax, noise, bounds_error=0, fill_value=0) at s, then s += g * mag
 __global__ void sp_interp_kernel(double *__restrict__ s, int n, const float *__restrict__ g, const double *__restrict__ axes,
                                  int X, int Y, int Z, double mag) {
-    const double *ax[3] = {axes, axes + X, axes + X + Y};
-    int L[3] = {X, Y, Z};
-    long long per = (long long)X * Y * Z;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-        double x[3] = {s[3 * i], s[3 * i + 1], s[3 * i + 2]};
-        int idx[3];
-        double y[3];
-        bool oob = false;
-        for (int d = 0; d < 3; d++) {
-            oob = oob || x[d] < ax[d][0] || x[d] > ax[d][L[d] - 1];
-            idx[d] = sp_interval(ax[d], L[d], x[d]);
-            y[d] = (x[d] - ax[d][idx[d]]) / (ax[d][idx[d] + 1] - ax[d][idx[d]]);
-        }
-        double v[3] = {0.0, 0.0, 0.0};
-        if (!oob) {
-            for (int h = 0; h < 8; h++) {            // itertools.product order: the last axis varies fastest
-                int b0 = (h >> 2) & 1, b1 = (h >> 1) & 1, b2 = h & 1;
-                double wt = 1.0;
-                wt = wt * (b0 ? y[0] : 1.0 - y[0]);
-                wt = wt * (b1 ? y[1] : 1.0 - y[1]);
-                wt = wt * (b2 ? y[2] : 1.0 - y[2]);
-                long long e = ((long long)(idx[0] + b0) * Y + (idx[1] + b1)) * Z + (idx[2] + b2);
-                for (int c = 0; c < 3; c++) v[c] = v[c] + (double)g[c * per + e] * wt;
-            }
-        }
-        for (int c = 0; c < 3; c++) s[3 * i + c] = x[c] + v[c] * mag;
-    }
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
+        sp_interp_point(s + 3 * (size_t)i, g, axes, X, Y, Z, mag);
 }
 
 size_t d3_scene_elastic_ws_bytes(int X, int Y, int Z) {
@@ -267,13 +212,7 @@ struct SpVec6 { double off[3], rng[3]; };
 __global__ void sp_crop_kernel(const double *__restrict__ s, int n, SpVec6 p, int *__restrict__ flags, int *__restrict__ count) {
     int c = 0;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-        bool lo = true, hi = true;
-        for (int d = 0; d < 3; d++) {
-            double v = s[3 * i + d] + p.off[d];
-            lo = lo && v >= 0.0;
-            hi = hi && v < p.rng[d];
-        }
-        int f = (lo && hi) ? 1 : 0;
+        int f = sp_crop_keep(s + 3 * (size_t)i, p.off, p.rng);
         flags[i] = f;
         c += f;
     }
@@ -393,20 +332,7 @@ __global__ void sp_presence_kernel(const int *__restrict__ ids, int n, int V, in
 // val_of[v] = the id the points that had id v end with; orig_at[u] = which original id holds value u now (-1: none).
 __global__ void sp_relabel_map_kernel(const int *__restrict__ pres, int V, int *__restrict__ val_of, int *__restrict__ orig_at) {
     if (blockIdx.x != 0 || threadIdx.x != 0) return;
-    int cur = -1;
-    for (int v = 0; v < V; v++) {
-        val_of[v] = v;
-        orig_at[v] = pres[v] ? v : -1;
-        if (pres[v]) cur = v;
-    }
-    for (int j = 0; j < cur; j++) {
-        if (orig_at[j] != -1) continue;
-        int o = orig_at[cur];
-        orig_at[j] = o;
-        val_of[o] = j;
-        orig_at[cur] = -1;
-        while (cur > j && orig_at[cur] == -1) cur--;
-    }
+    sp_relabel_walk(pres, V, val_of, orig_at);
 }
 
 __global__ void sp_relabel_apply_kernel(int *__restrict__ ids, int n, int V, const int *__restrict__ val_of) {

@@ -227,6 +227,7 @@ class SceneStore:
             setattr(self, k, t.pin_memory() if self.device.type == "cpu" and torch.cuda.is_available() and t.numel() else t.to(self.device))
         self._index = None
         self._extents = {}
+        self._absmax = None
 
     # --------------------------------------------------------------------------------------------- construction
     @classmethod
@@ -351,6 +352,16 @@ class SceneStore:
             self._extents[key] = scene_prep.store_extents(self, scale)
         return self._extents[key]
 
+    def absmax(self):
+        """the (S,3) float64 HOST table of per-scene, per-axis max |xyz| (0 for a scene without points), what
+        `scene_prep.elastic_grid_bound` sizes the noise grids from; built on first use (one reduction per scene, one read) and
+        kept.  The store's points must not change afterwards."""
+        if self._absmax is None:
+            zero = torch.zeros(3, dtype=torch.float32, device=self.points.device)
+            rows = [self.points[int(a):int(b)].abs().amax(0) if b > a else zero for a, b in zip(self.offsets[:-1], self.offsets[1:])]
+            self._absmax = torch.stack(rows).cpu().numpy().astype(np.float64)
+        return self._absmax
+
     def scene(self, scene_id, device=None):
         """the raw-scene dict of `prepare_scene`: views (device store) or non-blocking device copies (pinned store; `device`
         defaults to the current one); `points` and `feats` only from a labels=False store"""
@@ -388,8 +399,14 @@ class PipelineLoader:
 
     fused=True builds the scene half of every batch with `scene_prep.prepare_batch_store` instead -- straight from the store and its
     instance index, no read-back, no per-scene tensor, the same draws in the same order and the same bits -- wherever
-    `fused_active()` holds.  Elsewhere it silently takes the path above: the augmented detector-only mode (elastic distortion and
-    crop make the point count data-dependent), a pinned-host store or one on another device, and noise="host".
+    `fused_active()` holds.  Elsewhere it takes the path above: the augmented detector-only mode (elastic distortion and crop make
+    the point count data-dependent), a pinned-host store or one on another device, and noise="host".
+
+    fused_elastic=True (with fused=True) covers the first of these: where `fused_elastic_active()` holds -- is_augment in the
+    detector-only configuration, noise="device", the store resident on the loader's device -- a batch is
+    `scene_prep.prepare_batch_store_elastic`'s: one read-back per batch instead of four or more per scene.  Its crop draws come from
+    a generator seeded per slot, not from the pass's, so a batch equals the per-scene path's whenever no slot is cropped (always,
+    at the shipped data.max_num_point) and is a different, equally valid crop otherwise.
 
     label_free (default: split == "test"; True on another split is the reference's general.task == "test") takes the `else:`
     branch of the reference's `__getitem__` (pipeline.py:320-380): a batch is `scene_prep.prepare_points_store`'s seven keys plus,
@@ -398,7 +415,7 @@ class PipelineLoader:
     ValueError; `fused` and `fused_active()` do not bear on it."""
 
     def __init__(self, cfg, store, index, split, mode, rank=0, world=1, seed=None, shuffle=None, is_augment=False, mean_size_arr=None,
-                 noise="device", device=None, scene_ids=None, fused=False, label_free=None):
+                 noise="device", device=None, scene_ids=None, fused=False, label_free=None, fused_elastic=False):
         self.cfg, self.store, self.index, self.split, self.mode = cfg, store, index, split, mode
         self.rank, self.world = int(rank), int(world)
         self.seed = int(cfg.general.manual_seed if seed is None else seed)
@@ -411,6 +428,7 @@ class PipelineLoader:
         self.apply_word_erase = bool(_opt(_opt(cfg, "train", None), "apply_word_erase", True))
         self.mean_size_arr = mean_size_arr
         self.fused, self._mean_size_dev = bool(fused), None
+        self.fused_elastic = bool(fused_elastic)
         self.scene_ids = list(store.scene_ids if scene_ids is None else scene_ids) if index is None else None
         self._next_epoch = 0
         self.last_order = None
@@ -448,9 +466,40 @@ class PipelineLoader:
         dev = torch.device("cuda", torch.cuda.current_device()) if dev is None else torch.device(dev)
         return dev.type == "cuda" and dev.index in (None, self.store.points.device.index)
 
-    def _build_fused(self, idxs, rng, pyrng, dev):
+    def fused_elastic_active(self, device=None):
+        """whether `build` takes `scene_prep.prepare_batch_store_elastic` (a host predicate): fused and fused_elastic are set,
+        the elastic distortion and crop run (is_augment in the detector-only configuration), noise is "device", and the store is
+        resident on the loader's device"""
+        if not (self.fused and self.fused_elastic and self.noise == "device" and not self.label_free
+                and scene_prep.elastic_applicable(self.cfg, self.is_augment, self.store)):
+            return False
+        dev = self.device if device is None else device
+        dev = torch.device("cuda", torch.cuda.current_device()) if dev is None else torch.device(dev)
+        return dev.type == "cuda" and dev.index in (None, self.store.points.device.index)
+
+    def _mean_sizes(self):
         if self._mean_size_dev is None or self._mean_size_dev.device != self.store.points.device:
             self._mean_size_dev = torch.from_numpy(np.ascontiguousarray(self.mean_size_arr, dtype=np.float64)).to(self.store.points.device)
+        return self._mean_size_dev
+
+    def _build_fused_elastic(self, idxs, rng, pyrng, dev):
+        elastic = lambda sids, draws: scene_prep.prepare_batch_store_elastic(self.store, sids, self.cfg, self._mean_sizes(), rng=rng, device=dev,
+                                                                             mode=self.voxel_mode, draws=draws)
+        if self.index is None:
+            return elastic([self.scene_ids[i] for i in idxs], None)
+        index = self.index
+        dev = lang_prep._device(index, dev)
+        descr, draws = [], []
+        for c in idxs:                                     # per sample: the description draws, then the scene's matrix and seed
+            descr.append(lang_prep.draw_descriptions(index, c, rng, pyrng, self.is_augment, self.apply_word_erase))
+            m = scene_prep.augment_matrix(rng, self.cfg.data.transform)
+            draws.append((m, int(rng.randint(0, 2 ** 31 - 1))))
+        batch = elastic([index.scene_id(c) for c in idxs], draws)
+        batch.update(lang_prep._launch(index, descr, idxs, batch, dev))
+        return batch
+
+    def _build_fused(self, idxs, rng, pyrng, dev):
+        self._mean_sizes()
         fused = lambda sids, mats: scene_prep.prepare_batch_store(self.store, sids, self.cfg, self._mean_size_dev, rng=rng, is_augment=self.is_augment,
                                                                   device=dev, mode=self.voxel_mode, matrices=mats)
         if self.index is None:
@@ -484,6 +533,8 @@ class PipelineLoader:
             return self._build_label_free(idxs, rng, pyrng, dev)
         if self.fused_active(dev):
             return self._build_fused(idxs, rng, pyrng, dev)
+        if self.fused_elastic_active(dev):
+            return self._build_fused_elastic(idxs, rng, pyrng, dev)
         prep = lambda sid: scene_prep.prepare_scene(self.store.scene(sid), self.cfg, self.mean_size_arr, rng=rng, is_augment=self.is_augment,
                                                     noise=self.noise, device=dev)
         if self.index is None:
@@ -576,7 +627,7 @@ def _namespace(index, vocabulary, glove):
                                  chunked_data=[[raw[n] for n in chunk] for chunk in index.chunks])
 
 
-def build_loaders(cfg, device, rank=0, world=1, multiview=None, store_device=None, fused=False):
+def build_loaders(cfg, device, rank=0, world=1, multiview=None, store_device=None, fused=False, augment=False):
     """`init_data` (scripts/train.py:220-245) with its `init_detector_data` / `init_speaker_data` / `init_listener_data` and the
     loader choice of `start_training` (:338-365) -> (training source, validation source(s), dataset, stores):
 
@@ -589,7 +640,9 @@ def build_loaders(cfg, device, rank=0, world=1, multiview=None, store_device=Non
     Training sources shuffle, validation sources do not; both are sharded over `world` ranks (Lightning's DistributedSampler).
     dataset: {"train", "val"} namespaces with vocabulary, glove, chunked_data, organized, raw_data -- the speaker's when there
     is one (scripts/train.py:284), else the listener's, None in mode 0.  stores: {"train", "val"} SceneStores on `store_device`
-    (default `device`), one per split, shared by the split's loaders.  fused: every loader's `fused=` (`PipelineLoader`)."""
+    (default `device`), one per split, shared by the split's loaders.  fused: every loader's `fused=` (`PipelineLoader`).
+    augment: the TRAINING loaders' `is_augment=` (the reference dataset's own switch, which scripts/train.py leaves off); they then
+    also get `fused_elastic=fused`.  Validation loaders are never augmented."""
     m = cfg.model
     if m.no_detection:
         raise NotImplementedError("GT-proposal modes 4-6 (no_detection) are not on the hot path")
@@ -627,7 +680,9 @@ def build_loaders(cfg, device, rank=0, world=1, multiview=None, store_device=Non
     if ("detector", "train") in lists:
         for split in ("train", "val"):
             loaders[("detector", split)] = PipelineLoader(cfg, stores[split], None, split, "detector", rank, world, seed, mean_size_arr=means,
-                                                          device=device, scene_ids=lists[("detector", split)][1], fused=fused)
+                                                          device=device, scene_ids=lists[("detector", split)][1], fused=fused,
+                                                          is_augment=bool(augment) and split == "train",
+                                                          fused_elastic=bool(augment) and bool(fused) and split == "train")
         return loaders[("detector", "train")], loaders[("detector", "val")], None, stores
     vocabulary, glove = load_vocabulary(cfg, cfg.general.dataset)
     raw2label = lang_prep.raw2label_from_tsv(cfg.SCANNETV2_PATH.combine_file)
@@ -637,7 +692,9 @@ def build_loaders(cfg, device, rank=0, world=1, multiview=None, store_device=Non
         indexes[(role, split)] = lang_prep.DescriptionIndex(raw, vocabulary, glove, max_len, cfg.data.num_des_per_scene, raw2label,
                                                             scan2cad_rotation=scan2cad, split=split, device=device)
         loaders[(role, split)] = PipelineLoader(cfg, stores[split], indexes[(role, split)], split, role, rank, world, seed,
-                                                mean_size_arr=means, device=device, fused=fused)
+                                                mean_size_arr=means, device=device, fused=fused,
+                                                is_augment=bool(augment) and split == "train",
+                                                fused_elastic=bool(augment) and bool(fused) and split == "train")
     role = "listener" if m.no_captioning else "speaker"
     dataset = {split: _namespace(indexes[(role, split)], vocabulary, glove) for split in ("train", "val")}
     if m.no_captioning or m.no_grounding:

@@ -11,6 +11,9 @@ synchronises with the device, per scene:
   * each crop iteration's kept-point count (the reference's `while` loop);
   * the instance count and labelled-point count (output shapes).
 
+`prepare_batch_store` (no elastic, no crop: no read-back at all) and `prepare_batch_store_elastic` (the augmented detector-only mode:
+one read-back per batch) build the same batches straight from a resident `dataset.SceneStore` instead.
+
 Random draws come from `rng` (a numpy RandomState, or None for numpy's global state as the reference's loader uses) in the
 reference's order: randn(3,3) jitter, randint(0,2) flip, rand() rotation, then the noise grids, then one rand(3) per crop
 iteration.  noise="host" draws the six noise grids with rng.randn in the reference's order and sizes, which reproduces the
@@ -76,6 +79,28 @@ def crop_loop(count, n, pc_range, max_num_point, scale, rng):
         valid = count(offset, max_pc_range.astype(np.float64))
         max_pc_range[:2] -= 32
     return offset, valid
+
+
+def crop_max_iters(full_scale):
+    """The hard bound of `crop_loop`'s iterations: once max_pc_range[:2] = full_scale - 32 j is <= 0 no point passes
+    `0 <= p < max_pc_range`, the count is 0 and the loop ends; that happens at j = ceil(full_scale / 32), the (j + 1)-th iteration."""
+    return int(-(-float(full_scale) // 32)) + 1
+
+
+_NOISE_ABS_MAX = 6.67      # csrc/scene_prep.h:sp_noise_quad: |z| <= sqrt(-2 ln 2^-32) = 6.66; blur and interpolation are convex
+
+
+def elastic_grid_bound(absmax_xyz, m, scale, call, slack=1):
+    """An upper bound, from host data alone, of the noise-grid shape `grid_shape(|s|.max(0), gran)` of elastic call 0 or 1 for
+    s = (xyz @ m) * scale: |s_d| <= scale * sum_j |m[j, d]| * absmax_xyz[j]; call 1 adds 6.67 * mag_0, the most the first
+    distortion can move a point.  `slack` cells per axis cover the rounding of the float64 products (a relative 1e-15) and of
+    the noise kernel's float32 arithmetic.  -> (3,) int64"""
+    params = elastic_params(scale)
+    gran = params[call][0]
+    b = float(scale) * (np.abs(np.asarray(m, np.float64)).T @ np.asarray(absmax_xyz, np.float64))
+    if call == 1:
+        b = b + _NOISE_ABS_MAX * params[0][1]
+    return (np.floor(b).astype(np.int64) // int(gran) + 3 + int(slack)).astype(np.int64)
 
 
 def relabel_table(present):
@@ -479,6 +504,151 @@ def prepare_batch_store(store, scene_ids, cfg, mean_size_arr, rng=None, is_augme
         copied.record()
     data["voxel_locs"], data["p2v_map"], data["v2p_map"] = pointgroup_ops.voxelization_idx(data["locs_scaled"], B, mode)
     return data
+
+
+# ------------------------------------------------------------------------------------------------ the elastic / crop batch from the store
+READBACK_COLUMNS = ("kept", "K", "Lp", "X1", "Y1", "Z1", "X2", "Y2", "Z2", "crop_iters")
+_readback_tables = {}
+
+
+def _readback_table(B, device):
+    """the pinned host image of one batch's read-back table, per (device, host thread, stream)"""
+    key = (device.index, threading.get_ident(), _stream().value or 0)
+    t = _readback_tables.get(key)
+    if t is None or t.shape[0] < B:
+        t = _readback_tables[key] = torch.empty((max(B, 8), len(READBACK_COLUMNS)), dtype=torch.int32).pin_memory()
+    return t[:B]
+
+
+def elastic_applicable(cfg, is_augment, store):
+    """Whether `prepare_batch_store_elastic` covers this path (a pure host predicate): the store is resident on a device and the
+    elastic distortion and crop run (the augmented detector-only mode) -- the complement of `fused_applicable` on a resident store."""
+    return torch.device(store.device).type == "cuda" and elastic_enabled(cfg, is_augment)
+
+
+def elastic_batch_queue(store, scene_ids, cfg, mean_size_arr, rng=None, device=None, draws=None):
+    """The queueing half of `prepare_batch_store_elastic`: the draws, the host bound of the noise grids, one table copy and every
+    launch, with no wait for the device.  -> the pending batch `elastic_batch_finish` completes."""
+    if not elastic_enabled(cfg, True):
+        raise ValueError("prepare_batch_store_elastic: no elastic distortion in this configuration (a language mode): prepare_batch_store's")
+    ix = store.instance_index()                        # a pinned-host store raises ValueError here
+    dev = store.points.device
+    if device is not None and torch.device(device).type != "cpu" and torch.device(device).index not in (None, dev.index):
+        raise ValueError("prepare_batch_store_elastic: the store is on %s, not on %s" % (dev, device))
+    B = len(scene_ids)
+    if B < 1:
+        raise ValueError("prepare_batch_store_elastic: no scenes")
+    d = cfg.data
+    scale, R, has_gt, Cf = d.scale, int(d.max_num_instance), bool(d.requires_gt_mask), store.feats.shape[1]
+    params = elastic_params(scale)
+    grans = [int(g) for g, _ in params]
+    if any(g < 1 or g != gf for g, (gf, _) in zip(grans, params)):
+        raise ValueError("prepare_batch_store_elastic: data.scale %r gives the elastic granularities %r" % (scale, [g for g, _ in params]))
+    crop_scale = d.full_scale[1]
+    T = crop_max_iters(crop_scale)
+    if draws is None:
+        rng = np.random if rng is None else rng
+        draws = []
+        for _ in range(B):                             # prepare_scene's draws in its order: the matrix, then the noise seed
+            m = augment_matrix(rng, d.transform)
+            draws.append((m, int(rng.randint(0, 2 ** 31 - 1))))
+    if len(draws) != B:
+        raise ValueError("prepare_batch_store_elastic: %d draws for %d slots" % (len(draws), B))
+    mats = np.ascontiguousarray(np.stack([np.asarray(m, np.float64) for m, _ in draws]).reshape(B, 9))
+    seeds = np.ascontiguousarray([int(sd) for _, sd in draws], dtype=np.uint64)
+    crop_u = np.ascontiguousarray(np.stack([np.random.RandomState(int(sd)).rand(T, 3) for _, sd in draws]))
+    rows = np.asarray([store.row_of(s) for s in scene_ids], np.int64)
+    row0 = np.ascontiguousarray(store.offsets[rows])
+    n = store.offsets[rows + 1] - row0
+    V = np.maximum(ix.scalars[rows, 1], 0) + 1
+    absmax = store.absmax()
+    bounds = np.stack([np.concatenate([elastic_grid_bound(absmax[r], mats[i].reshape(3, 3), scale, e) for e in (0, 1)])
+                       for i, r in enumerate(rows)])
+    if bounds.max() >= 2 ** 31:
+        _range_error("prepare_batch_store_elastic: noise grid bound %d" % int(bounds.max()))
+    slots = np.ascontiguousarray(np.concatenate([n[:, None], V[:, None], bounds], 1).astype(np.int32))
+    N, Vt = int(n.sum()), int(V.sum())
+    ms = mean_size_arr if torch.is_tensor(mean_size_arr) and mean_size_arr.device == dev and mean_size_arr.dtype == torch.float64 \
+        else _dev_tensor(np.asarray(mean_size_arr, dtype=np.float64), torch.float64, dev)
+    if ms.numel() < 54:
+        raise ValueError("prepare_batch_store_elastic: mean_size_arr has %d values, 18 x 3 expected" % ms.numel())
+    hp = lambda a: a.ctypes.data_as(C.c_void_p)
+    with _on(dev):
+        L = _lib.lib()
+        tbytes = int(L.d3_batch_elastic_table_bytes(B, T))
+        nbytes = int(L.d3_batch_elastic_ws_bytes(hp(slots), B, Cf, T)) if tbytes else 0
+        if tbytes == 0 or nbytes == 0:                 # refused before anything is allocated or queued
+            _range_error("prepare_batch_store_elastic: %d scenes, %d points, noise grid bounds up to %s, %d crop iterations"
+                         % (B, N, bounds.max(0).tolist(), T))
+        f32, i32, i64 = torch.float32, torch.int32, torch.int64
+        new = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
+        data = {"locs": new((N, 3), f32), "locs_scaled": new((N, 4), i64), "feats": new((N, Cf), f32), "sem_labels": new((N,), i64),
+                "instance_ids": new((N,), i64), "instance_info": new((N, 12), f32), "instance_num_point": new((Vt,), i32)}
+        if has_gt:
+            data.update(gt_proposals_idx=new((N, 2), i32), gt_proposals_offset=new((Vt + 1,), i32))
+        data.update(batch_offsets=new((B + 1,), i32), instance_offsets=new((B + 1,), i32))
+        data.update({k: new((B, R) + _BOX_TAIL.get(k, ()), i64 if k in _I64_BOX else f32) for k in _BOX_KEYS})
+        out = np.array([data[k].data_ptr() if k in data else 0
+                        for k in _POINT_KEYS + ("batch_offsets", "instance_offsets") + _BOX_KEYS], np.uint64)
+        readback = new((B, len(READBACK_COLUMNS)), i32)
+        table, copied = _batch_table(tbytes, dev)
+        ws = _workspace(nbytes, dev, "batch_elastic")
+        call("batch_elastic", _ptr(store.points), _ptr(store.feats), _ptr(store.sem_labels), _ptr(store.instance_ids),
+             store.points.shape[0], hp(row0), hp(slots), hp(mats), hp(seeds), hp(crop_u), B, Cf, R, T, int(has_gt), float(scale),
+             grans[0], grans[1], float(params[0][1]), float(params[1][1]), float(crop_scale), int(d.max_num_point), _ptr(ms), hp(out),
+             _ptr(readback), C.c_void_p(table.data_ptr()), _ptr(ws), ws.numel(), _stream())
+        copied.record()
+        host = _readback_table(B, dev)
+        host.copy_(readback, non_blocking=True)        # queued behind the launches; `elastic_batch_finish` waits for it
+        done = torch.cuda.Event()
+        done.record()
+    return {"data": data, "readback": host, "done": done, "bounds": bounds, "B": B, "has_gt": has_gt, "keep": (readback, ms)}
+
+
+def elastic_batch_finish(pending, mode=4, info=None):
+    """The batch's ONE device-to-host read: waits for the read-back table, checks the real noise-grid shapes against the host's
+    bound (a wrong bound is an error, never a silent clamp), and cuts the outputs to their real lengths.  info: a dict that
+    receives `readback` (B,10) int32 in `READBACK_COLUMNS` order and `bounds` (B,6)."""
+    pending["done"].synchronize()
+    rb = pending["readback"].numpy().copy()
+    if info is not None:
+        info.update(readback=rb, bounds=pending["bounds"].copy())
+    if (rb[:, 3:9] > pending["bounds"]).any():
+        bad = int(np.argmax((rb[:, 3:9] > pending["bounds"]).any(1)))
+        raise RuntimeError("prepare_batch_store_elastic: slot %d: real noise grids %s exceed the host bound %s"
+                           % (bad, rb[bad, 3:9].tolist(), pending["bounds"][bad].tolist()))
+    data, B = pending["data"], pending["B"]
+    kept, I, Lt = (int(v) for v in rb[:, :3].sum(0, dtype=np.int64))
+    for k in ("locs", "locs_scaled", "feats", "sem_labels", "instance_ids", "instance_info"):
+        data[k] = data[k][:kept]
+    data["instance_num_point"] = data["instance_num_point"][:I]
+    if pending["has_gt"]:
+        data["gt_proposals_idx"] = data["gt_proposals_idx"][:Lt]
+        data["gt_proposals_offset"] = data["gt_proposals_offset"][:I + 1]
+    data["voxel_locs"], data["p2v_map"], data["v2p_map"] = pointgroup_ops.voxelization_idx(data["locs_scaled"], B, mode)
+    return data
+
+
+def prepare_batch_store_elastic(store, scene_ids, cfg, mean_size_arr, rng=None, device=None, mode=4, draws=None, info=None):
+    """The batch `collate_scenes_device([prepare_scene(store.scene(s), cfg, msa, rng, is_augment=True, noise="device") for s in
+    scene_ids])` builds in the augmented detector-only mode (`elastic_enabled(cfg, True)`: jitter / flip / rotation, two elastic
+    distortions, crop to data.max_num_point, `_croppedInstanceIds`; pipeline.py:145-164) -- the same keys, dtypes, shapes and bits
+    -- straight from a resident `dataset.SceneStore` (csrc/batch_elastic.hip, `d3_batch_elastic`): one table copy and a number of
+    launches that depends neither on the batch size, nor on the scenes' sizes, nor on the crop iterations any slot runs; no
+    per-scene tensor; ONE device-to-host read per batch (`READBACK_COLUMNS` per slot) besides the voxelisation's own count
+    read-back.  A scene may fill several slots; every slot must have points.
+
+    Draws, per slot in slot order: `augment_matrix(rng, cfg.data.transform)` and `seed = rng.randint(0, 2**31 - 1)` --
+    `prepare_scene`'s draws in its order -- and nothing else from `rng`: the crop loop's draws are the rows of
+    `np.random.RandomState(seed).rand(crop_max_iters(full_scale[1]), 3)`, one row per iteration, so the caller's stream advances
+    the same way whatever the data does (the per-scene path takes one `rng.rand(3)` per crop iteration from the caller's stream
+    instead).  Whenever no slot is cropped the batch and the generator's state afterwards equal the per-scene path's outright.
+    `draws` (one `(matrix, seed)` per slot) replaces the draws.  mean_size_arr: as for `prepare_batch_store`.
+
+    Only where `elastic_applicable` holds: a configuration without the elastic and a pinned-host store raise ValueError; a noise
+    grid bound beyond the library's grid limits, more than 512 slots or a slot without points raise the library's range error,
+    all before anything is queued."""
+    return elastic_batch_finish(elastic_batch_queue(store, scene_ids, cfg, mean_size_arr, rng, device, draws), mode, info)
 
 
 # ------------------------------------------------------------------------------------------------ the label-free batch (test split)

@@ -9,7 +9,10 @@ a device-resident `SceneStore` and returns the mode's training and validation so
 RANK / LOCAL_RANK (torch.distributed.run) every rank takes its shard of each pass.  Pretrained weights and freezes are applied as
 `init_model` does (scripts/train.py:282-327); `--teacher` clusters on the labels, for a run that has no detector weights.
 `--fused-prep` builds each batch's scene half straight from the store (`scene_prep.prepare_batch_store`: no read-back, the same
-batches bit for bit) wherever that path applies; the start-up line says whether it is in use and what its index takes."""
+batches bit for bit) wherever that path applies; the start-up line says whether it is in use and what its index takes.
+`--augment` augments the training split (the reference dataset's `is_augment`, which scripts/train.py leaves off); in the
+detector-only mode that is PointGroup's own recipe -- elastic distortion and crop -- and with `--fused-prep` those batches come from
+`scene_prep.prepare_batch_store_elastic` (one read-back per batch)."""
 import argparse
 import copy
 import os
@@ -73,7 +76,7 @@ def _sources(x):
     return _sources(x.sources) if hasattr(x, "sources") else [x]
 
 
-def fit_data(cfg, root, teacher=False, fused=False):
+def fit_data(cfg, root, teacher=False, fused=False, augment=False):
     """--data: the configuration's splits through `dataset.build_loaders` into `Trainer.fit`"""
     from .checkpoint import apply_freeze, load_pretrained
     from .dataset import build_loaders
@@ -81,7 +84,7 @@ def fit_data(cfg, root, teacher=False, fused=False):
     dev = torch.device("cuda", local_rank)
     torch.cuda.set_device(dev)
     torch.manual_seed(cfg.general.manual_seed)
-    train, val, dataset, stores = build_loaders(cfg, dev, rank, world, fused=fused)
+    train, val, dataset, stores = build_loaders(cfg, dev, rank, world, fused=fused, augment=augment)
     model = PipelineNet(cfg, dataset).to(dev)             # init_model (scripts/train.py:282-327)
     loaded, frozen = load_pretrained(model, cfg), apply_freeze(model, cfg)
     print("=> pretrained: %s; frozen: %s" % (", ".join(loaded) or "none", ", ".join(frozen) or "none"))
@@ -93,11 +96,14 @@ def fit_data(cfg, root, teacher=False, fused=False):
                                                 for k, s in stores.items()), len(train), nval, trainer.epochs, trainer.root))
     if fused:
         loaders = _sources(train) + _sources(val)
-        active = [l for l in loaders if l.fused_active(dev)]
+        active = [l for l in loaders if l.fused_active(dev) or l.fused_elastic_active(dev)]
+        elastic = [l for l in active if l.fused_elastic_active(dev)]
         for l in active:
             l.store.instance_index()                      # built here, once per store, not inside the first batch
-        print("=> fused batch preparation: in use by %d of %d loaders; instance index: %s"
-              % (len(active), len(loaders), ", ".join("%s %.1f MiB" % (k, s.index_bytes() / 2 ** 20) for k, s in stores.items())))
+            if l in elastic:
+                l.store.absmax()
+        print("=> fused batch preparation: in use by %d of %d loaders (%d on the elastic / crop path); instance index: %s"
+              % (len(active), len(loaders), len(elastic), ", ".join("%s %.1f MiB" % (k, s.index_bytes() / 2 ** 20) for k, s in stores.items())))
     trainer.fit(train, val)
     return trainer
 
@@ -113,6 +119,9 @@ def main(argv=None, overrides=None):
                     "(the switch --synthetic always sets; for a run without pretrained detector weights)")
     ap.add_argument("--fused-prep", action="store_true", help="with --data: build batches straight from the scene store "
                     "(scene_prep.prepare_batch_store) where that path applies")
+    ap.add_argument("--augment", action="store_true", help="with --data: augment the training split as the reference dataset's "
+                    "is_augment does (jitter / flip / rotation; elastic distortion and crop in the detector-only mode); with "
+                    "--fused-prep the detector-only mode's batches come from scene_prep.prepare_batch_store_elastic")
     ap.add_argument("--epochs", type=int, default=None, help="override train.epochs")
     ap.add_argument("--root", default=None, help="run directory (default: <general.output_root>/<EXPERIMENT>)")
     args = ap.parse_args(argv)
@@ -124,7 +133,7 @@ def main(argv=None, overrides=None):
         over.setdefault("train", {})["epochs"] = args.epochs
     cfg = load_conf(os.path.join(CONF_DIR, "path.yaml"), conf, overrides=over or None)
     if args.data:
-        trainer = fit_data(cfg, args.root, args.teacher, args.fused_prep)
+        trainer = fit_data(cfg, args.root, args.teacher, args.fused_prep, args.augment)
         print("=> best %s: %s (epoch %s); metrics: %s" % (trainer.monitor, trainer.best_score, trainer.best_epoch,
                                                         os.path.join(trainer.root, "logs", "metrics.jsonl")))
         return trainer

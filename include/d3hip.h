@@ -1154,6 +1154,43 @@ int d3_points_batch(const float *xyz, const float *feats, long long store_rows, 
                     float *locs, long long *locs_scaled, float *out_feats, int *batch_offsets, void *table_host, void *ws,
                     size_t ws_bytes, void *stream);
 
+/* ---- the augmented detector-only batch from the resident scene store (csrc/batch_elastic.hip, driven by
+ * d3net_amd/scene_prep.py:prepare_batch_store_elastic) ----
+ * lib/dataset/pipeline.py:145-164 (`_augment`, the two `elastic` calls of lib/utils/transform.py, `points -= points.min(0)`,
+ * lib/utils/pc.py:crop, `_croppedInstanceIds` :699-709), then :711-772 / :804-833 and sparse_collate_fn's stacking: what
+ * d3_scene_transform ... d3_scene_instances compute per scene WITH elastic distortion and crop and d3_collate_scenes then stacks,
+ * bit for bit, in a number of copies and launches that depends neither on B, nor on the scenes' sizes, nor on the crop iterations
+ * any slot runs, and with no read-back inside the call: `readback` is for the caller to fetch once, afterwards.
+ *   xyz / feats / sem / ids, store_rows, row0_host, mats_host, mean_size, out_host: as for d3_batch_prepare, except that every
+ *     output is allocated at its upper bound -- N = sum of n point rows, sum of V instances (+ 1 offsets), N proposal rows -- and
+ *     the leading kept rows / K instances / Lp entries are written.
+ *   slots_host (B,8) i32, HOST: n points (>= 1), V = max(largest id, 0) + 1, and the caller's UPPER BOUND of the two noise-grid
+ *     shapes (3 + 3 ints, each in [3, 2048], at most 2^25 cells): the workspace regions are sized by it, the real shape
+ *     `int32(|s| max) // gran + 3` is taken on the device from the reduction and clamped to it.
+ *   seeds_host (B) u64, HOST: elastic e of a slot draws d3_scene_noise's stream with key (seed << 1) | e, counter = element index
+ *     in the slot's real (3, X, Y, Z) layout.  crop_u_host (B,T,3) f64, HOST: the crop loop's draws, one row per iteration.
+ *   T: the bound of pc.py:crop's loop, ceil(crop_scale / 32) + 1 (1 .. 80); gran0 / gran1, mag0 / mag1: the two elastic calls'
+ *     granularity and magnitude; crop_scale: data.full_scale[1]; max_num_point: data.max_num_point.
+ *   readback (B,10) i32 DEVICE: per slot kept points, K, Lp, the two real grid shapes as computed (a value above the bound means
+ *     the bound was wrong and the batch is void) and the crop iterations run.
+ *   table_host: d3_batch_elastic_table_bytes(B, T) bytes of (pinned) HOST memory the call fills and copies into ws with ONE
+ *     asynchronous copy: keep it unchanged until that copy has run.  ws: d3_batch_elastic_ws_bytes(slots_host, B, C, T) bytes.
+ * Stages: transform (y, s float64 kept; per-slot |s| max) -- twice: resolve the grid shape and axes, noise, six 3-tap passes,
+ * interpolation (+ the next reduction) -- offset -- T crop launches (a finished slot's blocks exit) -- scan + emit (stable
+ * compaction over all slots) + feature rows -- presence, relabel walk (one thread per slot), apply + hist -- rank / start / totals
+ * (one block) -- keys, one stable sort over (slot, rank) -- one wave per (slot, id value) -- unowned box rows -- info / proposal rows.
+ * Integer atomics only (encoded min / max, counts); per-instance sums sequential over ascending point index.
+ *   B outside [1, 512], T outside [1, 80], a slot without points or beyond d3_scene_limits, a bound outside the grid limits, a
+ *   total outside int32: D3_ERR_RANGE (the size queries: 0); a NULL or misaligned pointer, a slot outside the store: D3_ERR_ARG;
+ *   all checked on the host before anything is queued. */
+size_t d3_batch_elastic_table_bytes(int B, int T);
+size_t d3_batch_elastic_ws_bytes(const int *slots_host, int B, int C, int T);
+int d3_batch_elastic(const float *xyz, const float *feats, const int *sem, const int *ids, long long store_rows,
+                     const long long *row0_host, const int *slots_host, const double *mats_host, const unsigned long long *seeds_host,
+                     const double *crop_u_host, int B, int C, int R, int T, int has_gt, double scale, int gran0, int gran1,
+                     double mag0, double mag1, double crop_scale, int max_num_point, const double *mean_size, void *const *out_host,
+                     int *readback, void *table_host, void *ws, size_t ws_bytes, void *stream);
+
 /* ---- multiview feature projection (csrc/multiview.hip, driven by d3net_amd/multiview.py) --------------------------------------
  * The reference's ProjectionHelper.compute_projection / project (lib/utils/projection.py:180-256) and the per-scene loop of
  * data/scannet/project_multiview_features.py:88-205.  One scene: points (N,3) float32 mesh vertices; F frames in the caller's order:
