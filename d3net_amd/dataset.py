@@ -458,95 +458,66 @@ class PipelineLoader:
         per_rank = (self.num_samples() + self.world - 1) // self.world
         return (per_rank + self.batch_size - 1) // self.batch_size
 
-    def fused_active(self, device=None):
-        """whether `build` takes `scene_prep.prepare_batch_store` (a host predicate)"""
-        if not (self.fused and self.noise != "host" and scene_prep.fused_applicable(self.cfg, self.is_augment, self.store)):
-            return False
+    def _store_on(self, device=None):
+        """whether the store is resident on the loader's device (`device`, else the loader's, else the current one)"""
         dev = self.device if device is None else device
         dev = torch.device("cuda", torch.cuda.current_device()) if dev is None else torch.device(dev)
         return dev.type == "cuda" and dev.index in (None, self.store.points.device.index)
+
+    def fused_active(self, device=None):
+        """whether `build` takes `scene_prep.prepare_batch_store` (a host predicate)"""
+        return (self.fused and self.noise != "host" and scene_prep.fused_applicable(self.cfg, self.is_augment, self.store)
+                and self._store_on(device))
 
     def fused_elastic_active(self, device=None):
         """whether `build` takes `scene_prep.prepare_batch_store_elastic` (a host predicate): fused and fused_elastic are set,
         the elastic distortion and crop run (is_augment in the detector-only configuration), noise is "device", and the store is
         resident on the loader's device"""
-        if not (self.fused and self.fused_elastic and self.noise == "device" and not self.label_free
-                and scene_prep.elastic_applicable(self.cfg, self.is_augment, self.store)):
-            return False
-        dev = self.device if device is None else device
-        dev = torch.device("cuda", torch.cuda.current_device()) if dev is None else torch.device(dev)
-        return dev.type == "cuda" and dev.index in (None, self.store.points.device.index)
+        return (self.fused and self.fused_elastic and self.noise == "device" and not self.label_free
+                and scene_prep.elastic_applicable(self.cfg, self.is_augment, self.store) and self._store_on(device))
 
-    def _mean_sizes(self):
-        if self._mean_size_dev is None or self._mean_size_dev.device != self.store.points.device:
-            self._mean_size_dev = torch.from_numpy(np.ascontiguousarray(self.mean_size_arr, dtype=np.float64)).to(self.store.points.device)
+    def mean_sizes(self):
+        """`mean_size_arr` as the float64 tensor on the store's device the store paths take, uploaded once"""
+        dev = self.store.points.device
+        if self._mean_size_dev is None or self._mean_size_dev.device != dev:
+            self._mean_size_dev = scene_prep._mean_sizes_on(self.mean_size_arr, dev, "PipelineLoader")
         return self._mean_size_dev
 
-    def _build_fused_elastic(self, idxs, rng, pyrng, dev):
-        elastic = lambda sids, draws: scene_prep.prepare_batch_store_elastic(self.store, sids, self.cfg, self._mean_sizes(), rng=rng, device=dev,
-                                                                             mode=self.voxel_mode, draws=draws)
-        if self.index is None:
-            return elastic([self.scene_ids[i] for i in idxs], None)
-        index = self.index
-        dev = lang_prep._device(index, dev)
-        descr, draws = [], []
-        for c in idxs:                                     # per sample: the description draws, then the scene's matrix and seed
-            descr.append(lang_prep.draw_descriptions(index, c, rng, pyrng, self.is_augment, self.apply_word_erase))
-            m = scene_prep.augment_matrix(rng, self.cfg.data.transform)
-            draws.append((m, int(rng.randint(0, 2 ** 31 - 1))))
-        batch = elastic([index.scene_id(c) for c in idxs], draws)
-        batch.update(lang_prep._launch(index, descr, idxs, batch, dev))
-        return batch
-
-    def _build_fused(self, idxs, rng, pyrng, dev):
-        self._mean_sizes()
-        fused = lambda sids, mats: scene_prep.prepare_batch_store(self.store, sids, self.cfg, self._mean_size_dev, rng=rng, is_augment=self.is_augment,
-                                                                  device=dev, mode=self.voxel_mode, matrices=mats)
-        if self.index is None:
-            return fused([self.scene_ids[i] for i in idxs], None)
-        index = self.index
-        dev = lang_prep._device(index, dev)
-        draws, mats = [], []
-        for c in idxs:                                     # the per-sample order of draws below: descriptions, then the matrix
-            draws.append(lang_prep.draw_descriptions(index, c, rng, pyrng, self.is_augment, self.apply_word_erase))
-            if self.is_augment:
-                mats.append(scene_prep.augment_matrix(rng, self.cfg.data.transform))
-        batch = fused([index.scene_id(c) for c in idxs], mats if self.is_augment else None)
-        batch.update(lang_prep._launch(index, draws, idxs, batch, dev))
-        return batch
-
-    def _build_label_free(self, idxs, rng, pyrng, dev):
-        points = lambda sids: scene_prep.prepare_points_store(self.store, sids, self.cfg, device=dev, mode=self.voxel_mode)
-        if self.index is None:
-            return points([self.scene_ids[i] for i in idxs])
-        index = self.index
-        dev = lang_prep._device(index, dev)
-        draws = [lang_prep.draw_descriptions(index, c, rng, pyrng, False, self.apply_word_erase) for c in idxs]
-        batch = points([index.scene_id(c) for c in idxs])
-        batch.update(lang_prep._launch(index, draws, idxs, None, dev))
-        return batch
+    def _scene_half(self, rng, dev):
+        """The scene-half strategy of `build` -> (draw, batch_of): `draw(scene_id)` runs per sample, right after that sample's
+        description draws, and takes the scene's draws from `rng` (None: the path draws nothing); `batch_of(scene_ids, results)`
+        turns the per-sample results into the scene batch."""
+        cfg, store, mode, P = self.cfg, self.store, self.voxel_mode, scene_prep
+        if self.label_free:
+            return None, lambda sids, _: P.prepare_points_store(store, sids, cfg, device=dev, mode=mode)
+        if self.fused_active(dev):
+            draw = (lambda sid: P.augment_matrix(rng, cfg.data.transform)) if self.is_augment else None
+            return draw, lambda sids, mats: P.prepare_batch_store(store, sids, cfg, self.mean_sizes(), is_augment=self.is_augment, device=dev,
+                                                                  mode=mode, matrices=mats)
+        if self.fused_elastic_active(dev):
+            draw = lambda sid: (P.augment_matrix(rng, cfg.data.transform), int(rng.randint(0, 2 ** 31 - 1)))
+            return draw, lambda sids, draws: P.prepare_batch_store_elastic(store, sids, cfg, self.mean_sizes(), device=dev, mode=mode, draws=draws)
+        draw = lambda sid: P.prepare_scene(store.scene(sid), cfg, self.mean_size_arr, rng=rng, is_augment=self.is_augment, noise=self.noise,
+                                           device=dev)
+        return draw, lambda sids, samples: P.collate_scenes_device(samples, dev, mode)
 
     def build(self, idxs, rng, pyrng):
         """one batch of the samples `idxs`"""
-        dev = torch.device("cuda", torch.cuda.current_device()) if self.device is None else torch.device(self.device)
-        if self.label_free:
-            return self._build_label_free(idxs, rng, pyrng, dev)
-        if self.fused_active(dev):
-            return self._build_fused(idxs, rng, pyrng, dev)
-        if self.fused_elastic_active(dev):
-            return self._build_fused_elastic(idxs, rng, pyrng, dev)
-        prep = lambda sid: scene_prep.prepare_scene(self.store.scene(sid), self.cfg, self.mean_size_arr, rng=rng, is_augment=self.is_augment,
-                                                    noise=self.noise, device=dev)
-        if self.index is None:
-            return scene_prep.collate_scenes_device([prep(self.scene_ids[i]) for i in idxs], dev, self.voxel_mode)
         index = self.index
-        dev = lang_prep._device(index, dev)
-        draws, samples = [], []
-        for c in idxs:                                     # per sample: the description draws, then the scene's (pipeline.py:91-, :145-)
-            draws.append(lang_prep.draw_descriptions(index, c, rng, pyrng, self.is_augment, self.apply_word_erase))
-            samples.append(prep(index.scene_id(c)))
-        batch = scene_prep.collate_scenes_device(samples, dev, self.voxel_mode)
-        batch.update(lang_prep._launch(index, draws, idxs, batch, dev))
+        dev = torch.device("cuda", torch.cuda.current_device()) if self.device is None else torch.device(self.device)
+        if index is not None:
+            dev = lang_prep._device(index, dev)
+        draw, batch_of = self._scene_half(rng, dev)
+        sids = [self.sample_scene(i) for i in idxs]
+        descr, scene = [], None if draw is None else []
+        for c, sid in zip(idxs, sids):                     # per sample: the description draws, then the scene's (pipeline.py:91-, :145-)
+            if index is not None:
+                descr.append(lang_prep.draw_descriptions(index, c, rng, pyrng, self.is_augment, self.apply_word_erase))
+            if draw is not None:
+                scene.append(draw(sid))
+        batch = batch_of(sids, scene)
+        if index is not None:
+            batch.update(lang_prep._launch(index, descr, idxs, None if self.label_free else batch, dev))
         return batch
 
     def __iter__(self):
@@ -677,12 +648,12 @@ def build_loaders(cfg, device, rank=0, world=1, multiview=None, store_device=Non
         stores[split] = SceneStore.load(cfg, split, scans, store_device, multiview)
 
     loaders, indexes = {}, {}
+    loader = lambda index, split, role, **kw: PipelineLoader(cfg, stores[split], index, split, role, rank, world, seed, mean_size_arr=means,
+                                                             device=device, fused=fused, is_augment=bool(augment) and split == "train",
+                                                             fused_elastic=bool(augment) and bool(fused) and split == "train", **kw)
     if ("detector", "train") in lists:
         for split in ("train", "val"):
-            loaders[("detector", split)] = PipelineLoader(cfg, stores[split], None, split, "detector", rank, world, seed, mean_size_arr=means,
-                                                          device=device, scene_ids=lists[("detector", split)][1], fused=fused,
-                                                          is_augment=bool(augment) and split == "train",
-                                                          fused_elastic=bool(augment) and bool(fused) and split == "train")
+            loaders[("detector", split)] = loader(None, split, "detector", scene_ids=lists[("detector", split)][1])
         return loaders[("detector", "train")], loaders[("detector", "val")], None, stores
     vocabulary, glove = load_vocabulary(cfg, cfg.general.dataset)
     raw2label = lang_prep.raw2label_from_tsv(cfg.SCANNETV2_PATH.combine_file)
@@ -691,10 +662,7 @@ def build_loaders(cfg, device, rank=0, world=1, multiview=None, store_device=Non
         max_len = cfg.data.max_spk_len if role == "speaker" else cfg.data.max_lis_len
         indexes[(role, split)] = lang_prep.DescriptionIndex(raw, vocabulary, glove, max_len, cfg.data.num_des_per_scene, raw2label,
                                                             scan2cad_rotation=scan2cad, split=split, device=device)
-        loaders[(role, split)] = PipelineLoader(cfg, stores[split], indexes[(role, split)], split, role, rank, world, seed,
-                                                mean_size_arr=means, device=device, fused=fused,
-                                                is_augment=bool(augment) and split == "train",
-                                                fused_elastic=bool(augment) and bool(fused) and split == "train")
+        loaders[(role, split)] = loader(indexes[(role, split)], split, role)
     role = "listener" if m.no_captioning else "speaker"
     dataset = {split: _namespace(indexes[(role, split)], vocabulary, glove) for split in ("train", "val")}
     if m.no_captioning or m.no_grounding:

@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib, scene_prep
-from ._call import _ptr, _stream
+from ._call import _ptr, _stream, call
 
 SCANNET_CLASSES = ("cabinet", "bed", "chair", "sofa", "table", "door", "window", "bookshelf", "picture", "counter", "desk", "curtain",
                    "refrigerator", "shower curtain", "toilet", "sink", "bathtub", "others")
@@ -203,9 +203,8 @@ def _launch(index, draws, chunk_idxs, boxes, device):
     lens = torch.empty((B, Cn), dtype=torch.int64, device=device)
     ws = torch.empty(max(int(lib.d3_lang_features_ws_bytes(S, len(epos))), 1), dtype=torch.uint8, device=device)
     hp = lambda a: a.ctypes.data_as(C.c_void_p)
-    _lib.check(lib.d3_lang_features(_ptr(index.tokens), _ptr(index.lens), index.Nd, _ptr(index.glove), index.V, index.D, L_, index.unk,
-                                    hp(rows), hp(eptr), hp(epos), S, _ptr(feat), _ptr(ids), _ptr(lens), _ptr(ws), ws.numel(), st),
-               "d3_lang_features")
+    call("lang_features", _ptr(index.tokens), _ptr(index.lens), index.Nd, _ptr(index.glove), index.V, index.D, L_, index.unk,
+         hp(rows), hp(eptr), hp(epos), S, _ptr(feat), _ptr(ids), _ptr(lens), _ptr(ws), ws.numel(), st)
     meta = torch.from_numpy(np.stack([np.stack([d[k] for d in draws]) for k in _META])).to(device)
     out = {k: meta[i] for i, k in enumerate(_META)}
     out.update(lang_feat=feat, lang_len=lens, lang_ids=ids,
@@ -225,10 +224,10 @@ def _launch(index, draws, chunk_idxs, boxes, device):
     masks = torch.empty((B, R), dtype=torch.int64, device=device)
     ws2 = torch.empty(max(int(lib.d3_ref_targets_ws_bytes(B)), 1), dtype=torch.uint8, device=device)
     Ns = len(index.rot_off) - 1
-    _lib.check(lib.d3_ref_targets(_ptr(gid), _ptr(glab), _ptr(gbox), _ptr(out["object_id"]), B, Cn, R,
-                                  _ptr(index.rot_off_d) if Ns else None, _ptr(index.rot_ids_d) if Ns else None,
-                                  _ptr(index.rot_mats_d) if Ns else None, Ns, hp(scene), _ptr(ref), _ptr(corner), _ptr(rots), _ptr(masks),
-                                  _ptr(ws2), ws2.numel(), st), "d3_ref_targets")
+    call("ref_targets", _ptr(gid), _ptr(glab), _ptr(gbox), _ptr(out["object_id"]), B, Cn, R,
+         _ptr(index.rot_off_d) if Ns else None, _ptr(index.rot_ids_d) if Ns else None,
+         _ptr(index.rot_mats_d) if Ns else None, Ns, hp(scene), _ptr(ref), _ptr(corner), _ptr(rots), _ptr(masks),
+         _ptr(ws2), ws2.numel(), st)
     out.update(ref_box_label=ref, ref_box_corner_label=corner, scene_object_ids=gid, scene_object_rotations=rots,
                scene_object_rotation_masks=masks)
     index._host_args = (rows, eptr, epos, scene)          # the entry points' host arrays stay referenced until the next batch

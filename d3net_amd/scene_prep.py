@@ -21,6 +21,7 @@ reference wherever fp64 allows.  noise="device" instead takes ONE rng.randint dr
 device (Philox4x32-10 + Box-Muller): the training path then pays no host RNG for the grids, but the host RNG stream -- and so
 every later draw -- differs from the reference's.
 """
+import collections
 import ctypes as C
 import threading
 
@@ -172,13 +173,12 @@ def prepare_scene(scene, cfg, mean_size_arr, rng=None, is_augment=True, noise="d
     stats = torch.empty(12, dtype=torch.int64, device=device)
     m = augment_matrix(rng, d.transform) if is_augment else np.eye(3)
     mh = np.ascontiguousarray(m, dtype=np.float64)
-    _lib.check(L.d3_scene_transform(_ptr(xyz), n, mh.ctypes.data_as(C.c_void_p), float(scale), fp32, _ptr(y), _ptr(s), st),
-               "d3_scene_transform")
+    call("scene_transform", _ptr(xyz), n, mh.ctypes.data_as(C.c_void_p), float(scale), fp32, _ptr(y), _ptr(s), st)
 
     if elastic:
         seed = None if noise == "host" else int(rng.randint(0, 2 ** 31 - 1))
         for e, (gran, mag) in enumerate(elastic_params(scale)):
-            _lib.check(L.d3_scene_reduce(_ptr(s), None, n, _ptr(stats), st), "d3_scene_reduce")
+            call("scene_reduce", _ptr(s), None, n, _ptr(stats), st)
             bb = grid_shape(_decode(stats[0:3].cpu().numpy()), gran)             # sync: grid sizes
             X, Y, Z = (int(b) for b in bb)
             nbytes = L.d3_scene_elastic_ws_bytes(X, Y, Z)
@@ -188,13 +188,12 @@ def prepare_scene(scene, cfg, mean_size_arr, rng=None, is_augment=True, noise="d
                 grids = torch.from_numpy(np.stack(host_noise(rng, bb))).to(device)
             else:
                 grids = torch.empty((3, X, Y, Z), dtype=torch.float32, device=device)
-                _lib.check(L.d3_scene_noise(_ptr(grids), 3 * X * Y * Z, (seed << 1) | e, st), "d3_scene_noise")
+                call("scene_noise", _ptr(grids), 3 * X * Y * Z, (seed << 1) | e, st)
             axes = torch.from_numpy(np.concatenate(grid_axes(bb, gran))).to(device)
             ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
-            _lib.check(L.d3_scene_elastic(_ptr(s), n, _ptr(grids), _ptr(axes), X, Y, Z, float(mag), _ptr(ws), nbytes, st),
-                       "d3_scene_elastic")
+            call("scene_elastic", _ptr(s), n, _ptr(grids), _ptr(axes), X, Y, Z, float(mag), _ptr(ws), nbytes, st)
 
-    _lib.check(L.d3_scene_reduce(_ptr(s), _ptr(ids), n, _ptr(stats), st), "d3_scene_reduce")
+    call("scene_reduce", _ptr(s), _ptr(ids), n, _ptr(stats), st)
     sh = stats.cpu().numpy().view(np.uint64)                                         # sync: extent, id range
     mn, mx = _decode(sh[3:6]), _decode(sh[6:9])
     id_lo, id_hi = (int(v) - 2 ** 31 for v in sh[9:11]) if n else (-1, -1)
@@ -204,7 +203,7 @@ def prepare_scene(scene, cfg, mean_size_arr, rng=None, is_augment=True, noise="d
     if nbytes == 0:
         _range_error("scene_prep: %d points / instance id %d" % (n, id_hi))
     ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
-    _lib.check(L.d3_scene_offset(_ptr(s), n, _ptr(stats), fp32, st), "d3_scene_offset")
+    call("scene_offset", _ptr(s), n, _ptr(stats), fp32, st)
 
     flags, off, keep = None, None, n
     if elastic:
@@ -214,8 +213,7 @@ def prepare_scene(scene, cfg, mean_size_arr, rng=None, is_augment=True, noise="d
         def count(offset, rng_):
             o = np.ascontiguousarray(offset, dtype=np.float64)
             r = np.ascontiguousarray(rng_, dtype=np.float64)
-            _lib.check(L.d3_scene_crop_count(_ptr(s), n, o.ctypes.data_as(C.c_void_p), r.ctypes.data_as(C.c_void_p),
-                                             _ptr(flags_t), _ptr(cnt), st), "d3_scene_crop_count")
+            call("scene_crop_count", _ptr(s), n, o.ctypes.data_as(C.c_void_p), r.ctypes.data_as(C.c_void_p), _ptr(flags_t), _ptr(cnt), st)
             return int(cnt.item())                                               # sync: one per crop iteration
 
         off, keep = crop_loop(count, n, (mx - mn) - 0.0, d.max_num_point, d.full_scale[1], rng)
@@ -230,13 +228,11 @@ def prepare_scene(scene, cfg, mean_size_arr, rng=None, is_augment=True, noise="d
     feats2 = torch.empty((keep, Cf), dtype=torch.float32, device=device)
     sem2 = torch.empty(keep, dtype=torch.int32, device=device)
     ids2 = torch.empty(keep, dtype=torch.int32, device=device)
-    _lib.check(L.d3_scene_emit(_ptr(y), _ptr(s), _ptr(feats), Cf, _ptr(sem), _ptr(ids), n,
-                               _ptr(flags) if flags is not None else None,
-                               off.ctypes.data_as(C.c_void_p) if off is not None else None, fp32,
-                               _ptr(y2), _ptr(locs), _ptr(locs_scaled), _ptr(feats2), _ptr(sem2), _ptr(ids2),
-                               _ptr(ws), nbytes, st), "d3_scene_emit")
+    call("scene_emit", _ptr(y), _ptr(s), _ptr(feats), Cf, _ptr(sem), _ptr(ids), n, _ptr(flags),
+         off.ctypes.data_as(C.c_void_p) if off is not None else None, fp32,
+         _ptr(y2), _ptr(locs), _ptr(locs_scaled), _ptr(feats2), _ptr(sem2), _ptr(ids2), _ptr(ws), nbytes, st)
     if elastic:
-        _lib.check(L.d3_scene_relabel(_ptr(ids2), keep, id_hi, _ptr(ws), nbytes, st), "d3_scene_relabel")
+        call("scene_relabel", _ptr(ids2), keep, id_hi, _ptr(ws), nbytes, st)
 
     V = max(id_hi, 0) + 1
     info = torch.empty((keep, 12), dtype=torch.float32, device=device)
@@ -245,9 +241,8 @@ def prepare_scene(scene, cfg, mean_size_arr, rng=None, is_augment=True, noise="d
     gt_off = torch.zeros(V + 1, dtype=torch.int32, device=device)
     boxes = torch.zeros((R, 36), dtype=torch.float64, device=device)
     counts = torch.empty(4, dtype=torch.int32, device=device)
-    _lib.check(L.d3_scene_instances(_ptr(y2), _ptr(ids2), _ptr(sem2), keep, id_hi, fp32, R, _ptr(ms), _ptr(info), _ptr(npt),
-                                    _ptr(gt_idx), _ptr(gt_off), _ptr(boxes), _ptr(counts), _ptr(ws), nbytes, st),
-               "d3_scene_instances")
+    call("scene_instances", _ptr(y2), _ptr(ids2), _ptr(sem2), keep, id_hi, fp32, R, _ptr(ms), _ptr(info), _ptr(npt),
+         _ptr(gt_idx), _ptr(gt_off), _ptr(boxes), _ptr(counts), _ptr(ws), nbytes, st)
     K, Lp, _, _ = (int(v) for v in counts.cpu())                                    # sync: output shapes
 
     out = {"locs": locs, "locs_scaled": locs_scaled, "feats": feats2, "sem_labels": sem2, "instance_ids": ids2,
@@ -270,8 +265,99 @@ def prepare_scene(scene, cfg, mean_size_arr, rng=None, is_augment=True, noise="d
     return out
 
 
-_BOX_KEYS = ("center_label", "sem_cls_label", "heading_class_label", "heading_residual_label", "size_class_label",
-             "size_residual_label", "gt_bbox_object_id", "gt_bbox_label", "gt_bbox")
+# ------------------------------------------------------------------------------------------------ the batch's output tensors
+_Key = collections.namedtuple("_Key", "name dtype tail extent scene_dtype scene_tail gt")
+_f32, _i32, _i64 = torch.float32, torch.int32, torch.int64
+
+
+def _key(name, dtype, tail, extent, scene_dtype=None, scene_tail=None, gt=False):
+    return _Key(name, dtype, tail, extent, dtype if scene_dtype is None else scene_dtype, tail if scene_tail is None else scene_tail, gt)
+
+
+# The 20 tensors every labelled batch kernel writes, in the C ABI's order (`BpOut`, csrc/scene_prep.h; the `out_host` pointer
+# array of d3_collate_scenes / d3_batch_prepare / d3_batch_elastic).  Per key: the batch dtype, the trailing shape ("C" the
+# feature columns) and the leading extent -- "points", "instances", "instances+1", "entries" (GT proposal entries), "B+1" or "B,R"
+# -- then what a per-scene sample of `prepare_scene` holds where it differs (32-bit labels and a three-column float locs_scaled:
+# the kernels widen them and add the batch index), and whether the key exists only with data.requires_gt_mask (slot 0 otherwise).
+_BATCH_KEYS = (
+    _key("locs", _f32, (3,), "points"),
+    _key("locs_scaled", _i64, (4,), "points", _f32, (3,)),
+    _key("feats", _f32, ("C",), "points"),
+    _key("sem_labels", _i64, (), "points", _i32),
+    _key("instance_ids", _i64, (), "points", _i32),
+    _key("instance_info", _f32, (12,), "points"),
+    _key("instance_num_point", _i32, (), "instances"),
+    _key("gt_proposals_idx", _i32, (2,), "entries", gt=True),
+    _key("gt_proposals_offset", _i32, (), "instances+1", gt=True),
+    _key("batch_offsets", _i32, (), "B+1"),
+    _key("instance_offsets", _i32, (), "B+1"),
+    _key("center_label", _f32, (3,), "B,R"),
+    _key("sem_cls_label", _i64, (), "B,R"),
+    _key("heading_class_label", _i64, (), "B,R"),
+    _key("heading_residual_label", _f32, (), "B,R"),
+    _key("size_class_label", _i64, (), "B,R"),
+    _key("size_residual_label", _f32, (3,), "B,R"),
+    _key("gt_bbox_object_id", _i64, (), "B,R"),
+    _key("gt_bbox_label", _i64, (), "B,R"),
+    _key("gt_bbox", _f32, (8, 3), "B,R"),
+)
+_SCENE_KEYS = tuple(k for k in _BATCH_KEYS if k.extent != "B+1")       # a per-scene sample's tensors: d3_collate_scenes' pointer columns
+_BOX_KEYS = tuple(k.name for k in _BATCH_KEYS if k.extent == "B,R")     # the stacked box labels
+
+
+def _shape(lead, tail, Cf):
+    return lead + tuple(Cf if t == "C" else t for t in tail)
+
+
+def _alloc_batch(device, B, R, Cf, has_gt, points, instances, entries):
+    """The labelled batch's uninitialised output tensors for the given extents (the elastic path passes upper bounds and cuts
+    afterwards) -> (data dict in `_BATCH_KEYS` order, the (20,) uint64 pointer array of the C ABI).  Without has_gt the GT
+    proposal keys are absent and their pointer slots 0."""
+    lead = {"points": (points,), "instances": (instances,), "instances+1": (instances + 1,), "entries": (entries,), "B+1": (B + 1,),
+            "B,R": (B, R)}
+    new = lambda shape, dt: torch.empty(shape, dtype=dt, device=device)
+    data = {k.name: new(_shape(lead[k.extent], k.tail, Cf), k.dtype) for k in _BATCH_KEYS if has_gt or not k.gt}
+    return data, np.array([data[k.name].data_ptr() if k.name in data else 0 for k in _BATCH_KEYS], np.uint64)
+
+
+_TABLE_RING = 4
+_rings = {}
+
+
+def _pinned(tag, nbytes, device):
+    """A pinned host buffer of at least `nbytes` with its event, handed out round-robin from a ring of `_TABLE_RING` per (tag,
+    device, host thread, stream), like the workspace.  The caller records the event behind the asynchronous copy that reads or
+    fills the buffer; an entry comes round again only after that copy has run (the wait happens only when the whole ring is
+    still in flight: the host may run several batches ahead of the device).  -> (uint8 tensor, event)"""
+    key = (tag, device.index, threading.get_ident(), _stream().value or 0)
+    ring = _rings.setdefault(key, {"next": 0, "ents": [None] * _TABLE_RING})
+    k = ring["next"]
+    ring["next"] = (k + 1) % _TABLE_RING
+    ent = ring["ents"][k]
+    if ent is None or ent[0].numel() < nbytes:
+        ent = ring["ents"][k] = (torch.empty(int(nbytes * 1.25) + 1024, dtype=torch.uint8).pin_memory(), torch.cuda.Event())
+    elif not ent[1].query():
+        ent[1].synchronize()
+    return ent
+
+
+def _store_device(store, device, who):
+    """the device of a resident store; a pinned-host store, or a `device` that names another card, is a ValueError"""
+    dev = store.points.device
+    if dev.type != "cuda":
+        raise ValueError("%s: the store is pinned host memory; this path serves the resident store only" % who)
+    if device is not None and torch.device(device).type != "cpu" and torch.device(device).index not in (None, dev.index):
+        raise ValueError("%s: the store is on %s, not on %s" % (who, dev, device))
+    return dev
+
+
+def _mean_sizes_on(mean_size_arr, dev, who):
+    """the (18,3) mean-size table as a float64 tensor on `dev`; nothing is uploaded when it already is one"""
+    ms = mean_size_arr if torch.is_tensor(mean_size_arr) and mean_size_arr.device == dev and mean_size_arr.dtype == torch.float64 \
+        else _dev_tensor(np.asarray(mean_size_arr, dtype=np.float64), torch.float64, dev)
+    if ms.numel() < 54:
+        raise ValueError("%s: mean_size_arr has %d values, 18 x 3 expected" % (who, ms.numel()))
+    return ms
 
 
 def collate_scenes(samples, device, mode=4):
@@ -317,26 +403,6 @@ def collate_scenes(samples, device, mode=4):
     return data
 
 
-_POINT_KEYS = ("locs", "locs_scaled", "feats", "sem_labels", "instance_ids", "instance_info", "instance_num_point",
-               "gt_proposals_idx", "gt_proposals_offset")
-_I64_BOX = ("sem_cls_label", "heading_class_label", "size_class_label", "gt_bbox_object_id", "gt_bbox_label")
-_BOX_TAIL = {"center_label": (3,), "size_residual_label": (3,), "gt_bbox": (8, 3)}
-_tables = {}
-
-
-def _collate_table(nbytes, device):
-    """the pinned table of one batch, per (device, host thread, stream) like the workspace, with the event that tells when its
-    copy to the device has run"""
-    key = (device.index, threading.get_ident(), _stream().value or 0)
-    ent = _tables.get(key)
-    if ent is None or ent[0].numel() < nbytes:
-        ent = (torch.empty(int(nbytes * 1.25) + 1024, dtype=torch.uint8).pin_memory(), torch.cuda.Event())
-        _tables[key] = ent
-    else:
-        ent[1].synchronize()            # the earlier batch's copy (long done: prepare_scene has read back since)
-    return ent
-
-
 def collate_scenes_device(samples, device, mode=4):
     """`collate_scenes` as ONE launch (csrc/collate.hip, `d3_collate_scenes`): the same keys, dtypes, shapes and bits, from the
     per-scene dicts of `prepare_scene`.  The per-scene pointers and counts go up as one pinned table in one asynchronous copy;
@@ -353,23 +419,18 @@ def collate_scenes_device(samples, device, mode=4):
     if any(("gt_proposals_idx" in s) != has_gt for s in samples):
         raise ValueError("collate_scenes_device: GT proposal lists on some samples only")
     Cf, R = samples[0]["feats"].shape[1], samples[0]["center_label"].shape[0]
-    f32, i32, i64 = torch.float32, torch.int32, torch.int64
-    keep, ptrs, counts = [], np.zeros((B, len(_POINT_KEYS) + len(_BOX_KEYS)), np.uint64), np.zeros((B, 3), np.int32)
+    keep, ptrs, counts = [], np.zeros((B, len(_SCENE_KEYS)), np.uint64), np.zeros((B, 3), np.int32)
     for i, s in enumerate(samples):
         n, K = s["locs"].shape[0], int(s["num_instance"])
         Lp = s["gt_proposals_idx"].shape[0] if has_gt else 0
-        want = {"locs": (f32, (n, 3)), "locs_scaled": (f32, (n, 3)), "feats": (f32, (n, Cf)), "sem_labels": (i32, (n,)),
-                "instance_ids": (i32, (n,)), "instance_info": (f32, (n, 12)), "instance_num_point": (i32, (K,))}
-        if has_gt:
-            want.update(gt_proposals_idx=(i32, (Lp, 2)), gt_proposals_offset=(i32, (K + 1,)))
-        want.update({k: (i64 if k in _I64_BOX else f32, (R,) + _BOX_TAIL.get(k, ())) for k in _BOX_KEYS})
-        for j, k in enumerate(_POINT_KEYS + _BOX_KEYS):
-            if k not in want:
+        lead = {"points": (n,), "instances": (K,), "instances+1": (K + 1,), "entries": (Lp,), "B,R": (R,)}
+        for j, k in enumerate(_SCENE_KEYS):
+            if k.gt and not has_gt:
                 continue
-            t = s[k]
-            if t.dtype != want[k][0] or tuple(t.shape) != want[k][1] or t.device != device:
+            t, dt, shape = s[k.name], k.scene_dtype, _shape(lead[k.extent], k.scene_tail, Cf)
+            if t.dtype != dt or tuple(t.shape) != shape or t.device != device:
                 raise ValueError("collate_scenes_device: sample %d %s is %s %s on %s, expected %s %s on %s"
-                                 % (i, k, t.dtype, tuple(t.shape), t.device, want[k][0], want[k][1], device))
+                                 % (i, k.name, t.dtype, tuple(t.shape), t.device, dt, shape, device))
             t = t.contiguous()
             keep.append(t)
             ptrs[i, j] = t.data_ptr()
@@ -377,21 +438,13 @@ def collate_scenes_device(samples, device, mode=4):
     N, I, Lt = (int(v) for v in counts.sum(0, dtype=np.int64))
     if max(N, I, Lt) >= 2 ** 31:
         _range_error("collate_scenes_device: %d points / %d instances / %d proposal entries" % (N, I, Lt))
-    new = lambda shape, dt: torch.empty(shape, dtype=dt, device=device)
-    data = {"locs": new((N, 3), f32), "locs_scaled": new((N, 4), i64), "feats": new((N, Cf), f32), "sem_labels": new((N,), i64),
-            "instance_ids": new((N,), i64), "instance_info": new((N, 12), f32), "instance_num_point": new((I,), i32)}
-    if has_gt:
-        data.update(gt_proposals_idx=new((Lt, 2), i32), gt_proposals_offset=new((I + 1,), i32))
-    data.update(batch_offsets=new((B + 1,), i32), instance_offsets=new((B + 1,), i32))
-    data.update({k: new((B, R) + _BOX_TAIL.get(k, ()), i64 if k in _I64_BOX else f32) for k in _BOX_KEYS})
-    out = np.array([data[k].data_ptr() if k in data else 0
-                    for k in _POINT_KEYS + ("batch_offsets", "instance_offsets") + _BOX_KEYS], np.uint64)
+    data, out = _alloc_batch(device, B, R, Cf, has_gt, N, I, Lt)
     hp = lambda a: a.ctypes.data_as(C.c_void_p)
     with _on(device):
         nbytes = int(_lib.lib().d3_collate_table_bytes(B))
         if nbytes == 0:
             _range_error("collate_scenes_device: %d scenes" % B)
-        table, copied = _collate_table(nbytes, device)
+        table, copied = _pinned("table", nbytes, device)
         ws = _workspace(nbytes, device, "collate")
         call("collate_scenes", hp(ptrs), hp(counts), B, Cf, R, int(has_gt), hp(out), C.c_void_p(table.data_ptr()), _ptr(ws), nbytes,
              _stream())
@@ -424,25 +477,6 @@ def batch_plan(offsets, table_offsets, scalars, rows):
             "N": int(n.sum()), "I": int(scalars[rows, 2].sum()), "L": int(scalars[rows, 3].sum()), "V": int(V.sum())}
 
 
-_TABLE_RING = 4
-_batch_tables = {}
-
-
-def _batch_table(nbytes, device):
-    """`_collate_table` for a path that never reads back: a ring of pinned tables per (device, host thread, stream), so that the
-    host, which may run several batches ahead of the device, waits for a table's earlier copy only when the whole ring is in flight"""
-    key = (device.index, threading.get_ident(), _stream().value or 0)
-    ring = _batch_tables.setdefault(key, {"next": 0, "ents": [None] * _TABLE_RING})
-    k = ring["next"]
-    ring["next"] = (k + 1) % _TABLE_RING
-    ent = ring["ents"][k]
-    if ent is None or ent[0].numel() < nbytes:
-        ent = ring["ents"][k] = (torch.empty(int(nbytes * 1.25) + 1024, dtype=torch.uint8).pin_memory(), torch.cuda.Event())
-    elif not ent[1].query():
-        ent[1].synchronize()
-    return ent
-
-
 def prepare_batch_store(store, scene_ids, cfg, mean_size_arr, rng=None, is_augment=False, device=None, mode=4, matrices=None):
     """The batch `collate_scenes_device([prepare_scene(store.scene(s), ...) for s in scene_ids])` builds -- the same keys, dtypes,
     shapes and bits -- straight from a resident `dataset.SceneStore` and its `instance_index()`: one table copy and three launches
@@ -456,10 +490,8 @@ def prepare_batch_store(store, scene_ids, cfg, mean_size_arr, rng=None, is_augme
     Only where `fused_applicable` holds: the elastic / crop path and a pinned-host store raise ValueError."""
     if elastic_enabled(cfg, is_augment):
         raise ValueError("prepare_batch_store: the augmented detector-only path (elastic distortion, crop) is prepare_scene's")
-    ix = store.instance_index()
-    dev = store.points.device
-    if device is not None and torch.device(device).type != "cpu" and torch.device(device).index not in (None, dev.index):
-        raise ValueError("prepare_batch_store: the store is on %s, not on %s" % (dev, device))
+    ix = store.instance_index()                        # a pinned-host store raises ValueError here
+    dev = _store_device(store, device, "prepare_batch_store")
     B = len(scene_ids)
     if B < 1:
         raise ValueError("prepare_batch_store: no scenes")
@@ -475,27 +507,15 @@ def prepare_batch_store(store, scene_ids, cfg, mean_size_arr, rng=None, is_augme
     N, I, Lt = plan["N"], plan["I"], plan["L"]
     if max(N, I, Lt) >= 2 ** 31:
         _range_error("prepare_batch_store: %d points / %d instances / %d proposal entries" % (N, I, Lt))
-    ms = mean_size_arr if torch.is_tensor(mean_size_arr) and mean_size_arr.device == dev and mean_size_arr.dtype == torch.float64 \
-        else _dev_tensor(np.asarray(mean_size_arr, dtype=np.float64), torch.float64, dev)
-    if ms.numel() < 54:
-        raise ValueError("prepare_batch_store: mean_size_arr has %d values, 18 x 3 expected" % ms.numel())
-    f32, i32, i64 = torch.float32, torch.int32, torch.int64
-    new = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
-    data = {"locs": new((N, 3), f32), "locs_scaled": new((N, 4), i64), "feats": new((N, Cf), f32), "sem_labels": new((N,), i64),
-            "instance_ids": new((N,), i64), "instance_info": new((N, 12), f32), "instance_num_point": new((I,), i32)}
-    if has_gt:
-        data.update(gt_proposals_idx=new((Lt, 2), i32), gt_proposals_offset=new((I + 1,), i32))
-    data.update(batch_offsets=new((B + 1,), i32), instance_offsets=new((B + 1,), i32))
-    data.update({k: new((B, R) + _BOX_TAIL.get(k, ()), i64 if k in _I64_BOX else f32) for k in _BOX_KEYS})
-    out = np.array([data[k].data_ptr() if k in data else 0
-                    for k in _POINT_KEYS + ("batch_offsets", "instance_offsets") + _BOX_KEYS], np.uint64)
+    ms = _mean_sizes_on(mean_size_arr, dev, "prepare_batch_store")
+    data, out = _alloc_batch(dev, B, R, Cf, has_gt, N, I, Lt)
     hp = lambda a: a.ctypes.data_as(C.c_void_p)
     with _on(dev):
         L = _lib.lib()
         tbytes, nbytes = int(L.d3_batch_prepare_table_bytes(B)), int(L.d3_batch_prepare_ws_bytes(B, plan["V"]))
         if tbytes == 0 or nbytes == 0:
             _range_error("prepare_batch_store: %d scenes" % B)
-        table, copied = _batch_table(tbytes, dev)
+        table, copied = _pinned("table", tbytes, dev)
         ws = _workspace(nbytes, dev, "batch_prep")
         call("batch_prepare", _ptr(store.points), _ptr(store.feats), _ptr(store.sem_labels), _ptr(store.instance_ids),
              store.points.shape[0], _ptr(ix.hist), _ptr(ix.rank), _ptr(ix.start), _ptr(ix.sorted), ix.hist.shape[0],
@@ -508,16 +528,6 @@ def prepare_batch_store(store, scene_ids, cfg, mean_size_arr, rng=None, is_augme
 
 # ------------------------------------------------------------------------------------------------ the elastic / crop batch from the store
 READBACK_COLUMNS = ("kept", "K", "Lp", "X1", "Y1", "Z1", "X2", "Y2", "Z2", "crop_iters")
-_readback_tables = {}
-
-
-def _readback_table(B, device):
-    """the pinned host image of one batch's read-back table, per (device, host thread, stream)"""
-    key = (device.index, threading.get_ident(), _stream().value or 0)
-    t = _readback_tables.get(key)
-    if t is None or t.shape[0] < B:
-        t = _readback_tables[key] = torch.empty((max(B, 8), len(READBACK_COLUMNS)), dtype=torch.int32).pin_memory()
-    return t[:B]
 
 
 def elastic_applicable(cfg, is_augment, store):
@@ -528,13 +538,15 @@ def elastic_applicable(cfg, is_augment, store):
 
 def elastic_batch_queue(store, scene_ids, cfg, mean_size_arr, rng=None, device=None, draws=None):
     """The queueing half of `prepare_batch_store_elastic`: the draws, the host bound of the noise grids, one table copy and every
-    launch, with no wait for the device.  -> the pending batch `elastic_batch_finish` completes."""
+    launch, with no wait for the device.  -> the pending batch `elastic_batch_finish` completes.
+
+    A caller may queue ahead: every pending batch has its own pinned image of the read-back table, from a ring of `_TABLE_RING`
+    per (device, host thread, stream).  So at most `_TABLE_RING - 1` batches may be queued and unfinished there when another is
+    queued; beyond that the oldest pending batch's image is handed to the new one and that batch must not be finished any more."""
     if not elastic_enabled(cfg, True):
         raise ValueError("prepare_batch_store_elastic: no elastic distortion in this configuration (a language mode): prepare_batch_store's")
     ix = store.instance_index()                        # a pinned-host store raises ValueError here
-    dev = store.points.device
-    if device is not None and torch.device(device).type != "cpu" and torch.device(device).index not in (None, dev.index):
-        raise ValueError("prepare_batch_store_elastic: the store is on %s, not on %s" % (dev, device))
+    dev = _store_device(store, device, "prepare_batch_store_elastic")
     B = len(scene_ids)
     if B < 1:
         raise ValueError("prepare_batch_store_elastic: no scenes")
@@ -568,10 +580,7 @@ def elastic_batch_queue(store, scene_ids, cfg, mean_size_arr, rng=None, device=N
         _range_error("prepare_batch_store_elastic: noise grid bound %d" % int(bounds.max()))
     slots = np.ascontiguousarray(np.concatenate([n[:, None], V[:, None], bounds], 1).astype(np.int32))
     N, Vt = int(n.sum()), int(V.sum())
-    ms = mean_size_arr if torch.is_tensor(mean_size_arr) and mean_size_arr.device == dev and mean_size_arr.dtype == torch.float64 \
-        else _dev_tensor(np.asarray(mean_size_arr, dtype=np.float64), torch.float64, dev)
-    if ms.numel() < 54:
-        raise ValueError("prepare_batch_store_elastic: mean_size_arr has %d values, 18 x 3 expected" % ms.numel())
+    ms = _mean_sizes_on(mean_size_arr, dev, "prepare_batch_store_elastic")
     hp = lambda a: a.ctypes.data_as(C.c_void_p)
     with _on(dev):
         L = _lib.lib()
@@ -580,27 +589,18 @@ def elastic_batch_queue(store, scene_ids, cfg, mean_size_arr, rng=None, device=N
         if tbytes == 0 or nbytes == 0:                 # refused before anything is allocated or queued
             _range_error("prepare_batch_store_elastic: %d scenes, %d points, noise grid bounds up to %s, %d crop iterations"
                          % (B, N, bounds.max(0).tolist(), T))
-        f32, i32, i64 = torch.float32, torch.int32, torch.int64
-        new = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
-        data = {"locs": new((N, 3), f32), "locs_scaled": new((N, 4), i64), "feats": new((N, Cf), f32), "sem_labels": new((N,), i64),
-                "instance_ids": new((N,), i64), "instance_info": new((N, 12), f32), "instance_num_point": new((Vt,), i32)}
-        if has_gt:
-            data.update(gt_proposals_idx=new((N, 2), i32), gt_proposals_offset=new((Vt + 1,), i32))
-        data.update(batch_offsets=new((B + 1,), i32), instance_offsets=new((B + 1,), i32))
-        data.update({k: new((B, R) + _BOX_TAIL.get(k, ()), i64 if k in _I64_BOX else f32) for k in _BOX_KEYS})
-        out = np.array([data[k].data_ptr() if k in data else 0
-                        for k in _POINT_KEYS + ("batch_offsets", "instance_offsets") + _BOX_KEYS], np.uint64)
-        readback = new((B, len(READBACK_COLUMNS)), i32)
-        table, copied = _batch_table(tbytes, dev)
+        data, out = _alloc_batch(dev, B, R, Cf, has_gt, N, Vt, N)      # the static upper bounds; `elastic_batch_finish` cuts
+        readback = torch.empty((B, len(READBACK_COLUMNS)), dtype=torch.int32, device=dev)
+        table, copied = _pinned("table", tbytes, dev)
         ws = _workspace(nbytes, dev, "batch_elastic")
         call("batch_elastic", _ptr(store.points), _ptr(store.feats), _ptr(store.sem_labels), _ptr(store.instance_ids),
              store.points.shape[0], hp(row0), hp(slots), hp(mats), hp(seeds), hp(crop_u), B, Cf, R, T, int(has_gt), float(scale),
              grans[0], grans[1], float(params[0][1]), float(params[1][1]), float(crop_scale), int(d.max_num_point), _ptr(ms), hp(out),
              _ptr(readback), C.c_void_p(table.data_ptr()), _ptr(ws), ws.numel(), _stream())
         copied.record()
-        host = _readback_table(B, dev)
+        image, done = _pinned("readback", readback.numel() * 4, dev)
+        host = image[:readback.numel() * 4].view(torch.int32).view(readback.shape)
         host.copy_(readback, non_blocking=True)        # queued behind the launches; `elastic_batch_finish` waits for it
-        done = torch.cuda.Event()
         done.record()
     return {"data": data, "readback": host, "done": done, "bounds": bounds, "B": B, "has_gt": has_gt, "keep": (readback, ms)}
 
@@ -660,9 +660,7 @@ def store_extents(store, scale):
     and axis the kernels' order-preserving encoding (`_decode`) of min(fl32(x * fl32(scale))) -- `points.min(0)` of
     pipeline.py:352-380, a constant of the (store, scale) pair since that branch draws nothing and drops no point.
     `SceneStore.extents` caches it."""
-    dev, S = store.points.device, len(store)
-    if dev.type != "cuda":
-        raise ValueError("store_extents: the store is pinned host memory; the table serves the resident store only")
+    dev, S = _store_device(store, None, "store_extents"), len(store)
     ext = torch.empty((S, 3), dtype=torch.int64, device=dev)
     offsets = np.ascontiguousarray(store.offsets, dtype=np.int64)
     with _on(dev):
@@ -670,7 +668,7 @@ def store_extents(store, scale):
         tbytes, nbytes = int(L.d3_store_extents_table_bytes(S)), int(L.d3_store_extents_ws_bytes(S))
         if tbytes == 0 or nbytes == 0:
             _range_error("store_extents: %d scenes" % S)
-        table, copied = _batch_table(tbytes, dev)
+        table, copied = _pinned("table", tbytes, dev)
         ws = _workspace(nbytes, dev, "store_extents")
         call("store_extents", _ptr(store.points), store.points.shape[0], offsets.ctypes.data_as(C.c_void_p), S, float(scale), _ptr(ext),
              C.c_void_p(table.data_ptr()), _ptr(ws), ws.numel(), _stream())
@@ -688,11 +686,7 @@ def prepare_points_store(store, scene_ids, cfg, device=None, mode=4):
     The store's labels, if it has any, are ignored; a scene may fill several slots.  A pinned-host store raises ValueError.
     The extents launch covers every scene of the store, so a store that holds a scene without points (a labelled store may) is
     refused by that scene's name on the first call, whether or not the batch names it."""
-    dev = store.points.device
-    if dev.type != "cuda":
-        raise ValueError("prepare_points_store: the store is pinned host memory; this path serves the resident store only")
-    if device is not None and torch.device(device).type != "cpu" and torch.device(device).index not in (None, dev.index):
-        raise ValueError("prepare_points_store: the store is on %s, not on %s" % (dev, device))
+    dev = _store_device(store, device, "prepare_points_store")
     B = len(scene_ids)
     if B < 1:
         raise ValueError("prepare_points_store: no scenes")
@@ -713,7 +707,7 @@ def prepare_points_store(store, scene_ids, cfg, device=None, mode=4):
         tbytes, nbytes = int(L.d3_points_batch_table_bytes(B)), int(L.d3_points_batch_ws_bytes(B))
         if tbytes == 0 or nbytes == 0:
             _range_error("prepare_points_store: %d scenes" % B)
-        table, copied = _batch_table(tbytes, dev)
+        table, copied = _pinned("table", tbytes, dev)
         ws = _workspace(nbytes, dev, "points_batch")
         call("points_batch", _ptr(store.points), _ptr(store.feats), store.points.shape[0], _ptr(ext), len(store), hp(row0), hp(srow), hp(n),
              B, Cf, float(scale), _ptr(data["locs"]), _ptr(data["locs_scaled"]), _ptr(data["feats"]), _ptr(data["batch_offsets"]),

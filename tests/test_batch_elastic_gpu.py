@@ -235,6 +235,32 @@ def test_queueing_half_never_waits(dev, stores):
     assert batch["locs"].shape[0] == int(info["readback"][:, COL["kept"]].sum()) < sum(store.num_points(s) for s in ids)
 
 
+def test_two_batches_in_flight_keep_their_own_read_back(dev, stores):
+    """Queue two batches, then finish them in order: each equals its solo run, key by key and in its read-back rows.  The first
+    batch has a cropped slot and the second none, so their read-back tables differ.  With ONE host image of the read-back table
+    per (device, thread, stream), as before the pinned ring, this test fails: the second batch's copy lands in the image the
+    first batch reads, so the first is checked against the second's grid shapes (here a RuntimeError from the bound check) or
+    cut to the second's `kept / K / Lp` (a wrong length, not an access out of bounds: the outputs are allocated at the scenes'
+    full sizes)."""
+    store, cfg = stores[3], _cfg(max_pt=1000)
+    r = np.random.RandomState(8)
+    jobs = [(list(ids), [(SP.augment_matrix(r, cfg.data.transform), int(r.randint(0, 2 ** 31 - 1))) for _ in ids])
+            for ids in (("n2500", "n257"), ("n255", "n256"))]
+    want, infos = [], []
+    for ids, draws in jobs:
+        infos.append({})
+        want.append(SP.prepare_batch_store_elastic(store, ids, cfg, MSA, device=dev, mode=cfg.data.mode, draws=draws, info=infos[-1]))
+    rb0, rb1 = infos[0]["readback"], infos[1]["readback"]
+    assert rb0[0, COL["crop_iters"]] > 0 and 0 < rb0[0, COL["kept"]] < 2500 and (rb1[:, COL["crop_iters"]] == 0).all()
+    assert not np.array_equal(rb0[:, :3], rb1[:, :3])        # the counts `elastic_batch_finish` cuts by differ
+    pending = [SP.elastic_batch_queue(store, ids, cfg, MSA, device=dev, draws=draws) for ids, draws in jobs]
+    torch.cuda.synchronize()                                 # both read-back copies have landed before the first batch is finished
+    for p, w, solo in zip(pending, want, infos):
+        info = {}
+        _assert_batches_equal(SP.elastic_batch_finish(p, cfg.data.mode, info), w)
+        assert np.array_equal(info["readback"], solo["readback"]) and np.array_equal(info["bounds"], solo["bounds"])
+
+
 # ---------------------------------------------------------------------------------------------------- loader and command
 @pytest.mark.parametrize("rank", [0, 1])
 def test_loader_passes(dev, rank):

@@ -109,7 +109,7 @@ def main():
     sids, mode = [index.scene_id(c) for c in idxs], int(cfg.data.mode)
     per_scene = lambda: SP.collate_scenes_device([SP.prepare_scene(store.scene(s), cfg, msa, rng=gens[False][0], is_augment=False, device=dev)
                                                   for s in sids], dev, mode)
-    from_store = lambda: SP.prepare_batch_store(store, sids, cfg, loaders[True]._mean_size_dev, is_augment=False, device=dev, mode=mode)
+    from_store = lambda: SP.prepare_batch_store(store, sids, cfg, loaders[True].mean_sizes(), is_augment=False, device=dev, mode=mode)
     vox = device_ops(lambda: pointgroup_ops.voxelization_idx(b["locs_scaled"], 4, mode))
     half = {False: device_ops(per_scene), True: device_ops(from_store)}
     vox_ms = []

@@ -76,7 +76,7 @@ def main():
     mode = int(cfg.data.mode)
     vox = device_ops(lambda: pointgroup_ops.voxelization_idx(b["locs_scaled"], 4, mode))
     info = {}
-    SP.prepare_batch_store_elastic(store, [store.scene_ids[i] for i in idxs], cfg, loaders[True]._mean_sizes(), rng=gens[True][0], device=dev,
+    SP.prepare_batch_store_elastic(store, [store.scene_ids[i] for i in idxs], cfg, loaders[True].mean_sizes(), rng=gens[True][0], device=dev,
                                    mode=mode, info=info)
     n, Cf = np.diff(store.offsets), int(store.feats.shape[1])
     slots = np.ascontiguousarray(np.concatenate([n[:, None], (np.maximum(store.instance_index().scalars[:, 1], 0) + 1)[:, None], info["bounds"]],
